@@ -15,6 +15,11 @@ ctx's communication stream, overlapping the next step's index build) -- assemble
 
 Prints ONE JSON line (rank 0).  value = edges checked per second, whole job; r-disc queries per second is
 reported next to it in "submetrics".
+
+A plain run sets up, warms up, times --steps steps and prints that line.  --full adds what takes work of its own beyond the
+headline: the CPU baselines, the cold-call and whole-solve submetrics, the free-edge checksum of the last step ("consistency")
+and, for cfg5, the adaptive-IS timing.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float64 / float32, at most 64 MB; a seeded sample of the entries of a larger graph).
 """
 import argparse
 import json
@@ -37,6 +42,83 @@ FP16_MFMA_PEAK_TFLOPS = 2500.0 # MI355X_MICROARCH.md: dense BF16/FP16 MFMA ~2.5 
 GATHER_CEILING_ROWS_PER_S = 4.51e10      # measured: 1e8 random 48-byte rows of a 48 MB array in 2.219 ms (profiles/r01_ubench_fetch_calib.txt)
 GATHER_CEILING_L2_ROWS_PER_S = 1.9e11    # the same gather when the rows it touches are L2-resident (profiles/r02_ubench_gather_variants.txt)
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "traffic.json")      # written by tools/pmc_traffic.py from a rocprofv3 --pmc run
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_COLUMNS = 1 << 20         # per-column arrays of a larger sample set: this many columns (fixed positions, drawn from DUMP_SEED)
+DUMP_ENTRIES = 1 << 20         # per-entry arrays of a larger graph: at most this many entries (the same way)
+DUMP_SEED = 20250101
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy (float32 / float64 only, DUMP_MAX_BYTES in all)."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "outputs of %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+def dump_positions(n, k):
+    """k sorted positions of range(n) drawn from DUMP_SEED (duplicates dropped); all of range(n) when n <= k."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=k))
+
+
+def column_outputs(N, arrays):
+    """Per-column arrays (name -> host array of N) at dump_positions(N, DUMP_COLUMNS), as float64; column_position when sampled."""
+    cols = dump_positions(N, DUMP_COLUMNS)
+    out = {} if len(cols) == N else {"column_position": cols.astype(np.float64)}
+    out.update({k: np.asarray(v)[cols].astype(np.float64) for k, v in arrays.items()})
+    return out
+
+
+def csc_outputs(dev, N, nnz, colptr_p, rowval_p, free_p, per_entry):
+    """The CSC + free-edge mask a step left in HBM (colptr int64[N+1] and rowval int32[nnz], 0-based; mask uint64 words), as the
+    arrays --dump-outputs writes.  Per column (column_outputs): column_start (colptr), degree, free_edges.  Per entry, at sorted
+    positions drawn from DUMP_SEED (every entry when they fit): entry_position, rowval, free (0 / 1) and every array of per_entry
+    (name -> (device pointer, typestr)).  The sample is taken on the device: only the written values cross PCIe; the mask is read
+    word by word (set bits per word from a byte table), never expanded to one value per entry."""
+    import torch
+    from motionplanning_jl_amd.distributed import DevArray
+    torch.cuda.synchronize()
+    colptr = torch.as_tensor(DevArray(colptr_p, N + 1, "<i8"), device=dev)
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    words = torch.as_tensor(DevArray(free_p, (nnz + 63) // 64, "<i8"), device=dev) if nnz > 0 else zero
+    ones = torch.tensor([bin(b).count("1") for b in range(256)], dtype=torch.int64, device=dev)      # set bits of a byte
+    word_prefix = torch.cat([zero, torch.cumsum(ones[words.view(torch.uint8).long()].view(-1, 8).sum(1), 0)])
+
+    def free_before(q):
+        """Set bits of the mask below each position of q (int64, 0 <= q <= nnz): whole words from word_prefix, then the low
+        (q & 63) bits of q's own word, byte by byte."""
+        b = words[torch.clamp(q >> 6, max=words.numel() - 1)].view(torch.uint8).view(-1, 8).long()
+        k = (q & 63).unsqueeze(1)
+        j = torch.arange(8, device=dev)
+        low = torch.where(j < (k >> 3), b, torch.where(j == (k >> 3), b & ((torch.ones_like(k) << (k & 7)) - 1), torch.zeros_like(b)))
+        return word_prefix[q >> 6] + ones[low].sum(1)
+
+    cp = colptr.cpu().numpy()
+    out = column_outputs(N, {"column_start": cp[:-1], "degree": np.diff(cp),
+                             "free_edges": torch.diff(free_before(colptr)).cpu().numpy()})
+    entry_bytes = 8 + 8 + 4 + sum(4 if t.endswith("1") else 8 for _, t in per_entry.values())
+    pos = dump_positions(nnz, min(DUMP_ENTRIES, (DUMP_MAX_BYTES - sum(v.nbytes for v in out.values())) // entry_bytes))
+    out["entry_position"] = pos.astype(np.float64)
+    p = torch.from_numpy(pos).to(dev)
+
+    def take(ptr, typestr):
+        return torch.as_tensor(DevArray(ptr, nnz, typestr), device=dev)[p].cpu().numpy() if nnz > 0 else np.zeros(0)
+    out["rowval"] = take(rowval_p, "<i4").astype(np.float64)
+    out["free"] = ((words[p >> 6] >> (p & 63)) & 1).cpu().numpy().astype(np.float32)
+    for k, (ptr, t) in per_entry.items():
+        out[k] = take(ptr, t).astype(np.float32 if t.endswith("1") else np.float64)
+    return out
+
+
+def leg_counts(args, steps, warmup):
+    """Timed and warm-up steps of a leg: --steps / --warmup where given, else the leg's defaults."""
+    return (args.steps if args.steps is not None else steps), (args.warmup if args.warmup is not None else warmup)
 
 
 def profiled_traffic(so_path, workload, world):
@@ -134,7 +216,7 @@ def stream_bench(args):
     H = mp._lib.pack_bits(rng.random(w.N) < 0.25)
     ctx = mp.Context(0)
     ctx.upload_samples(w.X); ctx.upload_boxes(w.lohi, w.ss_lo, w.ss_hi)
-    steps, warm = max(1, min(args.steps, 5)), max(1, min(args.warmup, 1))
+    steps, warm = leg_counts(args, 5, 1)
     for _ in range(warm):
         got = ctx.rdisc_stream(r, Cc, H)
     torch.cuda.synchronize()
@@ -145,6 +227,8 @@ def stream_bench(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     ms = 1e3 * dt / steps
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, column_outputs(w.N, {"degree": got["deg"], "parent": got["parent"], "cost": got["cost"]}))
     kms = ctx.timing("stream_kernel")[0]
     pairs = ctx.stat("pairs_tested")
     mfma_tflops = pairs * 2.0 * 16 / (kms * 1e-3) / 1e12 if kms > 0 else 0.0
@@ -201,7 +285,7 @@ def di_bench(args):
     w = mp.workloads.cfg4(args.n) if args.n else mp.workloads.cfg4()
     ctx = mp.Context(0)
     ctx.upload_samples(w.X); ctx.upload_boxes(w.lohi, w.ss_lo, w.ss_hi)
-    steps, warm = max(1, min(args.steps, 10)), max(1, min(args.warmup, 2))
+    steps, warm = leg_counts(args, 10, 2)
     for _ in range(warm):
         nnz = ctx.di_graph_step_device(w.rho, w.r)
     torch.cuda.synchronize()
@@ -212,11 +296,15 @@ def di_bench(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     ms = 1e3 * dt / steps
+    if args.dump_outputs:
+        cp, rv, nz, tv, fr, ns = ctx.di_graph_device_ptrs()
+        write_outputs(args.dump_outputs, csc_outputs(torch.device("cuda", 0), w.N, nnz, cp, rv, fr,
+                                                     {"nzval": (nz, "<f8"), "tval": (tv, "<f8"), "nseg": (ns, "|u1")}))
     t_cnt, t_fill, t_swp = ctx.timing("di_count")[0], ctx.timing("di_fill")[0], ctx.timing("di_sweep")[0]
     pairs = float(w.N) * float(w.N - 1)
     prof = profiled_valu(mp._lib.so_path(), w.name)
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as orc
         orc.lib()
         sub, t_cpu, n_sub, nz_sub = 1000, 0.0, 0, 0
@@ -274,7 +362,7 @@ def mc_bench(args):
     for k, v in enumerate(src):
         inds, _ = ctx.rdisc_query(int(v), w.r)
         dst[k] = inds[rng.integers(0, len(inds))] if len(inds) else v
-    steps, warm = max(1, min(args.steps, 10)), max(1, min(args.warmup, 1))
+    steps, warm = leg_counts(args, 10, 1)
     for _ in range(warm):
         hits = ctx.mc_edges_collision(src, dst, sigma, R, seed=11)
     torch.cuda.synchronize()
@@ -285,14 +373,21 @@ def mc_bench(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     ms = 1e3 * dt / steps
-    t1 = time.perf_counter()
-    for k in range(steps):
-        p_ais, _, _ = ctx.mc_edges_collision_ais(src, dst, sigma, R, seed=11 + k)
-    torch.cuda.synchronize()
-    ms_ais = 1e3 * (time.perf_counter() - t1) / steps
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"hits": np.asarray(hits, dtype=np.float64)})
+    ais = None
+    if args.full:
+        t1 = time.perf_counter()
+        for k in range(steps):
+            p_ais, _, _ = ctx.mc_edges_collision_ais(src, dst, sigma, R, seed=11 + k)
+        torch.cuda.synchronize()
+        ms_ais = 1e3 * (time.perf_counter() - t1) / steps
+        ais = {"ms_per_step": ms_ais, "rollouts_per_s": E * R / (ms_ais * 1e-3), "mean_probability": float(np.mean(p_ais)),
+               "note": "mpfmt_mc_edges_collision_ais: 4096-rollout pilot per edge, cross-entropy mean shift, mixture of the nominal and the "
+                       "shifted density; same rollout count"}
     prof = profiled_valu(mp._lib.so_path(), "cfg5_mc_r6_m200")
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as orc
         orc.lib()
         Rc, t_cpu, n_cpu = 20000, 0.0, 0
@@ -313,9 +408,7 @@ def mc_bench(args):
            "config": {"workload": "cfg5_mc_r6_m200", "edges": E, "rollouts_per_edge": R, "sigma": sigma, "d": w.d, "M": int(len(w.lohi)),
                       "step": "mpfmt_mc_edges_collision on %d candidate edges (host index arrays in, host counts out: 6 KB over PCIe inside the step)" % E},
            "submetrics": {"edges_per_s": E * steps / dt, "mean_collision_probability": float(p.mean()), "edges_with_p_below_1e-4": int((p < 1e-4).sum()),
-                          "adaptive_is": {"ms_per_step": ms_ais, "rollouts_per_s": E * R / (ms_ais * 1e-3), "mean_probability": float(np.mean(p_ais)),
-                                          "note": "mpfmt_mc_edges_collision_ais: 4096-rollout pilot per edge, cross-entropy mean shift, mixture of the nominal and the "
-                                                  "shifted density; same rollout count"}},
+                          "adaptive_is": ais},
            "roofline": valu_roofline("k_mc_edges<6> (lane = rollout: 12 Philox4x32-10 draws, perturbed segment against the edge's culled boxes)",
                                      prof.get("k_mc_edges"), ms, prof.get("source"),
                                      "no HBM stream at all (inputs: two states and <= 200 boxes per edge, outputs: one count): integer / fp64 vector issue bound; "
@@ -351,8 +444,12 @@ def spawn_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 50; cfg3_full 5, cfg4 and cfg5 10)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 3; cfg3_full 1, cfg4 2, cfg5 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what a plain run leaves out: CPU baselines, cold-call and whole-solve submetrics, the free-edge checksum, "
+                         "cfg5's adaptive-IS timing (--no-cpu-baseline / --no-solve / --no-cold drop single parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (single GPU)")
     ap.add_argument("--workload", default="north_star", choices=["north_star", "cfg2", "cfg1", "cfg3", "cfg3_full", "cfg4", "cfg5", "ns_clustered", "ns_biased"])
     ap.add_argument("--n", type=int, default=0, help="override the sample count")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -362,6 +459,12 @@ def main():
                     help="distinct sample sets (same N, r, obstacles; resident in HBM) the steps cycle through: every step builds the "
                          "graph of NEW samples, as a planner's calls do; 1 = the same samples every step")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs needs a single-GPU run")
 
     if args.workload == "cfg3_full":
         return stream_bench(args)
@@ -369,6 +472,7 @@ def main():
         return di_bench(args)
     if args.workload == "cfg5":
         return mc_bench(args)
+    args.steps, args.warmup = leg_counts(args, 50, 3)
     one_device = bool(os.environ.get("MPFMT_BENCH_ONE_DEVICE"))
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -512,22 +616,27 @@ def main():
     else:
         nnz_total, nnz_sum_total = nnz, nnz_sum
 
-    # consistency of a sharded run with the unsharded one (tools/first_8gpu_run.sh): free edges over all shards of the LAST step
+    if args.dump_outputs:
+        cp, rv, nz, fr = ctx.graph_device_ptrs()
+        write_outputs(args.dump_outputs, csc_outputs(dev, w.N, nnz, cp, rv, fr, {"nzval": (nz, "<f8")}))
+
+    # (--full) consistency of a sharded run with the unsharded one (tools/first_8gpu_run.sh): free edges over all shards of the LAST step
     free_edges = None
-    try:
-        from motionplanning_jl_amd.distributed import DevArray
-        fr = ctx.graph_device_ptrs()[3]
-        if fr and nnz > 0:
-            wds = torch.as_tensor(DevArray(fr, (nnz + 63) // 64), device=dev).cpu().numpy().view(np.uint8)
-            free_edges = int(np.unpackbits(wds, bitorder="little")[:nnz].sum())
-        else:
-            free_edges = 0
-        if dist is not None:
-            tf = torch.tensor([free_edges], dtype=torch.int64, device=dev)
-            dist.all_reduce(tf, op=dist.ReduceOp.SUM)
-            free_edges = int(tf.item())
-    except Exception:
-        free_edges = None
+    if args.full:
+        try:
+            from motionplanning_jl_amd.distributed import DevArray
+            fr = ctx.graph_device_ptrs()[3]
+            if fr and nnz > 0:
+                wds = torch.as_tensor(DevArray(fr, (nnz + 63) // 64), device=dev).cpu().numpy().view(np.uint8)
+                free_edges = int(np.unpackbits(wds, bitorder="little")[:nnz].sum())
+            else:
+                free_edges = 0
+            if dist is not None:
+                tf = torch.tensor([free_edges], dtype=torch.int64, device=dev)
+                dist.all_reduce(tf, op=dist.ReduceOp.SUM)
+                free_edges = int(tf.item())
+        except Exception:
+            free_edges = None
     ms_step = 1e3 * dt / max(args.steps, 1)
     nnz_last = nnz
     nnz = nnz_sum / max(args.steps, 1)               # this rank's mean entries per step: what the per-kernel averages below belong to
@@ -603,7 +712,8 @@ def main():
                            ("; half build: every pair of samples is tested once by the pair kernel, which writes the hit records of both columns" if half_build else "") +
                            ("; edge tests fused: the broad phase of a pair's segment runs in the pair kernel's drain (once for both directions), "
                             "the flagged pairs' slab tests in k_exact_pairs, the mask is written by the ordering pass -- no separate sweep kernel" if edge_form == 2 else "")},
-        "consistency": {"free_edges": free_edges, "of_entries": nnz_total, "what": "set bits of the free-edge mask of the last step, summed over the shards"},
+        **({"consistency": {"free_edges": free_edges, "of_entries": nnz_total,
+                            "what": "set bits of the free-edge mask of the last step, summed over the shards"}} if args.full else {}),
         "submetrics": {
             "rdisc_queries_per_s": w.N * args.steps / dt,
             # (form 2: no kernel is "the sweep" -- every edge's broad phase runs inside the pair kernel and k_exact_pairs visits the
@@ -749,7 +859,7 @@ def main():
 
     # cold calls (outside the timed region, fresh contexts): what the FIRST call of a planner costs -- every device buffer is
     # allocated inside it, no size of an earlier build can be taken on trust -- next to the steady-state step above
-    if world == 1 and not args.no_cold and args.workload != "cfg3":
+    if args.full and world == 1 and not args.no_cold and args.workload != "cfg3":
         try:
             def wall(f):
                 torch.cuda.synchronize()
@@ -832,7 +942,7 @@ def main():
 
     # whole solve (outside the timed region): fmtstar! with the recursion on the device (mpfmt_fmtstar_wavefront) --
     # what a planner call costs end to end, next to the eager step above
-    if world == 1 and not args.no_solve and args.workload != "cfg3":
+    if args.full and world == 1 and not args.no_solve and args.workload != "cfg3":
         try:
             ctx.set_option("rebuild_index", 0)
             band = 0.25 * w.r
@@ -879,7 +989,7 @@ def main():
         except mp.MPFMTError as e:            # never lose the headline line to the extra
             out["submetrics"]["fmt_solve"] = {"error": str(e)}
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(w, mp)
         print(json.dumps(out))
         sys.stdout.flush()

@@ -98,6 +98,19 @@ def test_bench_gpus_flag_is_honoured():
     assert p.returncode == 2 and "does not match WORLD_SIZE" in p.stderr
 
 
+def test_bench_refuses_what_it_cannot_honour():
+    """--steps below 1 and --dump-outputs with several ranks are refused before anything is set up."""
+    import os
+    import subprocess
+    import sys
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    bench = os.path.join(ROOT, "bench.py")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    for args, msg in ((["--steps", "0"], "--steps"), (["--gpus", "2", "--dump-outputs", "out"], "--dump-outputs")):
+        p = subprocess.run([sys.executable, bench] + args, env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 2 and msg in p.stderr and p.stdout.strip() == "", args
+
+
 def test_host_side_under_asan_ubsan(orc, tmp_path):
     """The host part of libmpfmt.so (mpfmt_host.cpp: sequential recursion, directed recursion, import validation) built with
     -fsanitize=address,undefined and run on an oracle-made graph: no sanitizer report, and the tree equals the oracle's."""

@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 for n in 1 2 4 8; do
   echo "== $n rank(s) =="
-  timeout 900 python bench.py --gpus $n --steps 20 --warmup 5 --sample-sets 1 --no-cpu-baseline --no-solve --no-cold > "$OUT/bench_n$n.json" 2> "$OUT/bench_n$n.err" \
+  timeout 900 python bench.py --gpus $n --steps 20 --warmup 5 --sample-sets 1 --full --no-cpu-baseline --no-solve --no-cold > "$OUT/bench_n$n.json" 2> "$OUT/bench_n$n.err" \
     || { echo "bench.py --gpus $n failed:"; tail -20 "$OUT/bench_n$n.err"; }
 done
 python - "$OUT" <<'PY'
