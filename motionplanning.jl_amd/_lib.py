@@ -455,42 +455,44 @@ class Context:
 
     def fmtstar(self, r, goal_kind, goal_params, init_idx=1, checkpts=True):
         g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A = np.empty(max(self.N, 1), dtype=np.int64)
-        Cc = np.empty(max(self.N, 1), dtype=np.float64)
-        path = np.empty(max(self.N, 1), dtype=np.int64)
+        A, Cc, path = self._fmt_arrays()
         res = FmtResult()
         self._chk(self._L.mpfmt_fmtstar(self._h, float(r), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g),
                                         _ip(A), _dp(Cc), _ip(path), C.byref(res)))
-        return dict(status=int(res.status), cost=float(res.cost), z=int(res.z),
-                    collision_checks=int(res.collision_checks), nnz=int(res.nnz),
-                    ms_graph=res.ms_graph, ms_sweep=res.ms_sweep, ms_host_loop=res.ms_host_loop,
-                    A=A[:self.N], C=Cc[:self.N], path=path[:res.path_len].copy())
+        return self._fmt_out(res, A, Cc, path)
 
-    # ---- wavefront solve (recursion on the device) -------------------------------------------------
-    @staticmethod
-    def _wf_info(i):
-        return {k: getattr(i, k) for k, _ in WfInfo._fields_}
+    def _fmt_arrays(self, want_tree=True):
+        """The output arrays of a plan: parents A and costs C (None without the tree) and the path."""
+        A = np.empty(max(self.N, 1), dtype=np.int64) if want_tree else None
+        Cc = np.empty(max(self.N, 1), dtype=np.float64) if want_tree else None
+        return A, Cc, np.empty(max(self.N, 1), dtype=np.int64)
 
     def _fmt_out(self, res, A, Cc, path):
         return dict(status=int(res.status), cost=float(res.cost), z=int(res.z), collision_checks=int(res.collision_checks),
                     nnz=int(res.nnz), ms_graph=res.ms_graph, ms_sweep=res.ms_sweep, ms_host_loop=res.ms_host_loop,
                     A=None if A is None else A[:self.N], C=None if Cc is None else Cc[:self.N], path=path[:res.path_len].copy())
 
+    # ---- wavefront solve (recursion on the device) -------------------------------------------------
+    @staticmethod
+    def _wf_info(i):
+        return {k: getattr(i, k) for k, _ in WfInfo._fields_}
+
+    def _wf_out(self, res, info, A, Cc, path):
+        out = self._fmt_out(res, A, Cc, path)
+        out["info"] = self._wf_info(info)
+        return out
+
     def fmtstar_wavefront(self, r, goal_kind, goal_params, band=0.0, single=False, eager=False, lazy=False, init_idx=1, checkpts=True,
                           want_tree=True):
         """fmtstar! with the recursion on the device (include/mpfmt.h): band = cost width of a batch; single = one node per
         step (the reference's order exactly)."""
         g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A = np.empty(max(self.N, 1), dtype=np.int64) if want_tree else None
-        Cc = np.empty(max(self.N, 1), dtype=np.float64) if want_tree else None
-        path = np.empty(max(self.N, 1), dtype=np.int64)
+        A, Cc, path = self._fmt_arrays(want_tree)
         res, info = FmtResult(), WfInfo()
         flags = (WF_SINGLE if single else 0) | (WF_EAGER if eager else 0) | (WF_LAZY if lazy else 0)
         self._chk(self._L.mpfmt_fmtstar_wavefront(self._h, float(r), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g), float(band),
                                                   flags, _ip(A), _dp(Cc), _ip(path), C.byref(res), C.byref(info)))
-        out = self._fmt_out(res, A, Cc, path)
-        out["info"] = self._wf_info(info)
-        return out
+        return self._wf_out(res, info, A, Cc, path)
 
     def wf_begin(self, r, goal_kind, goal_params, band=0.0, single=False, eager=False, init_idx=1, checkpts=True, lazy=False):
         g = np.ascontiguousarray(goal_params, dtype=np.float64)
@@ -527,9 +529,7 @@ class Context:
         self._chk(self._L.mpfmt_wf_commit(self._h, len(x), _ip(x), _ip(y), _dp(c)))
 
     def wf_finish(self, want_tree=True):
-        A = np.empty(max(self.N, 1), dtype=np.int64) if want_tree else None
-        Cc = np.empty(max(self.N, 1), dtype=np.float64) if want_tree else None
-        path = np.empty(max(self.N, 1), dtype=np.int64)
+        A, Cc, path = self._fmt_arrays(want_tree)
         res = FmtResult()
         self._chk(self._L.mpfmt_wf_finish(self._h, _ip(A), _dp(Cc), _ip(path), C.byref(res)))
         return self._fmt_out(res, A, Cc, path)
@@ -594,43 +594,48 @@ class Context:
         wsum = wsum[:len(src)]
         return wsum.astype(np.float64) / (2.0 ** 40) / max(int(rollouts), 1), wsum, sh[:len(src)]
 
-    # ---- Dubins and Reeds-Shepp cars --------------------------------------------------------------
-    def _car_graph(self, car, turn_radius, speed, r):
+    # ---- steering spaces: double integrator (space "di", params (rho, r)), Dubins and Reeds-Shepp cars (turn_radius, speed, r) ----
+    def _steer_graph(self, space, params, tval=False):
+        """(colptr, rowval, nzval[, tval]), CSC 1-based."""
         colptr = np.empty(self.N + 1, dtype=np.int64)
         nnz = C.c_int64()
-        self._chk(getattr(self._L, f"mpfmt_{car}_graph_count")(self._h, float(turn_radius), float(speed), float(r), _ip(colptr), C.byref(nnz)))
+        self._chk(getattr(self._L, f"mpfmt_{space}_graph_count")(self._h, *map(float, params), _ip(colptr), C.byref(nnz)))
         self.nnz = n = nnz.value
         rowval = np.empty(max(n, 1), dtype=np.int64)
-        nzval = np.empty(max(n, 1), dtype=np.float64)
-        self._chk(getattr(self._L, f"mpfmt_{car}_graph_fill")(self._h, _ip(rowval), _dp(nzval)))
-        return colptr, rowval[:n], nzval[:n]
+        vals = [np.empty(max(n, 1), dtype=np.float64) for _ in range(2 if tval else 1)]
+        self._chk(getattr(self._L, f"mpfmt_{space}_graph_fill")(self._h, _ip(rowval), *map(_dp, vals)))
+        return (colptr, rowval[:n]) + tuple(v[:n] for v in vals)
 
-    def _car_graph_edges_free(self, car):
+    def _steer_graph_edges_free(self, space):
         n = self.nnz
         mask = np.zeros(max(nwords(n), 1), dtype=np.uint64)
         nseg = np.zeros(max(n, 1), dtype=np.uint8)
-        self._chk(getattr(self._L, f"mpfmt_{car}_graph_edges_free")(self._h, _up(mask), nseg.ctypes.data_as(c_u8_p)))
+        self._chk(getattr(self._L, f"mpfmt_{space}_graph_edges_free")(self._h, _up(mask), nseg.ctypes.data_as(c_u8_p)))
         return mask[:nwords(n)], nseg[:n]
 
-    def _car_fmtstar(self, car, turn_radius, speed, r, goal_kind, goal_params, init_idx, checkpts):
+    def _steer_fmtstar(self, space, params, goal_kind, goal_params, init_idx, checkpts):
         g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A = np.empty(max(self.N, 1), dtype=np.int64)
-        Cc = np.empty(max(self.N, 1), dtype=np.float64)
-        path = np.empty(max(self.N, 1), dtype=np.int64)
+        A, Cc, path = self._fmt_arrays()
         res = FmtResult()
-        self._chk(getattr(self._L, f"mpfmt_{car}_fmtstar")(self._h, float(turn_radius), float(speed), float(r), int(init_idx),
-                                                           int(bool(checkpts)), int(goal_kind), _dp(g), _ip(A), _dp(Cc), _ip(path),
-                                                           C.byref(res)))
-        return dict(status=int(res.status), cost=float(res.cost), z=int(res.z), collision_checks=int(res.collision_checks),
-                    nnz=int(res.nnz), ms_graph=res.ms_graph, ms_sweep=res.ms_sweep, ms_host_loop=res.ms_host_loop,
-                    A=A[:self.N], C=Cc[:self.N], path=path[:res.path_len].copy())
+        self._chk(getattr(self._L, f"mpfmt_{space}_fmtstar")(self._h, *map(float, params), int(init_idx), int(bool(checkpts)), int(goal_kind),
+                                                             _dp(g), _ip(A), _dp(Cc), _ip(path), C.byref(res)))
+        return self._fmt_out(res, A, Cc, path)
+
+    def _steer_fmtstar_wavefront(self, space, params, goal_kind, goal_params, band, single, init_idx, checkpts, want_tree=True):
+        g = np.ascontiguousarray(goal_params, dtype=np.float64)
+        A, Cc, path = self._fmt_arrays(want_tree)
+        res, info = FmtResult(), WfInfo()
+        self._chk(getattr(self._L, f"mpfmt_{space}_fmtstar_wavefront")(self._h, *map(float, params), int(init_idx), int(bool(checkpts)),
+                                                                       int(goal_kind), _dp(g), float(band), WF_SINGLE if single else 0,
+                                                                       _ip(A), _dp(Cc), _ip(path), C.byref(res), C.byref(info)))
+        return self._wf_out(res, info, A, Cc, path)
 
     def dubins_graph(self, turn_radius, speed, r):
         """Chopped backward sets of the Dubins quasi-metric, CSC 1-based: (colptr, rowval, nzval)."""
-        return self._car_graph("dubins", turn_radius, speed, r)
+        return self._steer_graph("dubins", (turn_radius, speed, r))
 
     def dubins_graph_edges_free(self):
-        return self._car_graph_edges_free("dubins")
+        return self._steer_graph_edges_free("dubins")
 
     def dubins_steer(self, X0, X1, turn_radius, speed=1.0):
         X0 = np.ascontiguousarray(X0, dtype=np.float64); X1 = np.ascontiguousarray(X1, dtype=np.float64)
@@ -640,14 +645,14 @@ class Context:
         return cost[:n], ctrl[:n]
 
     def dubins_fmtstar(self, turn_radius, speed, r, goal_kind, goal_params, init_idx=1, checkpts=True):
-        return self._car_fmtstar("dubins", turn_radius, speed, r, goal_kind, goal_params, init_idx, checkpts)
+        return self._steer_fmtstar("dubins", (turn_radius, speed, r), goal_kind, goal_params, init_idx, checkpts)
 
     def reedsshepp_graph(self, turn_radius, speed, r):
         """Chopped Reeds-Shepp neighbourhoods, CSC 1-based: column v = rows w with nzval = reedsshepp(v, w)."""
-        return self._car_graph("reedsshepp", turn_radius, speed, r)
+        return self._steer_graph("reedsshepp", (turn_radius, speed, r))
 
     def reedsshepp_graph_edges_free(self):
-        return self._car_graph_edges_free("reedsshepp")
+        return self._steer_graph_edges_free("reedsshepp")
 
     def reedsshepp_steer(self, X0, X1, turn_radius, speed=1.0):
         """(cost, controls (n,5,3), nsegs)."""
@@ -659,7 +664,7 @@ class Context:
         return cost[:n], ctrl[:n], nsegs[:n]
 
     def reedsshepp_fmtstar(self, turn_radius, speed, r, goal_kind, goal_params, init_idx=1, checkpts=True):
-        return self._car_fmtstar("reedsshepp", turn_radius, speed, r, goal_kind, goal_params, init_idx, checkpts)
+        return self._steer_fmtstar("reedsshepp", (turn_radius, speed, r), goal_kind, goal_params, init_idx, checkpts)
 
     # ---- closest obstacle points ----------------------------------------------------------------
     def closest(self, P, W=None):
@@ -724,22 +729,10 @@ class Context:
     # ---- double integrator ------------------------------------------------------------------------
     def di_graph(self, rho, r):
         """Sparse cost matrix of the double-integrator space, CSC 1-based: (colptr, rowval, nzval, tval)."""
-        colptr = np.empty(self.N + 1, dtype=np.int64)
-        nnz = C.c_int64()
-        self._chk(self._L.mpfmt_di_graph_count(self._h, float(rho), float(r), _ip(colptr), C.byref(nnz)))
-        self.nnz = n = nnz.value
-        rowval = np.empty(max(n, 1), dtype=np.int64)
-        nzval = np.empty(max(n, 1), dtype=np.float64)
-        tval = np.empty(max(n, 1), dtype=np.float64)
-        self._chk(self._L.mpfmt_di_graph_fill(self._h, _ip(rowval), _dp(nzval), _dp(tval)))
-        return colptr, rowval[:n], nzval[:n], tval[:n]
+        return self._steer_graph("di", (rho, r), tval=True)
 
     def di_graph_edges_free(self):
-        n = self.nnz
-        mask = np.zeros(max(nwords(n), 1), dtype=np.uint64)
-        nseg = np.zeros(max(n, 1), dtype=np.uint8)
-        self._chk(self._L.mpfmt_di_graph_edges_free(self._h, _up(mask), nseg.ctypes.data_as(c_u8_p)))
-        return mask[:nwords(n)], nseg[:n]
+        return self._steer_graph_edges_free("di")
 
     def di_graph_step_device(self, rho, r):
         """Double-integrator graph + 5-waypoint edge bits, outputs left in HBM (see include/mpfmt.h).  Returns nnz."""
@@ -763,44 +756,15 @@ class Context:
         return cost[:n], t[:n]
 
     def di_fmtstar(self, rho, r, goal_kind, goal_params, init_idx=1, checkpts=True):
-        g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A = np.empty(max(self.N, 1), dtype=np.int64)
-        Cc = np.empty(max(self.N, 1), dtype=np.float64)
-        path = np.empty(max(self.N, 1), dtype=np.int64)
-        res = FmtResult()
-        self._chk(self._L.mpfmt_di_fmtstar(self._h, float(rho), float(r), int(init_idx), int(bool(checkpts)), int(goal_kind),
-                                           _dp(g), _ip(A), _dp(Cc), _ip(path), C.byref(res)))
-        return dict(status=int(res.status), cost=float(res.cost), z=int(res.z), collision_checks=int(res.collision_checks),
-                    nnz=int(res.nnz), ms_graph=res.ms_graph, ms_sweep=res.ms_sweep, ms_host_loop=res.ms_host_loop,
-                    A=A[:self.N], C=Cc[:self.N], path=path[:res.path_len].copy())
+        return self._steer_fmtstar("di", (rho, r), goal_kind, goal_params, init_idx, checkpts)
 
     def car_fmtstar_wavefront(self, car, turn_radius, speed, r, goal_kind, goal_params, band=0.0, single=False, init_idx=1, checkpts=True):
         """dubins / reedsshepp planner with the recursion on the device."""
-        g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A = np.empty(max(self.N, 1), dtype=np.int64); Cc = np.empty(max(self.N, 1), dtype=np.float64)
-        path = np.empty(max(self.N, 1), dtype=np.int64)
-        res, info = FmtResult(), WfInfo()
-        self._chk(getattr(self._L, f"mpfmt_{car}_fmtstar_wavefront")(self._h, float(turn_radius), float(speed), float(r), int(init_idx),
-                                                                     int(bool(checkpts)), int(goal_kind), _dp(g), float(band),
-                                                                     WF_SINGLE if single else 0, _ip(A), _dp(Cc), _ip(path), C.byref(res),
-                                                                     C.byref(info)))
-        out = self._fmt_out(res, A, Cc, path)
-        out["info"] = self._wf_info(info)
-        return out
+        return self._steer_fmtstar_wavefront(car, (turn_radius, speed, r), goal_kind, goal_params, band, single, init_idx, checkpts)
 
     def di_fmtstar_wavefront(self, rho, r, goal_kind, goal_params, band=0.0, single=False, init_idx=1, checkpts=True, want_tree=True):
         """di_fmtstar with the recursion on the device (directed wavefront form)."""
-        g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A = np.empty(max(self.N, 1), dtype=np.int64) if want_tree else None
-        Cc = np.empty(max(self.N, 1), dtype=np.float64) if want_tree else None
-        path = np.empty(max(self.N, 1), dtype=np.int64)
-        res, info = FmtResult(), WfInfo()
-        self._chk(self._L.mpfmt_di_fmtstar_wavefront(self._h, float(rho), float(r), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g),
-                                                     float(band), WF_SINGLE if single else 0, _ip(A), _dp(Cc), _ip(path), C.byref(res),
-                                                     C.byref(info)))
-        out = self._fmt_out(res, A, Cc, path)
-        out["info"] = self._wf_info(info)
-        return out
+        return self._steer_fmtstar_wavefront("di", (rho, r), goal_kind, goal_params, band, single, init_idx, checkpts, want_tree)
 
     # ---- device-resident -------------------------------------------------------------------------
     def graph_build_device(self, r):

@@ -512,12 +512,6 @@ __device__ inline bool car_motion_free(const double* v0, const double* w, double
 }
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_car_xy(const double* __restrict__ X, int64_t N, double* __restrict__ XY)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < N) { XY[2 * i] = X[3 * i]; XY[2 * i + 1] = X[3 * i + 1]; }
-}
-
 // lane = candidate entry e of the positions graph (row i, column j): Dubins: cost(i -> j) (backward set of j); Reeds-Shepp:
 // cost(j -> i) (inball(j), ds = colwise(dist, V[j], V[inds])); keep bit = cost <= r
 template <int KIND>
@@ -637,7 +631,7 @@ static int32_t car_check(mpfmt_ctx* ctx, double rt, double sp, double r)
 
 static int32_t car_scan(mpfmt_ctx* ctx, const int64_t* in, int64_t* out, size_t n) { return mpfmt_scan_i64(ctx, in, out, n); }
 
-int32_t mpfmt_car_build(mpfmt_ctx* ctx, int kind, double rt, double sp, double r)
+int32_t mpfmt_car_build(mpfmt_ctx* ctx, mpfmt_steer kind, double rt, double sp, double r)
 {
     int32_t rc;
     if ((rc = car_check(ctx, rt, sp, r))) return rc;
@@ -647,9 +641,8 @@ int32_t mpfmt_car_build(mpfmt_ctx* ctx, int kind, double rt, double sp, double r
     if (!ctx->aux && (rc = mpfmt_ctx_create(ctx->device, &ctx->aux))) return mpfmt_fail(ctx, rc, "helper ctx: %s", mpfmt_last_error(nullptr));
     mpfmt_ctx* ax = ctx->aux;
     {
-        std::vector<double> Xh((size_t)N * 3), xy((size_t)N * 2);
-        HIPCHK(ctx, hipMemcpy(Xh.data(), ctx->Xo, sizeof(double) * (size_t)N * 3, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < N; ++i) { xy[2 * i] = Xh[3 * i]; xy[2 * i + 1] = Xh[3 * i + 1]; }
+        std::vector<double> Xh, xy;
+        if ((rc = mpfmt_states_host(ctx, 2, Xh, xy))) return rc;
         if ((rc = mpfmt_upload_samples(ax, xy.data(), N, 2))) return mpfmt_fail(ctx, rc, "helper ctx: %s", mpfmt_last_error(ax));
     }
     int64_t cnnz = 0;
@@ -665,7 +658,7 @@ int32_t mpfmt_car_build(mpfmt_ctx* ctx, int kind, double rt, double sp, double r
     HIPCHK(ctx, hipMemsetAsync(ctx->deg, 0, sizeof(int64_t) * (size_t)(N + 1), ctx->stream));
     ctx->deg_zero_valid = false;
     if (cnnz > 0) {
-        if (kind == 2)
+        if (kind == MPFMT_STEER_REEDSSHEPP)
             hipLaunchKernelGGL(k_car_cost<2>, dim3((unsigned)((cnnz + 255) / 256)), dim3(256), 0, ctx->stream, ctx->Xo, N, ax->colptr, ax->rowval,
                                cnnz, rt, sp, r, ctx->valtmp, ctx->car_keep);
         else
@@ -689,16 +682,16 @@ int32_t mpfmt_car_build(mpfmt_ctx* ctx, int kind, double rt, double sp, double r
     tm1.end("car_graph");
     ctx->nnz = nnz;
     ctx->pairs_tested = cnnz;
-    ctx->car_rt = rt; ctx->car_sp = sp; ctx->di_r = r;
-    ctx->steer_kind = (kind == 2) ? 3 : 2;
-    ctx->di_counted = ctx->di_filled = true; ctx->di_swept = false;
+    ctx->car_rt = rt; ctx->car_sp = sp; ctx->steer_r = r;
+    ctx->steer_kind = kind;
+    ctx->steer_counted = ctx->steer_filled = true; ctx->steer_swept = false;
     ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false;
     return MPFMT_OK;
 }
 
 int32_t mpfmt_car_sweep(mpfmt_ctx* ctx)
 {
-    if (!(ctx->di_filled && (ctx->steer_kind == 2 || ctx->steer_kind == 3))) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "car sweep before the car graph is built");
+    if (!(ctx->steer_filled && ctx->steer_kind != MPFMT_STEER_DI)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "car sweep before the car graph is built");
     if (!ctx->have_boxes || ctx->dw != 2)
         return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the car sweep needs a 2-D workspace checker (mpfmt_upload_boxes with dw = 2, or mpfmt_upload_shapes2d) and the 3 SE2 bounds");
     mpfmt_ws2d cc;
@@ -708,27 +701,27 @@ int32_t mpfmt_car_sweep(mpfmt_ctx* ctx)
     int32_t rc;
     const int64_t nnz = ctx->nnz, words = (nnz + 63) / 64;
     if ((rc = mpfmt_ensure(ctx, (void**)&ctx->graph_free, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->di_nseg, (size_t)std::max<int64_t>(nnz, 1)))) return rc;
+    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->steer_nseg, (size_t)std::max<int64_t>(nnz, 1)))) return rc;
     mpfmt_timed tm2(ctx);
     HIPCHK(ctx, hipMemsetAsync(ctx->graph_free, 0, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1), ctx->stream));
     if (nnz > 0) {
-        if (ctx->steer_kind == 3)
+        if (ctx->steer_kind == MPFMT_STEER_REEDSSHEPP)
             hipLaunchKernelGGL(k_car_sweep<2>, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ctx->stream, ctx->Xo, ctx->N, ctx->colptr,
-                               ctx->rowval, nnz, ctx->car_rt, ctx->car_sp, cc, ctx->ss, ctx->graph_free, ctx->di_nseg);
+                               ctx->rowval, nnz, ctx->car_rt, ctx->car_sp, cc, ctx->ss, ctx->graph_free, ctx->steer_nseg);
         else
             hipLaunchKernelGGL(k_car_sweep<1>, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ctx->stream, ctx->Xo, ctx->N, ctx->colptr,
-                               ctx->rowval, nnz, ctx->car_rt, ctx->car_sp, cc, ctx->ss, ctx->graph_free, ctx->di_nseg);
+                               ctx->rowval, nnz, ctx->car_rt, ctx->car_sp, cc, ctx->ss, ctx->graph_free, ctx->steer_nseg);
         HIPCHK(ctx, hipGetLastError());
     }
     tm2.end("car_sweep");
-    ctx->di_swept = true;
+    ctx->steer_swept = true;
     return MPFMT_OK;
 }
 
-int32_t mpfmt_car_steer_batch(mpfmt_ctx* ctx, int kind, const double* d_X0, const double* d_X1, int64_t n, double rt, double sp, double* d_cost,
+int32_t mpfmt_car_steer_batch(mpfmt_ctx* ctx, mpfmt_steer kind, const double* d_X0, const double* d_X1, int64_t n, double rt, double sp, double* d_cost,
                               double* d_ctrl, int32_t* d_nseg)
 {
-    if (kind == 2) hipLaunchKernelGGL(k_car_steer<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_X0, d_X1, n, rt, sp, d_cost, d_ctrl, d_nseg);
+    if (kind == MPFMT_STEER_REEDSSHEPP) hipLaunchKernelGGL(k_car_steer<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_X0, d_X1, n, rt, sp, d_cost, d_ctrl, d_nseg);
     else hipLaunchKernelGGL(k_car_steer<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_X0, d_X1, n, rt, sp, d_cost, d_ctrl, d_nseg);
     HIPCHK(ctx, hipGetLastError());
     return MPFMT_OK;

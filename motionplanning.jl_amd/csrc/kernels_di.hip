@@ -488,8 +488,8 @@ int32_t mpfmt_di_count(mpfmt_ctx* ctx, double rho, double r)
     ctx->nnz = nnz;
     ctx->pairs_tested = (int64_t)ctr[0];
     ctx->survivors = (int64_t)ctr[1];
-    ctx->di_rho = rho; ctx->di_r = r;
-    ctx->di_counted = true; ctx->di_filled = false; ctx->di_swept = false; ctx->steer_kind = 1;
+    ctx->di_rho = rho; ctx->steer_r = r;
+    ctx->steer_counted = true; ctx->steer_filled = false; ctx->steer_swept = false; ctx->steer_kind = MPFMT_STEER_DI;
     // the Euclidean graph state shares colptr/rowval/nzval: invalidate it
     ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false;
     return MPFMT_OK;
@@ -497,7 +497,7 @@ int32_t mpfmt_di_count(mpfmt_ctx* ctx, double rho, double r)
 
 int32_t mpfmt_di_fill(mpfmt_ctx* ctx)
 {
-    if (!ctx->di_counted) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "di fill before di count");
+    if (!ctx->steer_counted) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "di fill before di count");
     const int64_t N = ctx->N, nnz = ctx->nnz;
     const int m = ctx->d / 2;
     int32_t rc;
@@ -509,7 +509,7 @@ int32_t mpfmt_di_fill(mpfmt_ctx* ctx)
     if ((rc = mpfmt_ensure(ctx, (void**)&ctx->tval, sizeof(double) * (size_t)nnz))) return rc;
     const int64_t ntiles = (N + 63) / 64;
     di_args a;
-    a.X = ctx->Xo; a.N = N; a.rho = ctx->di_rho; a.r = ctx->di_r;
+    a.X = ctx->Xo; a.N = N; a.rho = ctx->di_rho; a.r = ctx->steer_r;
     a.i2 = 1.0 / (a.r * a.r); a.i3 = a.i2 / a.r; a.i4 = a.i2 * a.i2; a.r2 = a.r * a.r;
     a.S = ctx->di_S; a.ntiles = ntiles; a.slice_cnt = ctx->slice_cnt; a.colptr = ctx->colptr;
     a.rowtmp = ctx->rowtmp; a.valtmp = ctx->valtmp; a.tvaltmp = ctx->tvaltmp; a.counters = nullptr;
@@ -532,13 +532,13 @@ int32_t mpfmt_di_fill(mpfmt_ctx* ctx)
         HIPCHK(ctx, hipGetLastError());
         tm2.end("di_fill");
     }
-    ctx->di_filled = true;
+    ctx->steer_filled = true;
     return MPFMT_OK;
 }
 
 int32_t mpfmt_di_sweep(mpfmt_ctx* ctx)
 {
-    if (!ctx->di_filled) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "di sweep before the di graph is filled");
+    if (!ctx->steer_filled) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "di sweep before the di graph is filled");
     if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
     const int m = ctx->d / 2;
     if (ctx->cc_kind != 0 && m != 2) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the 2-D SAT world needs a 2-D workspace (states in R^4)");
@@ -553,17 +553,17 @@ int32_t mpfmt_di_sweep(mpfmt_ctx* ctx)
     const int64_t nnz = ctx->nnz, words = (nnz + 63) / 64;
     int32_t rc;
     if ((rc = mpfmt_ensure(ctx, (void**)&ctx->graph_free, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->di_nseg, (size_t)std::max<int64_t>(nnz, 1)))) return rc;
+    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->steer_nseg, (size_t)std::max<int64_t>(nnz, 1)))) return rc;
     if (nnz > 0) {
         mpfmt_timed tm3(ctx);
         const unsigned nb = (unsigned)((nnz + 255) / 256);
         DISPATCH_M(m, hipLaunchKernelGGL((k_di_sweep<DM>), dim3(nb), dim3(256), lds, ctx->stream, ctx->Xo, ctx->N, ctx->colptr,
                                          ctx->rowval, ctx->tval, nnz, ctx->di_rho, ctx->boxes, nbox, ctx->ss, ctx->graph_free,
-                                         ctx->di_nseg, cc));
+                                         ctx->steer_nseg, cc));
         HIPCHK(ctx, hipGetLastError());
         tm3.end("di_sweep");
     }
-    ctx->di_swept = true;
+    ctx->steer_swept = true;
     return MPFMT_OK;
 }
 

@@ -801,7 +801,7 @@ static int32_t wf_enqueue_local(mpfmt_ctx* ctx, mpfmt_wf* s)
     if (pos) hipLaunchKernelGGL(k_wf_compact, dim3(nparts), dim3(64), 0, st, s->pwords, (const unsigned long long*)s->cands, s->xlist, s->ctr);
     else hipLaunchKernelGGL(k_wf_compact, dim3(nparts), dim3(64), 0, st, words, (const unsigned long long*)s->cand, s->xlist, s->ctr);
     const uint64_t* gfree = s->use_mask ? ctx->graph_free : nullptr;
-    const uint8_t* nseg = s->directed ? ctx->di_nseg : nullptr;
+    const uint8_t* nseg = s->directed ? ctx->steer_nseg : nullptr;
     // (a directed steering graph's validity bits are its own sweep's: gfree is set there too -- the mask form)
     const bool geom = gfree == nullptr;
     // (persistent workgroups: exactly as many as are resident at once -- the kernel's loops stride by the grid, so a workgroup that has to
@@ -1201,7 +1201,7 @@ extern "C++" int32_t mpfmt_wf_run(mpfmt_ctx* ctx)
 extern "C++" int32_t mpfmt_wf_begin_directed(mpfmt_ctx* ctx, int64_t init_idx, int32_t checkpts, const uint64_t* F_host, int32_t goal_kind,
                                 const double* goal_params, int32_t gd, double band, int32_t flags)
 {
-    if (!ctx->di_filled || !ctx->di_swept) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "directed wavefront solve needs a built and swept steering graph");
+    if (!ctx->steer_filled || !ctx->steer_swept) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "directed wavefront solve needs a built and swept steering graph");
     if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "directed wavefront solve runs on an unsharded ctx");
     const int64_t N = ctx->N;
     const int d = ctx->d;
@@ -1214,7 +1214,7 @@ extern "C++" int32_t mpfmt_wf_begin_directed(mpfmt_ctx* ctx, int64_t init_idx, i
     if ((rc = wf_alloc(ctx, s, N, 1))) return rc;
     s->sharded = 0; s->directed = true; s->use_mask = 1; s->all_in = 0; s->pos_space = 0;
     s->band = band; s->single = (flags & MPFMT_WF_SINGLE) ? 1 : 0; s->checkpts = checkpts ? 1 : 0;
-    s->init = init_idx - 1; s->r = ctx->di_r;
+    s->init = init_idx - 1; s->r = ctx->steer_r;
     s->goal.kind = goal_kind; s->goal.gd = goal_kind == MPFMT_GOAL_POINT ? d : gd;
     const int ng = goal_kind == MPFMT_GOAL_RECT ? 2 * gd : goal_kind == MPFMT_GOAL_BALL ? gd + 1 : d;
     memset(s->goal.g, 0, sizeof s->goal.g);

@@ -233,7 +233,7 @@ int32_t mpfmt_ctx_destroy(mpfmt_ctx* ctx)
     void* bufs[] = {ctx->Xo, ctx->perm, ctx->iperm, ctx->cellkey, ctx->idx_arena, ctx->Xt, ctx->tile_lo, ctx->tile_hi, ctx->tile_sub, ctx->tile_sub32,
                     ctx->slice_cnt, ctx->deg, ctx->colptr, ctx->rowtmp, ctx->valtmp, ctx->rowval, ctx->nzval,
                     ctx->graph_free, ctx->d_pairs, ctx->boxes, ctx->scratch, ctx->degs, ctx->tptr, ctx->Xs, ctx->ops, ctx->di_ops, ctx->Xo_next, ctx->cellcnt_pad,
-                    ctx->tvaltmp, ctx->tval, ctx->di_nseg, ctx->rowpos, ctx->pool_flag, ctx->qkey, ctx->qd2, ctx->qlen, ctx->smask, ctx->st_best, ctx->st_besti, ctx->st_nfree, ctx->pend_items, ctx->pend_cnt, ctx->pair_items, ctx->pair_cnt, ctx->lists, ctx->list_len, ctx->lists_stage, ctx->sweep_ctr, ctx->rt_cnt, ctx->rt_off, ctx->rt_tmp, ctx->rt_table, ctx->rt_total, ctx->rt_ss, ctx->ssflag_dev, ctx->shapes2d, ctx->car_keep, ctx->di_pool_i, ctx->di_pool_c, ctx->di_pool_t, ctx->spec_fail, ctx->rb_dev, ctx->bb_dev};
+                    ctx->tvaltmp, ctx->tval, ctx->steer_nseg, ctx->rowpos, ctx->pool_flag, ctx->qkey, ctx->qd2, ctx->qlen, ctx->smask, ctx->st_best, ctx->st_besti, ctx->st_nfree, ctx->pend_items, ctx->pend_cnt, ctx->pair_items, ctx->pair_cnt, ctx->lists, ctx->list_len, ctx->lists_stage, ctx->sweep_ctr, ctx->rt_cnt, ctx->rt_off, ctx->rt_tmp, ctx->rt_table, ctx->rt_total, ctx->rt_ss, ctx->ssflag_dev, ctx->shapes2d, ctx->car_keep, ctx->di_pool_i, ctx->di_pool_c, ctx->di_pool_t, ctx->spec_fail, ctx->rb_dev, ctx->bb_dev};
     if (ctx->rb_host) hipHostFree(ctx->rb_host);
     if (ctx->export_arena) hipHostFree(ctx->export_arena);
     if (ctx->bb_host) hipHostFree(ctx->bb_host);
@@ -363,7 +363,7 @@ static int32_t adopt_samples(mpfmt_ctx* ctx, const double* src, bool src_on_host
     ctx->samples_epoch += 1;
     ctx->grid_r = -1.0; ctx->graph_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0;
     ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false;
-    ctx->di_counted = ctx->di_filled = ctx->di_swept = false;
+    ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
     ctx->nnz = 0;
     if (N > 0) {
         const bb_block* h = (const bb_block*)ctx->bb_host;
@@ -401,7 +401,7 @@ int32_t mpfmt_set_state_bounds(mpfmt_ctx* ctx, const double* ss_lo, const double
     ctx->ss.d = ss_lo ? d_state : 0;
     for (int i = 0; i < MPFMT_MAX_DIM; ++i) { ctx->ss.lo[i] = -INFINITY; ctx->ss.hi[i] = INFINITY; }
     if (ss_lo) for (int i = 0; i < d_state; ++i) { ctx->ss.lo[i] = ss_lo[i]; ctx->ss.hi[i] = ss_hi[i]; }
-    ctx->graph_swept = false; ctx->di_swept = false; ctx->pend_valid = false;     // (a pending list belongs to the obstacle set it was made against)
+    ctx->graph_swept = false; ctx->steer_swept = false; ctx->pend_valid = false;     // (a pending list belongs to the obstacle set it was made against)
     return MPFMT_OK;
 }
 
@@ -426,7 +426,7 @@ int32_t mpfmt_upload_boxes(mpfmt_ctx* ctx, const double* lohi, int32_t M, int32_
     for (int i = 0; i < MPFMT_MAX_DIM; ++i) { ctx->ss.lo[i] = -INFINITY; ctx->ss.hi[i] = INFINITY; }
     if (ss_lo) for (int i = 0; i < d_state; ++i) { ctx->ss.lo[i] = ss_lo[i]; ctx->ss.hi[i] = ss_hi[i]; }
     ctx->graph_swept = false; ctx->pend_valid = false;
-    ctx->di_swept = false;
+    ctx->steer_swept = false;
     return MPFMT_OK;
 }
 
@@ -439,7 +439,7 @@ int32_t mpfmt_graph_build_device(mpfmt_ctx* ctx, double r, int64_t* nnz)
     if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
-    ctx->di_counted = ctx->di_filled = ctx->di_swept = false;
+    ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
     if (ctx->rebuild_index) { ctx->grid_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0; }    // index build (cell grid + operands) is part of the build
     if ((rc = mpfmt_launch_rdisc_count(ctx, r))) return rc;
     if ((rc = mpfmt_launch_rdisc_fill(ctx, r))) return rc;
@@ -454,7 +454,7 @@ int32_t mpfmt_graph_step_device(mpfmt_ctx* ctx, double r, int64_t* nnz)
     if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
-    ctx->di_counted = ctx->di_filled = ctx->di_swept = false;
+    ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
     if (ctx->rebuild_index) { ctx->grid_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0; }
     if ((rc = mpfmt_graph_step(ctx, r))) return rc;
     // results are complete on return (the speculative path has synchronised after its last launch already; the careful
@@ -470,7 +470,7 @@ int32_t mpfmt_graph_step_launch(mpfmt_ctx* ctx, double r)
     if (!(r >= 0.0) || !std::isfinite(r)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "radius must be finite and >= 0");
     if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    ctx->di_counted = ctx->di_filled = ctx->di_swept = false;
+    ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
     if (ctx->rebuild_index) { ctx->grid_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0; }
     return mpfmt_graph_step_launch_impl(ctx, r);
 }
@@ -494,7 +494,7 @@ int32_t mpfmt_rdisc_count(mpfmt_ctx* ctx, double r, int64_t* colptr, int64_t* nn
     if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
-    ctx->di_counted = ctx->di_filled = ctx->di_swept = false;
+    ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
     if ((rc = mpfmt_launch_rdisc_count(ctx, r))) return rc;
     const int64_t n1 = ctx->N + 1;
     void* scr;
@@ -572,7 +572,7 @@ int32_t mpfmt_graph_import(mpfmt_ctx* ctx, double r, const int64_t* colptr, cons
     ctx->graph_swept = false; ctx->pend_valid = false;
     ctx->pool_valid = false;
     ctx->rowpos_valid = false;
-    ctx->di_counted = ctx->di_filled = ctx->di_swept = false;
+    ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
     return MPFMT_OK;
 }
 
@@ -768,6 +768,17 @@ static int32_t explicit_sweep(mpfmt_ctx* ctx, const double* P, const double* Q, 
 }
 
 int32_t mpfmt_states_free(mpfmt_ctx* ctx, const double* P, int64_t n, uint64_t* mask) { return explicit_sweep(ctx, P, nullptr, n, mask); }
+
+extern "C++" int32_t mpfmt_states_host(mpfmt_ctx* ctx, int k, std::vector<double>& X, std::vector<double>& P)
+{
+    const int64_t N = ctx->N;
+    const int d = ctx->d;
+    X.resize((size_t)N * d);
+    HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * (size_t)N * d, hipMemcpyDeviceToHost));
+    P.resize((size_t)N * k);
+    for (int64_t i = 0; i < N; ++i) for (int q = 0; q < k; ++q) P[(size_t)i * k + q] = X[(size_t)i * d + q];
+    return MPFMT_OK;
+}
 
 int32_t mpfmt_motions_free(mpfmt_ctx* ctx, const double* P, const double* Q, int64_t n, uint64_t* mask)
 {
@@ -1082,7 +1093,44 @@ int32_t mpfmt_expand(mpfmt_ctx* ctx, const uint64_t* W, const uint64_t* H, const
 // mpfmt_host.cpp: plain C++ without HIP, so the same translation unit is also built with -fsanitize=address,undefined for the
 // CPU test suite (tests/asan/).
 static inline bool bit(const std::vector<uint64_t>& m, int64_t i) { return (m[i >> 6] >> (i & 63)) & 1ull; }
-static inline bool is_goal_pt(const double* v, int d, int kind, const double* g) { return mpfmt_is_goal_pt(v, d, kind, g); }
+
+using stamp = std::chrono::steady_clock::time_point;
+static stamp now() { return std::chrono::steady_clock::now(); }
+
+// the timing fields of a plan from its stamps: start, checkpts bitmap, graph built, graph swept, recursion begun, recursion done
+static void fmt_times(const mpfmt_ctx* ctx, mpfmt_fmt_result* res, const stamp (&t)[6])
+{
+    auto ms = [](stamp a, stamp b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    res->nnz = ctx->nnz;
+    res->ms_graph = ms(t[1], t[2]);
+    res->ms_sweep = ms(t[0], t[1]) + ms(t[2], t[3]);
+    res->ms_host_loop = ms(t[4], t[5]);
+}
+
+// the resident graph on the host for a recursion there: CSC (0-based rows), per-edge free bits and, for a steering graph, the
+// per-edge segment counts of its sweep
+struct host_graph {
+    std::vector<int64_t> colptr; std::vector<int32_t> rowval; std::vector<double> nzval; std::vector<uint64_t> efree; std::vector<uint8_t> nseg;
+};
+
+static int32_t graph_to_host(mpfmt_ctx* ctx, bool want_nseg, host_graph& g)
+{
+    const int64_t N = ctx->N, nnz = ctx->nnz;
+    const size_t n1 = (size_t)std::max<int64_t>(nnz, 1), words = (size_t)(nnz + 63) / 64;
+    g.colptr.resize(N + 1);
+    g.rowval.resize(n1);
+    g.nzval.resize(n1);
+    g.efree.resize(std::max<size_t>(words, 1));
+    if (want_nseg) g.nseg.resize(n1);
+    HIPCHK(ctx, hipMemcpy(g.colptr.data(), ctx->colptr, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost));
+    if (nnz > 0) {
+        HIPCHK(ctx, hipMemcpy(g.rowval.data(), ctx->rowval, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(g.nzval.data(), ctx->nzval, sizeof(double) * nnz, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(g.efree.data(), ctx->graph_free, sizeof(uint64_t) * words, hipMemcpyDeviceToHost));
+        if (want_nseg) HIPCHK(ctx, hipMemcpy(g.nseg.data(), ctx->steer_nseg, (size_t)nnz, hipMemcpyDeviceToHost));
+    }
+    return MPFMT_OK;
+}
 
 int32_t mpfmt_fmtstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t checkpts,
                       int32_t goal_kind, const double* goal_params,
@@ -1102,54 +1150,39 @@ int32_t mpfmt_fmtstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t checkp
     memset(res, 0, sizeof *res);
     res->cost = INFINITY;
     int32_t rc;
+    stamp t[6];
 
     // checkpts bitmap F (fmt.jl:31-36) -- also answers is_free_state(init) (fmt.jl:24-29)
-    const int64_t words = (N + 63) / 64;
-    std::vector<uint64_t> F(words, 0);
-    auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> F((N + 63) / 64, 0);
+    t[0] = now();
     if ((rc = mpfmt_points_free(ctx, nullptr, N, F.data()))) return rc;
     if (!bit(F, init_idx - 1)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
-    auto t1 = std::chrono::steady_clock::now();
+    t[1] = now();
 
     // r-disc graph + per-edge free mask, all edges, on the device.  A filled graph of the same samples and radius (a
     // previous plan, or mpfmt_graph_import) is reused: only the obstacle-dependent sweep is redone.
     if (!(ctx->graph_filled && ctx->graph_r == r) && (rc = mpfmt_graph_build_device(ctx, r, nullptr))) return rc;
-    auto t2 = std::chrono::steady_clock::now();
+    t[2] = now();
     ctx->pend_valid = false;
     if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    auto t3 = std::chrono::steady_clock::now();
-    const int64_t nnz = ctx->nnz;
-    std::vector<int64_t> colptr(N + 1);
-    std::vector<int32_t> rowval((size_t)std::max<int64_t>(nnz, 1));
-    std::vector<double> nzval((size_t)std::max<int64_t>(nnz, 1));
-    std::vector<uint64_t> efree((size_t)std::max<int64_t>((nnz + 63) / 64, 1));
+    t[3] = now();
+    host_graph g;
+    if ((rc = graph_to_host(ctx, false, g))) return rc;
     std::vector<double> X((size_t)N * d);
-    HIPCHK(ctx, hipMemcpy(colptr.data(), ctx->colptr, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost));
-    if (nnz > 0) {
-        HIPCHK(ctx, hipMemcpy(rowval.data(), ctx->rowval, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(nzval.data(), ctx->nzval, sizeof(double) * nnz, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(efree.data(), ctx->graph_free, sizeof(uint64_t) * ((nnz + 63) / 64), hipMemcpyDeviceToHost));
-    }
     HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * (size_t)N * d, hipMemcpyDeviceToHost));
-    auto t4 = std::chrono::steady_clock::now();
+    t[4] = now();
 
-    if ((rc = mpfmt_host_fmt_recursion(N, d, X.data(), colptr.data(), rowval.data(), nzval.data(), efree.data(),
+    if ((rc = mpfmt_host_fmt_recursion(N, d, X.data(), g.colptr.data(), g.rowval.data(), g.nzval.data(), g.efree.data(),
                                        checkpts ? F.data() : nullptr, ctx->ss.has ? ctx->ss.lo : nullptr,
                                        ctx->ss.has ? ctx->ss.hi : nullptr, init_idx, goal_kind, goal_params, A, C, path, res)))
         return mpfmt_fail(ctx, rc, "host recursion rejected its arguments");
-    auto t5 = std::chrono::steady_clock::now();
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    res->nnz = nnz;
-    res->ms_graph = ms(t1, t2);
-    res->ms_sweep = ms(t0, t1) + ms(t2, t3);
-    res->ms_host_loop = ms(t4, t5);
+    t[5] = now();
+    fmt_times(ctx, res, t);
     return MPFMT_OK;
 }
 
-// ---- double integrator (LinearQuadratic quasi-metric space) ----------------------------------------------------
+// ---- steering spaces: double integrator (LinearQuadratic quasi-metric), Dubins and Reeds-Shepp cars (kernels_di.hip, kernels_car.hip)
 
 static int32_t di_check(mpfmt_ctx* ctx, double rho, double r)
 {
@@ -1161,14 +1194,167 @@ static int32_t di_check(mpfmt_ctx* ctx, double rho, double r)
     return MPFMT_OK;
 }
 
-int32_t mpfmt_di_graph_count(mpfmt_ctx* ctx, double rho, double r, int64_t* colptr, int64_t* nnz)
+// What the shared drivers need to know of a space: the state and workspace dimensions (the obstacles and the workspace goals act
+// on the first dw coordinates of a state) and whether its graph is symmetric (Reeds-Shepp: forward and backward sets coincide,
+// nearneighbors.jl:200-203) or directed (double integrator, Dubins).
+struct steer_space { mpfmt_steer kind; int d, dw; bool symmetric; };
+
+static steer_space steer_space_of(const mpfmt_ctx* ctx, mpfmt_steer kind)
+{
+    if (kind == MPFMT_STEER_DI) return {kind, ctx->d, ctx->d / 2, false};
+    return {kind, 3, 2, kind == MPFMT_STEER_REEDSSHEPP};
+}
+
+// The planners' common prelude: the checks of the ctx against the space, then the states on the host (X) and the checkpts bitmap F,
+// is_free_state(v, CC, SS) = in_state_space(v) && point-vs-obstacles on the workspace coordinates.  The point test runs on the
+// workspace points with the state-space bounds (which have the states' dimension) switched off; they are applied here.
+// rho / r: the double integrator's build parameters, checked with the samples.
+static int32_t steer_prelude(mpfmt_ctx* ctx, const steer_space& s, double rho, double r, int64_t init_idx, int32_t goal_kind,
+                             std::vector<double>& X, std::vector<uint64_t>& F)
+{
+    int32_t rc;
+    if (s.kind == MPFMT_STEER_DI) {
+        if ((rc = di_check(ctx, rho, r))) return rc;
+        if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
+    } else {
+        if (!ctx->Xo || ctx->d != s.d) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "car planning needs SE2 samples (d = 3)");
+        if (!ctx->have_boxes || ctx->dw != s.dw)
+            return mpfmt_fail(ctx, MPFMT_ERR_STATE, "car planning needs a 2-D workspace checker (mpfmt_upload_boxes with dw = 2, or mpfmt_upload_shapes2d)");
+    }
+    const int64_t N = ctx->N;
+    if (init_idx < 1 || init_idx > N) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "init_idx out of range");
+    if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
+    if (ctx->dw != s.dw) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "workspace dim %d != state dim / 2 = %d", ctx->dw, s.dw);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<double> P;
+    if ((rc = mpfmt_states_host(ctx, s.dw, X, P))) return rc;
+    F.assign((size_t)(N + 63) / 64, 0);
+    const mpfmt_ss keep = ctx->ss;
+    ctx->ss.has = 0;
+    rc = mpfmt_states_free(ctx, P.data(), N, F.data());
+    ctx->ss = keep;
+    if (rc) return rc;
+    if (keep.has)
+        for (int64_t i = 0; i < N; ++i) {
+            const double* v = &X[(size_t)i * s.d];
+            bool ok = true;
+            for (int q = 0; q < s.d; ++q) ok = ok && (keep.lo[q] <= v[q]) && (v[q] <= keep.hi[q]);
+            if (!ok) F[i >> 6] &= ~(1ull << (i & 63));
+        }
+    if (!bit(F, init_idx - 1)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
+    return MPFMT_OK;
+}
+
+// the graph of a space: (a, b) = (rho, -) for the double integrator, (turning radius, speed) for the cars
+static int32_t steer_build(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b, double r)
+{
+    if (kind != MPFMT_STEER_DI) return mpfmt_car_build(ctx, kind, a, b, r);
+    int32_t rc;
+    if ((rc = mpfmt_di_count(ctx, a, r))) return rc;
+    return mpfmt_di_fill(ctx);
+}
+
+static int32_t steer_sweep(mpfmt_ctx* ctx, mpfmt_steer kind) { return kind == MPFMT_STEER_DI ? mpfmt_di_sweep(ctx) : mpfmt_car_sweep(ctx); }
+
+// fmtstar! in a steering space with the recursion on the host; the graph and its edge bits are built anew for every plan
+static int32_t steer_fmtstar(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b, double r, int64_t init_idx, int32_t checkpts,
+                             int32_t goal_kind, const double* goal_params, int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!A || !C || !path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
+    memset(res, 0, sizeof *res);
+    res->cost = INFINITY;
+    const steer_space s = steer_space_of(ctx, kind);
+    std::vector<double> X;
+    std::vector<uint64_t> F;
+    int32_t rc;
+    stamp t[6];
+    t[0] = now();
+    if ((rc = steer_prelude(ctx, s, a, r, init_idx, goal_kind, X, F))) return rc;
+    t[1] = now();
+    if ((rc = steer_build(ctx, kind, a, b, r))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    t[2] = now();
+    if ((rc = steer_sweep(ctx, kind))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    t[3] = now();
+    host_graph g;
+    if ((rc = graph_to_host(ctx, true, g))) return rc;
+    t[4] = now();
+    const int64_t N = ctx->N;
+    const uint64_t* Fc = checkpts ? F.data() : nullptr;
+    if (s.symmetric) {
+        // the symmetric recursion on column = inball; workspace goals act on the workspace coordinates, POINT on the whole state
+        if ((rc = mpfmt_host_fmt_recursion_impl(N, s.d, X.data(), g.colptr.data(), g.rowval.data(), g.nzval.data(), g.efree.data(), Fc,
+                                                nullptr, nullptr, init_idx, goal_kind, goal_params,
+                                                goal_kind == MPFMT_GOAL_POINT ? s.d : s.dw, g.nseg.data(), A, C, path, res)))
+            return mpfmt_fail(ctx, rc, "host recursion rejected its arguments");
+    } else {
+        auto goal_hit = [&](int64_t z) {
+            const double* v = &X[(size_t)z * s.d];
+            if (goal_kind == MPFMT_GOAL_POINT) {                      // StateGoal: exact state equality (goals.jl:128-131)
+                for (int q = 0; q < s.d; ++q) if (!(v[q] == goal_params[q])) return false;
+                return true;
+            }
+            return mpfmt_is_goal_pt(v, s.dw, goal_kind, goal_params);  // workspace goals act on C*v = the first dw coordinates
+        };
+        mpfmt_csr_host csr;
+        mpfmt_csr_view csr_view;
+        const mpfmt_csr_view* pre_ptr = nullptr;
+        if (mpfmt_csc_transpose_device(ctx, &csr) == MPFMT_OK) { csr_view = {csr.rowptr.data(), csr.colidx.data(), csr.centry.data()}; pre_ptr = &csr_view; }
+        mpfmt_directed_fmt_recursion(N, g.colptr.data(), g.rowval.data(), g.nzval.data(), g.efree.data(), g.nseg.data(), Fc,
+                                     init_idx, goal_hit, A, C, path, res, pre_ptr);
+    }
+    t[5] = now();
+    fmt_times(ctx, res, t);
+    return MPFMT_OK;
+}
+
+// fmtstar! in a steering space with the recursion on the device (kernels_wavefront.hip, directed form; the Reeds-Shepp graph is
+// structurally symmetric, so its rows are its columns and the same form applies): graph, waypoint sweep and the transpose (forward
+// sets) on the device, then cost-band batches; `single` reproduces the host recursion's pop order exactly.  A resident double-
+// integrator graph of the same (rho, r) is reused, and its sweep too while the obstacles stay; the car graphs are built anew.
+static int32_t steer_fmtstar_wavefront(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b, double r, int64_t init_idx, int32_t checkpts,
+                                       int32_t goal_kind, const double* goal_params, double band, int32_t flags, int64_t* A, double* C,
+                                       int64_t* path, mpfmt_fmt_result* res, mpfmt_wf_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
+    const steer_space s = steer_space_of(ctx, kind);
+    std::vector<double> X;
+    std::vector<uint64_t> F;
+    int32_t rc;
+    stamp t[6];
+    t[0] = now();
+    if ((rc = steer_prelude(ctx, s, a, r, init_idx, goal_kind, X, F))) return rc;
+    t[1] = now();
+    const bool resident = kind == MPFMT_STEER_DI && ctx->steer_filled && ctx->steer_kind == kind && ctx->di_rho == a && ctx->steer_r == r;
+    if (!resident && (rc = steer_build(ctx, kind, a, b, r))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    t[2] = now();
+    if (!ctx->steer_swept && (rc = steer_sweep(ctx, kind))) return rc;       // (a graph just built is not swept yet)
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    t[3] = t[4] = now();
+    if ((rc = mpfmt_wf_begin_directed(ctx, init_idx, checkpts, F.data(), goal_kind, goal_params, s.dw, band, flags))) return rc;
+    if ((rc = mpfmt_wf_run(ctx))) return rc;
+    if ((rc = mpfmt_wf_finish(ctx, A, C, path, res))) return rc;
+    t[5] = now();
+    fmt_times(ctx, res, t);
+    mpfmt_wf_info_now(ctx, info);
+    return MPFMT_OK;
+}
+
+// the graph accessors: (a, b) as for steer_build; tval (the double integrator's optimal times) may be NULL
+static int32_t steer_graph_count(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b, double r, int64_t* colptr, int64_t* nnz)
 {
     if (!ctx) return MPFMT_ERR_ARG;
     if (!colptr || !nnz) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "colptr / nnz is NULL");
     int32_t rc;
-    if ((rc = di_check(ctx, rho, r))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if ((rc = mpfmt_di_count(ctx, rho, r))) return rc;
+    if (kind == MPFMT_STEER_DI) {
+        if ((rc = di_check(ctx, a, r))) return rc;
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        if ((rc = mpfmt_di_count(ctx, a, r))) return rc;
+    } else if ((rc = mpfmt_car_build(ctx, kind, a, b, r))) return rc;
     const int64_t n1 = ctx->N + 1;
     void* scr;
     if ((rc = mpfmt_scratch(ctx, sizeof(int64_t) * n1, &scr))) return rc;
@@ -1179,14 +1365,16 @@ int32_t mpfmt_di_graph_count(mpfmt_ctx* ctx, double rho, double r, int64_t* colp
     return MPFMT_OK;
 }
 
-int32_t mpfmt_di_graph_fill(mpfmt_ctx* ctx, int64_t* rowval, double* nzval, double* tval)
+// (a car graph is filled when it is counted; a double-integrator one on the first call that needs its entries)
+static int32_t steer_graph_fill(mpfmt_ctx* ctx, mpfmt_steer kind, int64_t* rowval, double* nzval, double* tval)
 {
     if (!ctx) return MPFMT_ERR_ARG;
-    if (!ctx->di_counted || ctx->steer_kind != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "di_graph_fill before di_graph_count");
+    if (!ctx->steer_counted || ctx->steer_kind != kind)
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, kind == MPFMT_STEER_DI ? "di_graph_fill before di_graph_count" : "car graph_fill before graph_count");
     if (ctx->nnz > 0 && (!rowval || !nzval)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "rowval / nzval is NULL");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
-    if (!ctx->di_filled && (rc = mpfmt_di_fill(ctx))) return rc;
+    if (!ctx->steer_filled && (rc = mpfmt_di_fill(ctx))) return rc;
     const int64_t nnz = ctx->nnz;
     if (nnz > 0) {
         void* scr;
@@ -1200,23 +1388,32 @@ int32_t mpfmt_di_graph_fill(mpfmt_ctx* ctx, int64_t* rowval, double* nzval, doub
     return MPFMT_OK;
 }
 
-int32_t mpfmt_di_graph_edges_free(mpfmt_ctx* ctx, uint64_t* mask, uint8_t* nseg)
+static int32_t steer_graph_edges_free(mpfmt_ctx* ctx, mpfmt_steer kind, uint64_t* mask, uint8_t* nseg)
 {
     if (!ctx) return MPFMT_ERR_ARG;
-    if (!ctx->di_counted || ctx->steer_kind != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "di_graph_edges_free before di_graph_count");
+    if (!ctx->steer_counted || ctx->steer_kind != kind)
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, kind == MPFMT_STEER_DI ? "di_graph_edges_free before di_graph_count" : "car graph_edges_free before graph_count");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
-    if (!ctx->di_filled && (rc = mpfmt_di_fill(ctx))) return rc;
-    if ((rc = mpfmt_di_sweep(ctx))) return rc;
+    if (!ctx->steer_filled && (rc = mpfmt_di_fill(ctx))) return rc;
+    if ((rc = steer_sweep(ctx, kind))) return rc;
     const int64_t nnz = ctx->nnz, words = (nnz + 63) / 64;
     if (nnz > 0) {
         if (!mask) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "mask is NULL");
         HIPCHK(ctx, hipMemcpyAsync(mask, ctx->graph_free, sizeof(uint64_t) * words, hipMemcpyDeviceToHost, ctx->stream));
-        if (nseg) HIPCHK(ctx, hipMemcpyAsync(nseg, ctx->di_nseg, (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
+        if (nseg) HIPCHK(ctx, hipMemcpyAsync(nseg, ctx->steer_nseg, (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     return MPFMT_OK;
 }
+
+// ---- double integrator ----------------------------------------------------------------------------------------------
+
+int32_t mpfmt_di_graph_count(mpfmt_ctx* ctx, double rho, double r, int64_t* colptr, int64_t* nnz)
+{ return steer_graph_count(ctx, MPFMT_STEER_DI, rho, 0.0, r, colptr, nnz); }
+int32_t mpfmt_di_graph_fill(mpfmt_ctx* ctx, int64_t* rowval, double* nzval, double* tval)
+{ return steer_graph_fill(ctx, MPFMT_STEER_DI, rowval, nzval, tval); }
+int32_t mpfmt_di_graph_edges_free(mpfmt_ctx* ctx, uint64_t* mask, uint8_t* nseg) { return steer_graph_edges_free(ctx, MPFMT_STEER_DI, mask, nseg); }
 
 // the double-integrator graph and its edge bits with every output left in HBM (bench.py --workload cfg4: no PCIe in the timed region)
 int32_t mpfmt_di_graph_step_device(mpfmt_ctx* ctx, double rho, double r, int64_t* nnz)
@@ -1236,13 +1433,13 @@ int32_t mpfmt_di_graph_step_device(mpfmt_ctx* ctx, double rho, double r, int64_t
 int32_t mpfmt_di_graph_device_ptrs(mpfmt_ctx* ctx, void** colptr, void** rowval, void** nzval, void** tval, void** free_mask, void** nseg)
 {
     if (!ctx) return MPFMT_ERR_ARG;
-    if (!ctx->di_filled || ctx->steer_kind != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no double-integrator graph resident");
+    if (!ctx->steer_filled || ctx->steer_kind != MPFMT_STEER_DI) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no double-integrator graph resident");
     if (colptr) *colptr = ctx->colptr;
     if (rowval) *rowval = ctx->rowval;
     if (nzval) *nzval = ctx->nzval;
     if (tval) *tval = ctx->tval;
-    if (free_mask) *free_mask = ctx->di_swept ? (void*)ctx->graph_free : nullptr;
-    if (nseg) *nseg = ctx->di_swept ? (void*)ctx->di_nseg : nullptr;
+    if (free_mask) *free_mask = ctx->steer_swept ? (void*)ctx->graph_free : nullptr;
+    if (nseg) *nseg = ctx->steer_swept ? (void*)ctx->steer_nseg : nullptr;
     return MPFMT_OK;
 }
 
@@ -1276,204 +1473,18 @@ int32_t mpfmt_di_steer(mpfmt_ctx* ctx, const double* X0, const double* X1, int64
 int32_t mpfmt_di_fmtstar(mpfmt_ctx* ctx, double rho, double r, int64_t init_idx, int32_t checkpts,
                          int32_t goal_kind, const double* goal_params,
                          int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!A || !C || !path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
-    int32_t rc;
-    if ((rc = di_check(ctx, rho, r))) return rc;
-    if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
-    const int64_t N = ctx->N;
-    const int n = ctx->d, m = n / 2;
-    if (init_idx < 1 || init_idx > N) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "init_idx out of range");
-    if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    memset(res, 0, sizeof *res);
-    res->cost = INFINITY;
-    auto t0 = std::chrono::steady_clock::now();
-    // checkpts bitmap: is_free_state(v, CC, SS) = in_state_space(v) && point-vs-boxes on the workspace coordinates.
-    // The point kernel works on dw-dimensional points, so gather the workspace coordinates of every state.
-    std::vector<double> X((size_t)N * n);
-    HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * (size_t)N * n, hipMemcpyDeviceToHost));
-    std::vector<double> P((size_t)N * m);
-    for (int64_t i = 0; i < N; ++i) for (int q = 0; q < m; ++q) P[(size_t)i * m + q] = X[(size_t)i * n + q];
-    const int64_t words = (N + 63) / 64;
-    std::vector<uint64_t> F(words, 0);
-    {
-        const mpfmt_ss keep = ctx->ss;            // the workspace sweep must not apply the 2m-dim bounds
-        ctx->ss.has = 0;
-        rc = mpfmt_states_free(ctx, P.data(), N, F.data());
-        ctx->ss = keep;
-        if (rc) return rc;
-        if (keep.has)
-            for (int64_t i = 0; i < N; ++i) {
-                bool ok = true;
-                for (int q = 0; q < n; ++q) ok = ok && (keep.lo[q] <= X[(size_t)i * n + q]) && (X[(size_t)i * n + q] <= keep.hi[q]);
-                if (!ok) F[i >> 6] &= ~(1ull << (i & 63));
-            }
-    }
-    if (!bit(F, init_idx - 1)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
-    auto t1 = std::chrono::steady_clock::now();
-    if ((rc = mpfmt_di_count(ctx, rho, r))) return rc;
-    if ((rc = mpfmt_di_fill(ctx))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    auto t2 = std::chrono::steady_clock::now();
-    if ((rc = mpfmt_di_sweep(ctx))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    auto t3 = std::chrono::steady_clock::now();
-    const int64_t nnz = ctx->nnz;
-    std::vector<int64_t> colptr(N + 1);
-    std::vector<int32_t> rowval((size_t)std::max<int64_t>(nnz, 1));
-    std::vector<double> nzval((size_t)std::max<int64_t>(nnz, 1));
-    std::vector<uint64_t> efree((size_t)std::max<int64_t>((nnz + 63) / 64, 1));
-    std::vector<uint8_t> nseg((size_t)std::max<int64_t>(nnz, 1));
-    HIPCHK(ctx, hipMemcpy(colptr.data(), ctx->colptr, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost));
-    if (nnz > 0) {
-        HIPCHK(ctx, hipMemcpy(rowval.data(), ctx->rowval, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(nzval.data(), ctx->nzval, sizeof(double) * nnz, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(efree.data(), ctx->graph_free, sizeof(uint64_t) * ((nnz + 63) / 64), hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(nseg.data(), ctx->di_nseg, (size_t)nnz, hipMemcpyDeviceToHost));
-    }
-    auto t4 = std::chrono::steady_clock::now();
-    auto goal_hit = [&](int64_t z) {
-        const double* v = &X[(size_t)z * n];
-        if (goal_kind == MPFMT_GOAL_POINT) {                      // StateGoal: exact state equality (goals.jl:128-131)
-            for (int q = 0; q < n; ++q) if (!(v[q] == goal_params[q])) return false;
-            return true;
-        }
-        return is_goal_pt(v, m, goal_kind, goal_params);           // workspace goals act on C*v = first m coordinates
-    };
-    mpfmt_csr_host csr;
-    mpfmt_csr_view csr_view;
-    const mpfmt_csr_view* pre_ptr = nullptr;
-    if (mpfmt_csc_transpose_device(ctx, &csr) == MPFMT_OK) { csr_view = {csr.rowptr.data(), csr.colidx.data(), csr.centry.data()}; pre_ptr = &csr_view; }
-    mpfmt_directed_fmt_recursion(N, colptr.data(), rowval.data(), nzval.data(), efree.data(), nseg.data(), checkpts ? F.data() : nullptr,
-                                 init_idx, goal_hit, A, C, path, res, pre_ptr);
-    auto t5 = std::chrono::steady_clock::now();
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    res->nnz = nnz;
-    res->ms_graph = ms(t1, t2); res->ms_sweep = ms(t0, t1) + ms(t2, t3); res->ms_host_loop = ms(t4, t5);
-    return MPFMT_OK;
-}
+{ return steer_fmtstar(ctx, MPFMT_STEER_DI, rho, 0.0, r, init_idx, checkpts, goal_kind, goal_params, A, C, path, res); }
 
-// fmtstar! in the double-integrator space with the recursion on the device (kernels_wavefront.hip, directed form): graph,
-// 5-waypoint sweep and the transpose (forward sets) on the device, then cost-band batches; `single` reproduces
-// mpfmt_di_fmtstar / the reference's pop order exactly.
+// `single` reproduces mpfmt_di_fmtstar / the reference's pop order exactly
 int32_t mpfmt_di_fmtstar_wavefront(mpfmt_ctx* ctx, double rho, double r, int64_t init_idx, int32_t checkpts, int32_t goal_kind,
                                    const double* goal_params, double band, int32_t flags, int64_t* A, double* C, int64_t* path,
                                    mpfmt_fmt_result* res, mpfmt_wf_info* info)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
-    int32_t rc;
-    if ((rc = di_check(ctx, rho, r))) return rc;
-    if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
-    const int64_t N = ctx->N;
-    const int n = ctx->d, m = n / 2;
-    if (init_idx < 1 || init_idx > N) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "init_idx out of range");
-    if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    auto t0 = std::chrono::steady_clock::now();
-    // checkpts bitmap: in_state_space on the state, point test on the workspace coordinates (as in mpfmt_di_fmtstar)
-    std::vector<double> X((size_t)N * n);
-    HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * (size_t)N * n, hipMemcpyDeviceToHost));
-    std::vector<double> P((size_t)N * m);
-    for (int64_t i = 0; i < N; ++i) for (int q = 0; q < m; ++q) P[(size_t)i * m + q] = X[(size_t)i * n + q];
-    const int64_t words = (N + 63) / 64;
-    std::vector<uint64_t> F(words, 0);
-    {
-        const mpfmt_ss keep = ctx->ss;
-        ctx->ss.has = 0;
-        rc = mpfmt_states_free(ctx, P.data(), N, F.data());
-        ctx->ss = keep;
-        if (rc) return rc;
-        if (keep.has)
-            for (int64_t i = 0; i < N; ++i) {
-                bool ok = true;
-                for (int q = 0; q < n; ++q) ok = ok && (keep.lo[q] <= X[(size_t)i * n + q]) && (X[(size_t)i * n + q] <= keep.hi[q]);
-                if (!ok) F[i >> 6] &= ~(1ull << (i & 63));
-            }
-    }
-    if (!bit(F, init_idx - 1)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
-    auto t1 = std::chrono::steady_clock::now();
-    if (!(ctx->di_filled && ctx->steer_kind == 1 && ctx->di_rho == rho && ctx->di_r == r)) {
-        if ((rc = mpfmt_di_count(ctx, rho, r))) return rc;
-        if ((rc = mpfmt_di_fill(ctx))) return rc;
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    auto t2 = std::chrono::steady_clock::now();
-    if (!ctx->di_swept && (rc = mpfmt_di_sweep(ctx))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    auto t3 = std::chrono::steady_clock::now();
-    if ((rc = mpfmt_wf_begin_directed(ctx, init_idx, checkpts, F.data(), goal_kind, goal_params, m, band, flags))) return rc;
-    if ((rc = mpfmt_wf_run(ctx))) return rc;
-    if ((rc = mpfmt_wf_finish(ctx, A, C, path, res))) return rc;
-    auto t4 = std::chrono::steady_clock::now();
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    res->ms_graph = ms(t1, t2); res->ms_sweep = ms(t0, t1) + ms(t2, t3); res->ms_host_loop = ms(t3, t4);
-    mpfmt_wf_info_now(ctx, info);
-    return MPFMT_OK;
-}
+{ return steer_fmtstar_wavefront(ctx, MPFMT_STEER_DI, rho, 0.0, r, init_idx, checkpts, goal_kind, goal_params, band, flags, A, C, path, res, info); }
 
-// ---- Dubins and Reeds-Shepp cars (kernels_car.hip) ------------------------------------------------------------------
-
-static int32_t car_graph_count(mpfmt_ctx* ctx, int kind, double turn_radius, double speed, double r, int64_t* colptr, int64_t* nnz)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!colptr || !nnz) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "colptr / nnz is NULL");
-    int32_t rc;
-    if ((rc = mpfmt_car_build(ctx, kind, turn_radius, speed, r))) return rc;
-    const int64_t n1 = ctx->N + 1;
-    void* scr;
-    if ((rc = mpfmt_scratch(ctx, sizeof(int64_t) * n1, &scr))) return rc;
-    hipLaunchKernelGGL(k_add1_i64, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, ctx->stream, ctx->colptr, n1, (int64_t*)scr);
-    HIPCHK(ctx, hipMemcpyAsync(colptr, scr, sizeof(int64_t) * n1, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *nnz = ctx->nnz;
-    return MPFMT_OK;
-}
-
-static int32_t car_graph_fill(mpfmt_ctx* ctx, int kind, int64_t* rowval, double* nzval)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!(ctx->di_filled && ctx->steer_kind == kind + 1)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "car graph_fill before graph_count");
-    const int64_t nnz = ctx->nnz;
-    if (nnz > 0 && (!rowval || !nzval)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "rowval / nzval is NULL");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (nnz > 0) {
-        int32_t rc;
-        void* scr;
-        if ((rc = mpfmt_scratch(ctx, sizeof(int64_t) * nnz, &scr))) return rc;
-        hipLaunchKernelGGL(k_i32_to_i64_add1, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ctx->stream, ctx->rowval, nnz, (int64_t*)scr);
-        HIPCHK(ctx, hipMemcpyAsync(rowval, scr, sizeof(int64_t) * nnz, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(nzval, ctx->nzval, sizeof(double) * nnz, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return MPFMT_OK;
-}
-
-static int32_t car_graph_edges_free(mpfmt_ctx* ctx, int kind, uint64_t* mask, uint8_t* nseg)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!(ctx->di_filled && ctx->steer_kind == kind + 1)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "car graph_edges_free before graph_count");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int32_t rc;
-    if ((rc = mpfmt_car_sweep(ctx))) return rc;
-    const int64_t nnz = ctx->nnz, words = (nnz + 63) / 64;
-    if (nnz > 0) {
-        if (!mask) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "mask is NULL");
-        HIPCHK(ctx, hipMemcpyAsync(mask, ctx->graph_free, sizeof(uint64_t) * words, hipMemcpyDeviceToHost, ctx->stream));
-        if (nseg) HIPCHK(ctx, hipMemcpyAsync(nseg, ctx->di_nseg, (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return MPFMT_OK;
-}
+// ---- Dubins and Reeds-Shepp cars ------------------------------------------------------------------------------------
 
 // controls out: [n][nctl][3]; nctl = 3 (Dubins) or 5 (Reeds-Shepp); nsegs (may be NULL) = segments used per pair
-static int32_t car_steer_pairs(mpfmt_ctx* ctx, int kind, const double* X0, const double* X1, int64_t n, double turn_radius, double speed,
+static int32_t car_steer_pairs(mpfmt_ctx* ctx, mpfmt_steer kind, const double* X0, const double* X1, int64_t n, double turn_radius, double speed,
                                double* cost, double* controls, int32_t* nsegs)
 {
     if (!ctx) return MPFMT_ERR_ARG;
@@ -1499,183 +1510,42 @@ static int32_t car_steer_pairs(mpfmt_ctx* ctx, int kind, const double* X0, const
     if (nsegs) HIPCHK(ctx, hipMemcpyAsync(nsegs, dn, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (controls) {
-        const int nctl = (kind == 2) ? 5 : 3;
+        const int nctl = kind == MPFMT_STEER_REEDSSHEPP ? 5 : 3;
         for (int64_t i = 0; i < n; ++i) memcpy(controls + (size_t)i * nctl * 3, u5.data() + (size_t)i * 15, sizeof(double) * nctl * 3);
     }
-    return MPFMT_OK;
-}
-
-static int32_t car_fmtstar(mpfmt_ctx* ctx, int kind, double turn_radius, double speed, double r, int64_t init_idx, int32_t checkpts,
-                           int32_t goal_kind, const double* goal_params, int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!A || !C || !path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
-    if (!ctx->Xo || ctx->d != 3) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "car planning needs SE2 samples (d = 3)");
-    if (!ctx->have_boxes || ctx->dw != 2) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "car planning needs a 2-D workspace checker (mpfmt_upload_boxes with dw = 2, or mpfmt_upload_shapes2d)");
-    const int64_t N = ctx->N;
-    if (init_idx < 1 || init_idx > N) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "init_idx out of range");
-    if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    memset(res, 0, sizeof *res);
-    res->cost = INFINITY;
-    int32_t rc;
-    auto t0 = std::chrono::steady_clock::now();
-    // checkpts bitmap: in_state_space on the SE2 state, point test on (x, y)
-    std::vector<double> X((size_t)N * 3), P((size_t)N * 2);
-    HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * (size_t)N * 3, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < N; ++i) { P[2 * i] = X[3 * i]; P[2 * i + 1] = X[3 * i + 1]; }
-    const int64_t words = (N + 63) / 64;
-    std::vector<uint64_t> F(words, 0);
-    {
-        const mpfmt_ss keep = ctx->ss;
-        ctx->ss.has = 0;
-        rc = mpfmt_states_free(ctx, P.data(), N, F.data());
-        ctx->ss = keep;
-        if (rc) return rc;
-        if (keep.has)
-            for (int64_t i = 0; i < N; ++i) {
-                bool ok = true;
-                for (int q = 0; q < 3; ++q) ok = ok && (keep.lo[q] <= X[(size_t)i * 3 + q]) && (X[(size_t)i * 3 + q] <= keep.hi[q]);
-                if (!ok) F[i >> 6] &= ~(1ull << (i & 63));
-            }
-    }
-    if (!bit(F, init_idx - 1)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
-    auto t1 = std::chrono::steady_clock::now();
-    if ((rc = mpfmt_car_build(ctx, kind, turn_radius, speed, r))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    auto t2 = std::chrono::steady_clock::now();
-    if ((rc = mpfmt_car_sweep(ctx))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    auto t3 = std::chrono::steady_clock::now();
-    const int64_t nnz = ctx->nnz;
-    std::vector<int64_t> colptr(N + 1);
-    std::vector<int32_t> rowval((size_t)std::max<int64_t>(nnz, 1));
-    std::vector<double> nzval((size_t)std::max<int64_t>(nnz, 1));
-    std::vector<uint64_t> efree((size_t)std::max<int64_t>((nnz + 63) / 64, 1));
-    std::vector<uint8_t> nseg((size_t)std::max<int64_t>(nnz, 1));
-    HIPCHK(ctx, hipMemcpy(colptr.data(), ctx->colptr, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost));
-    if (nnz > 0) {
-        HIPCHK(ctx, hipMemcpy(rowval.data(), ctx->rowval, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(nzval.data(), ctx->nzval, sizeof(double) * nnz, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(efree.data(), ctx->graph_free, sizeof(uint64_t) * ((nnz + 63) / 64), hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(nseg.data(), ctx->di_nseg, (size_t)nnz, hipMemcpyDeviceToHost));
-    }
-    auto t4 = std::chrono::steady_clock::now();
-    if (kind == 2) {
-        // Reeds-Shepp: a (chopped) metric -- forward and backward sets coincide (nearneighbors.jl:200-203): the symmetric
-        // recursion on column = inball; the goal acts on (x, y), POINT = exact state
-        std::vector<double> gp3;
-        const double* gp = goal_params;
-        if ((rc = mpfmt_host_fmt_recursion_impl(N, 3, X.data(), colptr.data(), rowval.data(), nzval.data(), efree.data(),
-                                          checkpts ? F.data() : nullptr, nullptr, nullptr, init_idx, goal_kind, gp, goal_kind == MPFMT_GOAL_POINT ? 3 : 2,
-                                          nseg.data(), A, C, path, res)))
-            return mpfmt_fail(ctx, rc, "host recursion rejected its arguments");
-    } else {
-        auto goal_hit = [&](int64_t z) {
-            const double* v = &X[(size_t)z * 3];
-            if (goal_kind == MPFMT_GOAL_POINT) return v[0] == goal_params[0] && v[1] == goal_params[1] && v[2] == goal_params[2];
-            return is_goal_pt(v, 2, goal_kind, goal_params);                       // workspace goals act on (x, y)
-        };
-        mpfmt_csr_host csr;
-        mpfmt_csr_view csr_view;
-        const mpfmt_csr_view* pre_ptr = nullptr;
-        if (mpfmt_csc_transpose_device(ctx, &csr) == MPFMT_OK) { csr_view = {csr.rowptr.data(), csr.colidx.data(), csr.centry.data()}; pre_ptr = &csr_view; }
-        mpfmt_directed_fmt_recursion(N, colptr.data(), rowval.data(), nzval.data(), efree.data(), nseg.data(), checkpts ? F.data() : nullptr,
-                                     init_idx, goal_hit, A, C, path, res, pre_ptr);
-    }
-    auto t5 = std::chrono::steady_clock::now();
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    res->nnz = nnz;
-    res->ms_graph = ms(t1, t2); res->ms_sweep = ms(t0, t1) + ms(t2, t3); res->ms_host_loop = ms(t4, t5);
-    return MPFMT_OK;
-}
-
-// the car planners with the recursion on the device (directed wavefront form; the Reeds-Shepp graph is structurally symmetric,
-// so its rows are its columns and the same form applies): graph + waypoint sweep as in car_fmtstar, then cost-band batches
-static int32_t car_fmtstar_wavefront(mpfmt_ctx* ctx, int kind, double turn_radius, double speed, double r, int64_t init_idx, int32_t checkpts,
-                                     int32_t goal_kind, const double* goal_params, double band, int32_t flags, int64_t* A, double* C,
-                                     int64_t* path, mpfmt_fmt_result* res, mpfmt_wf_info* info)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
-    if (!ctx->Xo || ctx->d != 3) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "car planning needs SE2 samples (d = 3)");
-    if (!ctx->have_boxes || ctx->dw != 2) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "car planning needs a 2-D workspace checker (mpfmt_upload_boxes with dw = 2, or mpfmt_upload_shapes2d)");
-    const int64_t N = ctx->N;
-    if (init_idx < 1 || init_idx > N) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "init_idx out of range");
-    if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int32_t rc;
-    auto t0 = std::chrono::steady_clock::now();
-    std::vector<double> X((size_t)N * 3), P((size_t)N * 2);
-    HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * (size_t)N * 3, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < N; ++i) { P[2 * i] = X[3 * i]; P[2 * i + 1] = X[3 * i + 1]; }
-    const int64_t words = (N + 63) / 64;
-    std::vector<uint64_t> F(words, 0);
-    {
-        const mpfmt_ss keep = ctx->ss;
-        ctx->ss.has = 0;
-        rc = mpfmt_states_free(ctx, P.data(), N, F.data());
-        ctx->ss = keep;
-        if (rc) return rc;
-        if (keep.has)
-            for (int64_t i = 0; i < N; ++i) {
-                bool ok = true;
-                for (int q = 0; q < 3; ++q) ok = ok && (keep.lo[q] <= X[(size_t)i * 3 + q]) && (X[(size_t)i * 3 + q] <= keep.hi[q]);
-                if (!ok) F[i >> 6] &= ~(1ull << (i & 63));
-            }
-    }
-    if (!bit(F, init_idx - 1)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
-    auto t1 = std::chrono::steady_clock::now();
-    if ((rc = mpfmt_car_build(ctx, kind, turn_radius, speed, r))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    auto t2 = std::chrono::steady_clock::now();
-    if ((rc = mpfmt_car_sweep(ctx))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    auto t3 = std::chrono::steady_clock::now();
-    if ((rc = mpfmt_wf_begin_directed(ctx, init_idx, checkpts, F.data(), goal_kind, goal_params, 2, band, flags))) return rc;
-    if ((rc = mpfmt_wf_run(ctx))) return rc;
-    if ((rc = mpfmt_wf_finish(ctx, A, C, path, res))) return rc;
-    auto t4 = std::chrono::steady_clock::now();
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    res->ms_graph = ms(t1, t2); res->ms_sweep = ms(t0, t1) + ms(t2, t3); res->ms_host_loop = ms(t3, t4);
-    mpfmt_wf_info_now(ctx, info);
     return MPFMT_OK;
 }
 
 int32_t mpfmt_dubins_fmtstar_wavefront(mpfmt_ctx* ctx, double turn_radius, double speed, double r, int64_t init_idx, int32_t checkpts,
                                        int32_t goal_kind, const double* goal_params, double band, int32_t flags, int64_t* A, double* C,
                                        int64_t* path, mpfmt_fmt_result* res, mpfmt_wf_info* info)
-{ return car_fmtstar_wavefront(ctx, 1, turn_radius, speed, r, init_idx, checkpts, goal_kind, goal_params, band, flags, A, C, path, res, info); }
+{ return steer_fmtstar_wavefront(ctx, MPFMT_STEER_DUBINS, turn_radius, speed, r, init_idx, checkpts, goal_kind, goal_params, band, flags, A, C, path, res, info); }
 int32_t mpfmt_reedsshepp_fmtstar_wavefront(mpfmt_ctx* ctx, double turn_radius, double speed, double r, int64_t init_idx, int32_t checkpts,
                                            int32_t goal_kind, const double* goal_params, double band, int32_t flags, int64_t* A, double* C,
                                            int64_t* path, mpfmt_fmt_result* res, mpfmt_wf_info* info)
-{ return car_fmtstar_wavefront(ctx, 2, turn_radius, speed, r, init_idx, checkpts, goal_kind, goal_params, band, flags, A, C, path, res, info); }
+{ return steer_fmtstar_wavefront(ctx, MPFMT_STEER_REEDSSHEPP, turn_radius, speed, r, init_idx, checkpts, goal_kind, goal_params, band, flags, A, C, path, res, info); }
 
 int32_t mpfmt_dubins_graph_count(mpfmt_ctx* ctx, double turn_radius, double speed, double r, int64_t* colptr, int64_t* nnz)
-{ return car_graph_count(ctx, 1, turn_radius, speed, r, colptr, nnz); }
-int32_t mpfmt_dubins_graph_fill(mpfmt_ctx* ctx, int64_t* rowval, double* nzval) { return car_graph_fill(ctx, 1, rowval, nzval); }
-int32_t mpfmt_dubins_graph_edges_free(mpfmt_ctx* ctx, uint64_t* mask, uint8_t* nseg) { return car_graph_edges_free(ctx, 1, mask, nseg); }
+{ return steer_graph_count(ctx, MPFMT_STEER_DUBINS, turn_radius, speed, r, colptr, nnz); }
+int32_t mpfmt_dubins_graph_fill(mpfmt_ctx* ctx, int64_t* rowval, double* nzval) { return steer_graph_fill(ctx, MPFMT_STEER_DUBINS, rowval, nzval, nullptr); }
+int32_t mpfmt_dubins_graph_edges_free(mpfmt_ctx* ctx, uint64_t* mask, uint8_t* nseg) { return steer_graph_edges_free(ctx, MPFMT_STEER_DUBINS, mask, nseg); }
 int32_t mpfmt_dubins_steer(mpfmt_ctx* ctx, const double* X0, const double* X1, int64_t n, double turn_radius, double speed,
                            double* cost, double* controls)
-{ return car_steer_pairs(ctx, 1, X0, X1, n, turn_radius, speed, cost, controls, nullptr); }
+{ return car_steer_pairs(ctx, MPFMT_STEER_DUBINS, X0, X1, n, turn_radius, speed, cost, controls, nullptr); }
 int32_t mpfmt_dubins_fmtstar(mpfmt_ctx* ctx, double turn_radius, double speed, double r, int64_t init_idx, int32_t checkpts,
                              int32_t goal_kind, const double* goal_params, int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
-{ return car_fmtstar(ctx, 1, turn_radius, speed, r, init_idx, checkpts, goal_kind, goal_params, A, C, path, res); }
+{ return steer_fmtstar(ctx, MPFMT_STEER_DUBINS, turn_radius, speed, r, init_idx, checkpts, goal_kind, goal_params, A, C, path, res); }
 
 int32_t mpfmt_reedsshepp_graph_count(mpfmt_ctx* ctx, double turn_radius, double speed, double r, int64_t* colptr, int64_t* nnz)
-{ return car_graph_count(ctx, 2, turn_radius, speed, r, colptr, nnz); }
-int32_t mpfmt_reedsshepp_graph_fill(mpfmt_ctx* ctx, int64_t* rowval, double* nzval) { return car_graph_fill(ctx, 2, rowval, nzval); }
-int32_t mpfmt_reedsshepp_graph_edges_free(mpfmt_ctx* ctx, uint64_t* mask, uint8_t* nseg) { return car_graph_edges_free(ctx, 2, mask, nseg); }
+{ return steer_graph_count(ctx, MPFMT_STEER_REEDSSHEPP, turn_radius, speed, r, colptr, nnz); }
+int32_t mpfmt_reedsshepp_graph_fill(mpfmt_ctx* ctx, int64_t* rowval, double* nzval) { return steer_graph_fill(ctx, MPFMT_STEER_REEDSSHEPP, rowval, nzval, nullptr); }
+int32_t mpfmt_reedsshepp_graph_edges_free(mpfmt_ctx* ctx, uint64_t* mask, uint8_t* nseg) { return steer_graph_edges_free(ctx, MPFMT_STEER_REEDSSHEPP, mask, nseg); }
 int32_t mpfmt_reedsshepp_steer(mpfmt_ctx* ctx, const double* X0, const double* X1, int64_t n, double turn_radius, double speed,
                                double* cost, double* controls, int32_t* nsegs)
-{ return car_steer_pairs(ctx, 2, X0, X1, n, turn_radius, speed, cost, controls, nsegs); }
+{ return car_steer_pairs(ctx, MPFMT_STEER_REEDSSHEPP, X0, X1, n, turn_radius, speed, cost, controls, nsegs); }
 int32_t mpfmt_reedsshepp_fmtstar(mpfmt_ctx* ctx, double turn_radius, double speed, double r, int64_t init_idx, int32_t checkpts,
                                  int32_t goal_kind, const double* goal_params, int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
-{ return car_fmtstar(ctx, 2, turn_radius, speed, r, init_idx, checkpts, goal_kind, goal_params, A, C, path, res); }
+{ return steer_fmtstar(ctx, MPFMT_STEER_REEDSSHEPP, turn_radius, speed, r, init_idx, checkpts, goal_kind, goal_params, A, C, path, res); }
 
 // ---- measurement ---------------------------------------------------------------------------------------
 
@@ -1738,7 +1608,7 @@ int32_t mpfmt_set_option(mpfmt_ctx* ctx, const char* name, int64_t value)
         ctx->sweep_rounds = value != 0;
         return MPFMT_OK;
     }
-    if (strcmp(name, "di_path") == 0) { ctx->di_path = (int32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 2); ctx->di_counted = ctx->di_filled = ctx->di_swept = false; return MPFMT_OK; }
+    if (strcmp(name, "di_path") == 0) { ctx->di_path = (int32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 2); ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false; return MPFMT_OK; }
     if (strcmp(name, "wf_force_sharded") == 0) { ctx->wf_force_sharded = value != 0; return MPFMT_OK; }
     return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown option %s", name);
 }

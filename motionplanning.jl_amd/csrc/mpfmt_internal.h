@@ -78,6 +78,9 @@ struct mpfmt_shape2d {
 };
 struct mpfmt_aabb2d { double xr[2], yr[2]; };
 
+// the steering graph resident in a ctx (kernels_di.hip, kernels_car.hip)
+enum mpfmt_steer : int32_t { MPFMT_STEER_DI = 1, MPFMT_STEER_DUBINS = 2, MPFMT_STEER_REEDSSHEPP = 3 };
+
 struct mpfmt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -259,22 +262,23 @@ struct mpfmt_ctx {
     unsigned long long* d_pairs = nullptr;   // device counter: candidate pairs tested
     int64_t pairs_tested = 0;
 
-    // ---- double-integrator (LinearQuadratic) graph: shares colptr / rowval / nzval / graph_free -------------
+    // ---- steering graphs (double integrator, Dubins, Reeds-Shepp): share colptr / rowval / nzval / graph_free ---------------
+    mpfmt_steer steer_kind = MPFMT_STEER_DI;     // which steering graph the steer_* state describes
+    double steer_r = 0.0;                // cost radius of the built graph
+    bool steer_counted = false, steer_filled = false, steer_swept = false;
+    uint8_t* steer_nseg = nullptr;       // [nnz] workspace segment tests the reference would have made per edge
     int32_t di_S = 1;
-    double di_rho = 1.0, di_r = 0.0;
-    bool di_counted = false, di_filled = false, di_swept = false;
+    double di_rho = 1.0;
     int32_t* di_pool_i = nullptr; double* di_pool_c = nullptr; double* di_pool_t = nullptr;   // DI single-pass slot lists
     int64_t di_pool_cap = 0; bool di_pool_valid = false;
     void* di_ops = nullptr;              // matrix-core prefilter of the double-integrator build (kernels_di_mfma.hip): target- and source-role operands
     bool di_mf = false; float di_negT = 0.f;     // the counted DI graph went through it; its threshold
     int32_t di_path = 0;                 // option: 0 auto, 1 vector-ALU candidate test, 2 matrix-core prefilter
-    int32_t steer_kind = 1;              // which steering graph the di_* state describes: 1 double integrator, 2 Dubins car, 3 Reeds-Shepp car
     double car_rt = 1.0, car_sp = 1.0;   // Dubins turning radius / speed of the built graph
     uint64_t* car_keep = nullptr;        // keep bits over the candidate (positions) graph
     mpfmt_ctx* aux = nullptr;            // helper ctx: Euclidean r-disc graph of the positions (Dubins build)
     double* tvaltmp = nullptr;           // [nnz] optimal times, unsorted staging
     double* tval = nullptr;              // [nnz] optimal times t* per entry
-    uint8_t* di_nseg = nullptr;          // [nnz] workspace segment tests the reference would have made per edge
 
     // ---- obstacles -----------------------------------------------------------------------------
     double* boxes = nullptr;             // [M][2][dw]
@@ -319,6 +323,8 @@ int32_t mpfmt_fail(mpfmt_ctx* ctx, int32_t code, const char* fmt, ...);
     } while (0)
 
 int32_t mpfmt_scratch(mpfmt_ctx* ctx, size_t bytes, void** out);
+// the samples on the host (X: [N][d]) and their first k coordinates (P: [N][k], the workspace points of steering-space states)
+int32_t mpfmt_states_host(mpfmt_ctx* ctx, int k, std::vector<double>& X, std::vector<double>& P);
 // grow-only device buffer: (re)allocates *p when it is smaller than bytes
 int32_t mpfmt_ensure(mpfmt_ctx* ctx, void** p, size_t bytes);
 void mpfmt_time_begin(mpfmt_ctx* ctx);
@@ -391,9 +397,9 @@ int32_t mpfmt_launch_graph_sweep(mpfmt_ctx* ctx, const int32_t* spec_fail = null
 #include <vector>
 int32_t mpfmt_csc_transpose_device(mpfmt_ctx* ctx, mpfmt_csr_host* out);      // kernels_di.hip; needs nnz < 2^32
 int32_t mpfmt_csc_transpose_resident(mpfmt_ctx* ctx, int64_t* d_rowptr, int32_t* d_colidx);   // the same, result left on the device
-int32_t mpfmt_car_build(mpfmt_ctx* ctx, int kind, double rt, double sp, double r);      // kind 1 Dubins, 2 Reeds-Shepp
+int32_t mpfmt_car_build(mpfmt_ctx* ctx, mpfmt_steer kind, double rt, double sp, double r);      // kind Dubins or Reeds-Shepp
 int32_t mpfmt_car_sweep(mpfmt_ctx* ctx);
-int32_t mpfmt_car_steer_batch(mpfmt_ctx* ctx, int kind, const double* d_X0, const double* d_X1, int64_t n, double rt, double sp, double* d_cost,
+int32_t mpfmt_car_steer_batch(mpfmt_ctx* ctx, mpfmt_steer kind, const double* d_X0, const double* d_X1, int64_t n, double rt, double sp, double* d_cost,
                               double* d_ctrl, int32_t* d_nseg);
 struct di_args;
 int32_t mpfmt_di_mf_prepare(mpfmt_ctx* ctx, double rho, double r, float* negT, bool* usable, double* sp_out, double* sv_out, double* pc);      // kernels_di_mfma.hip

@@ -983,6 +983,85 @@ def test_reedsshepp_graph_sweep_and_plan(ctx, orc, N, rt, r):
         ctx.reedsshepp_graph_edges_free()
 
 
+# ---- argument and state errors of the steering-space planners ------------------------------------------------------------
+
+# (name, state dimension, planner(ctx, goal_kind, goal_params, init_idx)): the host and the device recursion of each space
+STEER_PLANNERS = [
+    ("di", 4, lambda c, k, g, i: c.di_fmtstar(1.0, 1.0, k, g, init_idx=i)),
+    ("di_wavefront", 4, lambda c, k, g, i: c.di_fmtstar_wavefront(1.0, 1.0, k, g, single=True, init_idx=i)),
+    ("dubins", 3, lambda c, k, g, i: c.dubins_fmtstar(0.15, 1.0, 0.3, k, g, init_idx=i)),
+    ("dubins_wavefront", 3, lambda c, k, g, i: c.car_fmtstar_wavefront("dubins", 0.15, 1.0, 0.3, k, g, single=True, init_idx=i)),
+    ("reedsshepp", 3, lambda c, k, g, i: c.reedsshepp_fmtstar(0.15, 1.0, 0.3, k, g, init_idx=i)),
+    ("reedsshepp_wavefront", 3, lambda c, k, g, i: c.car_fmtstar_wavefront("reedsshepp", 0.15, 1.0, 0.3, k, g, single=True, init_idx=i)),
+]
+
+
+def _steer_world(d, N=60, seed=5):
+    """States of dimension d (4: double integrator, 3: SE2), one 2-D box around state 2, and the state-space bounds."""
+    rng = np.random.default_rng(seed)
+    X = rng.random((N, d))
+    X[1, :2] = [0.5, 0.5]
+    lohi = np.array([[[0.45, 0.45], [0.55, 0.55]]])
+    return X, lohi, np.zeros(d), np.ones(d)
+
+
+@pytest.mark.parametrize("name,d,plan", STEER_PLANNERS, ids=[p[0] for p in STEER_PLANNERS])
+def test_steer_planner_errors(name, d, plan):
+    """Every refusal of the six steering-space planners, with its code and message, in the order the checks are made."""
+    car = not name.startswith("di")
+    g = np.array([0.9, 0.9, 0.1, 0.0])
+    X, lohi, lo, hi = _steer_world(d)
+    N = len(X)
+
+    def refuses(c, code, msg, k=mp._lib.GOAL_BALL, i=1):
+        with pytest.raises(mp.MPFMTError) as e:
+            plan(c, k, g, i)
+        assert e.value.code == code and msg in str(e.value), str(e.value)
+
+    with mp.Context(0) as c:
+        refuses(c, mp._lib.ERR_STATE, "car planning needs SE2 samples" if car else "no samples uploaded")
+        c.upload_samples(X)
+        refuses(c, mp._lib.ERR_STATE, "car planning needs a 2-D workspace checker" if car else "no obstacle set uploaded")
+        c.upload_boxes(lohi, lo, hi, dw=2)
+        refuses(c, mp._lib.ERR_ARG, "init_idx out of range", i=0)
+        refuses(c, mp._lib.ERR_ARG, "init_idx out of range", i=N + 1)
+        refuses(c, mp._lib.ERR_ARG, "init_idx out of range", k=3, i=0)            # the index is checked before the goal kind
+        refuses(c, mp._lib.ERR_ARG, "unknown goal kind 3", k=3)
+        refuses(c, mp._lib.ERR_INFEASIBLE, "initial state is infeasible", i=2)
+        if car:
+            c.upload_boxes(np.zeros((1, 2, 3)), lo, hi, dw=3)                      # a 3-D workspace checker
+            refuses(c, mp._lib.ERR_STATE, "car planning needs a 2-D workspace checker")
+            c.upload_samples(np.concatenate([X, X[:, :1]], axis=1))                # states in R^4
+            c.upload_boxes(lohi, lo, hi, dw=2)
+            refuses(c, mp._lib.ERR_STATE, "car planning needs SE2 samples")
+        else:
+            c.upload_samples(X[:, :3])                                              # an odd state dimension
+            refuses(c, mp._lib.ERR_ARG, "double-integrator states need an even dimension")
+
+
+def test_di_planners_refuse_a_workspace_of_the_wrong_dimension():
+    """Double-integrator states in R^4 with boxes of dw = 4 (not d / 2) are refused with ERR_ARG before any work, by the host and the
+    device recursion alike; the context then plans as a fresh one does."""
+    X, lohi, ss_lo, ss_hi = di_world(400, 12)
+    goal = [0.9, 0.9, 0.1]
+    box4 = np.concatenate([lohi, np.array([[[-1.0, -1.0]], [[1.0, 1.0]]]).transpose(1, 0, 2).repeat(len(lohi), axis=0)], axis=2)
+    with mp.Context(0) as c, mp.Context(0) as fresh:
+        c.upload_samples(X)
+        c.upload_boxes(box4, ss_lo, ss_hi)
+        for plan in (c.di_fmtstar, c.di_fmtstar_wavefront):
+            with pytest.raises(mp.MPFMTError) as e:
+                plan(1.0, 1.0, mp._lib.GOAL_BALL, goal)
+            assert e.value.code == mp._lib.ERR_ARG and "workspace dim 4 != state dim / 2 = 2" in str(e.value), str(e.value)
+        c.upload_boxes(lohi, ss_lo, ss_hi)
+        fresh.upload_samples(X)
+        fresh.upload_boxes(lohi, ss_lo, ss_hi)
+        for a, b in ((c.di_fmtstar(1.0, 1.0, mp._lib.GOAL_BALL, goal), fresh.di_fmtstar(1.0, 1.0, mp._lib.GOAL_BALL, goal)),
+                     (c.di_fmtstar_wavefront(1.0, 1.0, mp._lib.GOAL_BALL, goal, single=True),
+                      fresh.di_fmtstar_wavefront(1.0, 1.0, mp._lib.GOAL_BALL, goal, single=True))):
+            assert a["status"] == b["status"] == 1 and a["cost"] == b["cost"] and a["collision_checks"] == b["collision_checks"]
+            assert np.array_equal(a["A"], b["A"]) and np.array_equal(a["C"], b["C"]) and np.array_equal(a["path"], b["path"])
+
+
 # ---- Monte-Carlo collision probability of edges (BASELINE configs[4]) -------------------------------------------------
 
 @pytest.mark.parametrize("d,M,sigma,R", [(2, 20, 0.02, 3000), (6, 200, 0.03, 1500), (3, 300, 0.05, 1000), (6, 0, 0.1, 500)])
