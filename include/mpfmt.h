@@ -174,6 +174,30 @@ MPFMT_API int32_t mpfmt_fmtstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int3
                       int32_t goal_kind, const double* goal_params,
                       int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
 
+/* ---- k-nearest connections: fmtstar!(...; connections = :K, k) (src/planners/fmt.jl:6,17-19).  The reference exports the
+ *      names mutualknnF! / knnB! (src/nearneighbors.jl:9-11) and defines neither; the semantics here are this library's:
+ *      d2(v, i) in the canonical arithmetic of the r-disc graph; k_eff = min(k, N - 1); knn(v) = the k_eff samples i != v
+ *      smallest under the total order (d2(v, i), i) -- selection on d2, equal d2 to the lower index.  The graph is a CSC over
+ *      ALL samples: column v = knn(v), rows ascending, nzval = sqrt(d2), colptr[v] = 1 + (v - 1) k_eff (1-based like every
+ *      other graph).  knnB(x) = column x.  mutualknnF(z) = { x in knn(z) : z in knn(x) }: per entry e (row y in column x) the
+ *      mutual bit says x in knn(y), and the forward set of z is the set of columns that hold z with the bit set.
+ * knn_count : builds the graph on the device (exact for every sample distribution; candidate rounds at growing radii, the
+ *             last one a scan of all samples) and leaves it resident like an r-disc graph; colptr has N + 1 entries.
+ * knn_fill  : rowval[nnz], nzval[nnz], mutual[ceil(nnz/64)] (mutual may be NULL).
+ * knn_graph_edges_free : bit e = is_free_motion(V[row], V[col]) over the resident k-nearest graph (the sweep of
+ *             mpfmt_graph_edges_free).
+ * knn_fmtstar : fmt.jl:43-101 with nearF = mutualknnF, nearB = knnB (fmt.jl:17-19): outputs as mpfmt_fmtstar; res->nnz =
+ *             N k_eff.  AABB / 2-D SAT checkers on Euclidean samples, unsharded ctx; k < 1 is MPFMT_ERR_ARG.
+ * A later mpfmt_fmtstar(r) / mpfmt_graph_step_device(r) on the ctx builds its r-disc graph anew.  The graph occupies the ctx's one
+ * graph slot: while it is resident, the accessors that read that slot without a radius (mpfmt_rdisc_fill, mpfmt_graph_edges_free,
+ * mpfmt_graph_sweep_device, mpfmt_graph_device_ptrs, mpfmt_graph_export, mpfmt_expand) hand out the k-nearest graph (0-based /
+ * 1-based as they document); the knn accessors refuse an r-disc graph (MPFMT_ERR_STATE). */
+MPFMT_API int32_t mpfmt_knn_count(mpfmt_ctx* ctx, int64_t k, int64_t* colptr, int64_t* nnz);
+MPFMT_API int32_t mpfmt_knn_fill(mpfmt_ctx* ctx, int64_t* rowval, double* nzval, uint64_t* mutual);
+MPFMT_API int32_t mpfmt_knn_graph_edges_free(mpfmt_ctx* ctx, uint64_t* mask);
+MPFMT_API int32_t mpfmt_knn_fmtstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                          int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
+
 /* The sequential part of fmtstar! on its own (src/planners/fmt.jl:43-101): host code, no ctx and no device.  Input is
  * the finished r-disc graph in the device-native format -- colptr[N+1] 0-based offsets, rowval[nnz] 0-based int32 rows
  * (ascending per column), nzval[nnz] distances, efree = one bit per entry (row -> column motion free), F = checkpts
@@ -565,7 +589,10 @@ MPFMT_API int32_t mpfmt_set_option(mpfmt_ctx* ctx, const char* name, int64_t val
  * ordering pass, 8 more entries than allocated, 16 the pending-pair list was cut), "qcap" (records a quarter log holds), "ord_per_cu"
  * (ordering-pass workgroups per CU), "filter_valu" (1: the last single-pass build filtered with the exact fp64 test on the vector ALUs),
  * "wf_pos_space_used" (1: the last device solve gathered by cell-sorted position), "list_cap" / "list_max" / "list_q<permille>" / "list_argmax" / "list_sum" (chunk-list lengths of
- * the last list build; synchronising reads). */
+ * the last list build; synchronising reads); of the last k-nearest build: "knn_pairs_tested" (sample pairs distance-tested, counted once
+ * per column and round -- the passes of the selection evaluate them again), "knn_rounds" (candidate rounds run, the first included),
+ * "knn_short_columns" (columns the first round left to a later one), "knn_scan_columns" (columns answered by the scan of all samples).
+ * Timers of that build (mpfmt_timing_get): "knn_candidates" (cell-sorted index + tile boxes), "knn_select" (the rounds), "knn_mutual". */
 MPFMT_API int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value);
 /* work counters of the last graph build: candidate pairs distance-tested, tiles, slices. */
 MPFMT_API int32_t mpfmt_graph_stats(mpfmt_ctx* ctx, int64_t* pairs_tested, int64_t* tiles, int64_t* slices, int64_t* cells);

@@ -67,6 +67,10 @@ SYMBOLS = [
     ("mpfmt_euclid_propagate", C.c_int32, [C.c_void_p, c_i64_p, C.c_int64, c_d_p, c_d_p, c_d_p, c_d_p]),
     ("mpfmt_expand", C.c_int32, [C.c_void_p, c_u64_p, c_u64_p, c_u64_p, c_d_p, c_i64_p, C.c_int64,
                                  c_i64_p, c_i64_p, c_d_p, c_u8_p, C.c_int64, c_i64_p]),
+    ("mpfmt_knn_count", C.c_int32, [C.c_void_p, C.c_int64, c_i64_p, c_i64_p]),
+    ("mpfmt_knn_fill", C.c_int32, [C.c_void_p, c_i64_p, c_d_p, c_u64_p]),
+    ("mpfmt_knn_graph_edges_free", C.c_int32, [C.c_void_p, c_u64_p]),
+    ("mpfmt_knn_fmtstar", C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_d_p, c_i64_p, c_d_p, c_i64_p, C.POINTER(FmtResult)]),
     ("mpfmt_fmtstar", C.c_int32, [C.c_void_p, C.c_double, C.c_int64, C.c_int32, C.c_int32, c_d_p,
                                   c_i64_p, c_d_p, c_i64_p, C.POINTER(FmtResult)]),
     ("mpfmt_host_fmt_recursion", C.c_int32, [C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p,
@@ -459,6 +463,34 @@ class Context:
         res = FmtResult()
         self._chk(self._L.mpfmt_fmtstar(self._h, float(r), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g),
                                         _ip(A), _dp(Cc), _ip(path), C.byref(res)))
+        return self._fmt_out(res, A, Cc, path)
+
+    # ---- k-nearest connections (connections = :K, fmt.jl:6,17-19) -------------------------------
+    def knn_graph(self, k):
+        """(colptr, rowval, nzval, mutual_bits) of the exact k-nearest graph, 1-based CSC: column v = the min(k, N - 1) nearest samples
+        of v under (d2, index), rows ascending; mutual bit of entry (y in column x) = x is among the nearest of y."""
+        colptr = np.empty(self.N + 1, dtype=np.int64)
+        nnz = C.c_int64()
+        self._chk(self._L.mpfmt_knn_count(self._h, int(k), _ip(colptr), C.byref(nnz)))
+        self.nnz = nnz = nnz.value
+        rowval = np.empty(max(nnz, 1), dtype=np.int64)
+        nzval = np.empty(max(nnz, 1), dtype=np.float64)
+        mutual = np.zeros(max(nwords(nnz), 1), dtype=np.uint64)
+        self._chk(self._L.mpfmt_knn_fill(self._h, _ip(rowval), _dp(nzval), _up(mutual)))
+        return colptr, rowval[:nnz], nzval[:nnz], mutual[:nwords(nnz)]
+
+    def knn_graph_edges_free(self):
+        mask = np.zeros(max(nwords(self.nnz), 1), dtype=np.uint64)
+        self._chk(self._L.mpfmt_knn_graph_edges_free(self._h, _up(mask)))
+        return mask[:nwords(self.nnz)]
+
+    def knn_fmtstar(self, k, goal_kind, goal_params, init_idx=1, checkpts=True):
+        """fmtstar! with connections = :K: forward sets = mutual k-nearest, backward sets = k-nearest; same dict as fmtstar."""
+        g = np.ascontiguousarray(goal_params, dtype=np.float64)
+        A, Cc, path = self._fmt_arrays()
+        res = FmtResult()
+        self._chk(self._L.mpfmt_knn_fmtstar(self._h, int(k), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g),
+                                            _ip(A), _dp(Cc), _ip(path), C.byref(res)))
         return self._fmt_out(res, A, Cc, path)
 
     def _fmt_arrays(self, want_tree=True):

@@ -685,7 +685,7 @@ int32_t mpfmt_car_build(mpfmt_ctx* ctx, mpfmt_steer kind, double rt, double sp, 
     ctx->car_rt = rt; ctx->car_sp = sp; ctx->steer_r = r;
     ctx->steer_kind = kind;
     ctx->steer_counted = ctx->steer_filled = true; ctx->steer_swept = false;
-    ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false;
+    ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
     return MPFMT_OK;
 }
 

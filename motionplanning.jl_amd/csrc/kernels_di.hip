@@ -491,7 +491,7 @@ int32_t mpfmt_di_count(mpfmt_ctx* ctx, double rho, double r)
     ctx->di_rho = rho; ctx->steer_r = r;
     ctx->steer_counted = true; ctx->steer_filled = false; ctx->steer_swept = false; ctx->steer_kind = MPFMT_STEER_DI;
     // the Euclidean graph state shares colptr/rowval/nzval: invalidate it
-    ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false;
+    ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
     return MPFMT_OK;
 }
 

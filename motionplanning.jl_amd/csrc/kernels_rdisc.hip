@@ -661,7 +661,7 @@ int32_t mpfmt_build_grid(mpfmt_ctx* ctx, double r, bool whole)
     ctx->index_rank = ctx->rank; ctx->index_world = ctx->world;
     ctx->ops_r = mf ? r : -1.0;
     ctx->lists_r = -1.0;
-    ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false;
+    ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
     return MPFMT_OK;
 }
 
@@ -979,6 +979,7 @@ int32_t mpfmt_rdisc_count_launch(mpfmt_ctx* ctx, double r, bool spec)
     int32_t rc;
     if ((rc = mpfmt_side_join(ctx))) return rc;               // (whatever an abandoned build left on the side stream)
     ctx->masks_early = false;
+    if (ctx->knn_k) { ctx->knn_k = 0; ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; }      // (a k-nearest graph is no r-disc graph of any radius)
     if ((rc = mpfmt_build_grid(ctx, r))) return rc;
     const int64_t N = ctx->N;
     // (the shard -- tile_begin, tile_end -- is cut by the index build: mpfmt_build_grid)

@@ -233,7 +233,7 @@ int32_t mpfmt_ctx_destroy(mpfmt_ctx* ctx)
     void* bufs[] = {ctx->Xo, ctx->perm, ctx->iperm, ctx->cellkey, ctx->idx_arena, ctx->Xt, ctx->tile_lo, ctx->tile_hi, ctx->tile_sub, ctx->tile_sub32,
                     ctx->slice_cnt, ctx->deg, ctx->colptr, ctx->rowtmp, ctx->valtmp, ctx->rowval, ctx->nzval,
                     ctx->graph_free, ctx->d_pairs, ctx->boxes, ctx->scratch, ctx->degs, ctx->tptr, ctx->Xs, ctx->ops, ctx->di_ops, ctx->Xo_next, ctx->cellcnt_pad,
-                    ctx->tvaltmp, ctx->tval, ctx->steer_nseg, ctx->rowpos, ctx->pool_flag, ctx->qkey, ctx->qd2, ctx->qlen, ctx->smask, ctx->st_best, ctx->st_besti, ctx->st_nfree, ctx->pend_items, ctx->pend_cnt, ctx->pair_items, ctx->pair_cnt, ctx->lists, ctx->list_len, ctx->lists_stage, ctx->sweep_ctr, ctx->rt_cnt, ctx->rt_off, ctx->rt_tmp, ctx->rt_table, ctx->rt_total, ctx->rt_ss, ctx->ssflag_dev, ctx->shapes2d, ctx->car_keep, ctx->di_pool_i, ctx->di_pool_c, ctx->di_pool_t, ctx->spec_fail, ctx->rb_dev, ctx->bb_dev};
+                    ctx->knn_mutual, ctx->knn_st, ctx->knn_bitmap, ctx->knn_lists, ctx->tvaltmp, ctx->tval, ctx->steer_nseg, ctx->rowpos, ctx->pool_flag, ctx->qkey, ctx->qd2, ctx->qlen, ctx->smask, ctx->st_best, ctx->st_besti, ctx->st_nfree, ctx->pend_items, ctx->pend_cnt, ctx->pair_items, ctx->pair_cnt, ctx->lists, ctx->list_len, ctx->lists_stage, ctx->sweep_ctr, ctx->rt_cnt, ctx->rt_off, ctx->rt_tmp, ctx->rt_table, ctx->rt_total, ctx->rt_ss, ctx->ssflag_dev, ctx->shapes2d, ctx->car_keep, ctx->di_pool_i, ctx->di_pool_c, ctx->di_pool_t, ctx->spec_fail, ctx->rb_dev, ctx->bb_dev};
     if (ctx->rb_host) hipHostFree(ctx->rb_host);
     if (ctx->export_arena) hipHostFree(ctx->export_arena);
     if (ctx->bb_host) hipHostFree(ctx->bb_host);
@@ -269,7 +269,7 @@ int32_t mpfmt_set_shard(mpfmt_ctx* ctx, int32_t rank, int32_t world)
     ctx->rank = rank; ctx->world = world;
     ctx->deg_zero_valid = false;
     ctx->grid_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0;      // (the cell order and the built part of the index belong to the shard)
-    ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false;
+    ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
     return MPFMT_OK;
 }
 
@@ -362,7 +362,7 @@ static int32_t adopt_samples(mpfmt_ctx* ctx, const double* src, bool src_on_host
     }
     ctx->samples_epoch += 1;
     ctx->grid_r = -1.0; ctx->graph_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0;
-    ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false;
+    ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
     ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
     ctx->nnz = 0;
     if (N > 0) {
@@ -568,7 +568,7 @@ int32_t mpfmt_graph_import(mpfmt_ctx* ctx, double r, const int64_t* colptr, cons
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->nnz = nnz;
     ctx->graph_r = r;
-    ctx->graph_counted = ctx->graph_filled = true;
+    ctx->graph_counted = ctx->graph_filled = true; ctx->knn_k = 0;
     ctx->graph_swept = false; ctx->pend_valid = false;
     ctx->pool_valid = false;
     ctx->rowpos_valid = false;
@@ -1161,7 +1161,7 @@ int32_t mpfmt_fmtstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t checkp
 
     // r-disc graph + per-edge free mask, all edges, on the device.  A filled graph of the same samples and radius (a
     // previous plan, or mpfmt_graph_import) is reused: only the obstacle-dependent sweep is redone.
-    if (!(ctx->graph_filled && ctx->graph_r == r) && (rc = mpfmt_graph_build_device(ctx, r, nullptr))) return rc;
+    if (!(ctx->graph_filled && ctx->graph_r == r && !ctx->knn_k) && (rc = mpfmt_graph_build_device(ctx, r, nullptr))) return rc;
     t[2] = now();
     ctx->pend_valid = false;
     if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc;
@@ -1177,6 +1177,124 @@ int32_t mpfmt_fmtstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t checkp
                                        checkpts ? F.data() : nullptr, ctx->ss.has ? ctx->ss.lo : nullptr,
                                        ctx->ss.has ? ctx->ss.hi : nullptr, init_idx, goal_kind, goal_params, A, C, path, res)))
         return mpfmt_fail(ctx, rc, "host recursion rejected its arguments");
+    t[5] = now();
+    fmt_times(ctx, res, t);
+    return MPFMT_OK;
+}
+
+// ---- k-nearest connections (connections = :K, fmt.jl:6,17-19; mutualknnF! / knnB!, nearneighbors.jl:9-11; kernels_knn.hip) ----------
+
+static bool knn_resident(const mpfmt_ctx* ctx) { return ctx->knn_k > 0 && ctx->graph_filled; }
+
+int32_t mpfmt_knn_count(mpfmt_ctx* ctx, int64_t k, int64_t* colptr, int64_t* nnz)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!colptr || !nnz) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "colptr / nnz is NULL");
+    if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
+    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the k-nearest graph needs an unsharded ctx");
+    if (k < 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "k must be >= 1");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int32_t rc;
+    if ((rc = mpfmt_knn_build(ctx, k))) return rc;
+    const int64_t n1 = ctx->N + 1;
+    void* scr;
+    if ((rc = mpfmt_scratch(ctx, sizeof(int64_t) * n1, &scr))) return rc;
+    hipLaunchKernelGGL(k_add1_i64, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, ctx->stream, ctx->colptr, n1, (int64_t*)scr);
+    HIPCHK(ctx, hipMemcpyAsync(colptr, scr, sizeof(int64_t) * n1, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *nnz = ctx->nnz;
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_knn_fill(mpfmt_ctx* ctx, int64_t* rowval, double* nzval, uint64_t* mutual)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!knn_resident(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "knn_fill before knn_count");
+    if (ctx->nnz > 0 && (!rowval || !nzval)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "rowval / nzval is NULL");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int32_t rc;
+    const int64_t nnz = ctx->nnz;
+    if (nnz > 0) {
+        const int64_t slab = std::min<int64_t>(nnz, (int64_t)1 << 26);
+        void* scr;
+        if ((rc = mpfmt_scratch(ctx, sizeof(int64_t) * slab, &scr))) return rc;
+        for (int64_t o = 0; o < nnz; o += slab) {
+            const int64_t n = std::min(slab, nnz - o);
+            hipLaunchKernelGGL(k_i32_to_i64_add1, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->rowval + o, n, (int64_t*)scr);
+            HIPCHK(ctx, hipMemcpyAsync(rowval + o, scr, sizeof(int64_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        HIPCHK(ctx, hipMemcpyAsync(nzval, ctx->nzval, sizeof(double) * nnz, hipMemcpyDeviceToHost, ctx->stream));
+        if (mutual) HIPCHK(ctx, hipMemcpyAsync(mutual, ctx->knn_mutual, sizeof(uint64_t) * (size_t)((nnz + 63) / 64), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_knn_graph_edges_free(mpfmt_ctx* ctx, uint64_t* mask)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!knn_resident(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "knn_graph_edges_free before knn_count");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int32_t rc;
+    ctx->pend_valid = false;
+    if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc;
+    const int64_t words = (ctx->nnz + 63) / 64;
+    if (words > 0) {
+        if (!mask) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "mask is NULL");
+        HIPCHK(ctx, hipMemcpyAsync(mask, ctx->graph_free, sizeof(uint64_t) * words, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return MPFMT_OK;
+}
+
+// fmt.jl:43-101 with nearF = mutualknnF, nearB = knnB: the Euclidean prelude of mpfmt_fmtstar, the k-nearest graph and its sweep on
+// the device, then the directed recursion on the host over the column graph, its transposed view and the mutual bits
+int32_t mpfmt_knn_fmtstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                          int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!A || !C || !path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
+    if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
+    if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
+    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "fmtstar runs on an unsharded ctx");
+    const int64_t N = ctx->N;
+    const int d = ctx->d;
+    if (init_idx < 1 || init_idx > N) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "init_idx out of range");
+    if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
+    if (k < 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "k must be >= 1");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    memset(res, 0, sizeof *res);
+    res->cost = INFINITY;
+    int32_t rc;
+    stamp t[6];
+    std::vector<uint64_t> F((N + 63) / 64, 0);
+    t[0] = now();
+    if ((rc = mpfmt_points_free(ctx, nullptr, N, F.data()))) return rc;
+    if (!bit(F, init_idx - 1)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
+    t[1] = now();
+    // (a resident k-nearest graph of the same samples and the same k_eff is reused: only the sweep is redone)
+    if (!(knn_resident(ctx) && std::min(ctx->knn_k, N - 1) == std::min(k, N - 1)) && (rc = mpfmt_knn_build(ctx, k))) return rc;
+    t[2] = now();
+    ctx->pend_valid = false;
+    if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    t[3] = now();
+    host_graph g;
+    if ((rc = graph_to_host(ctx, false, g))) return rc;
+    const size_t words = (size_t)(ctx->nnz + 63) / 64;
+    std::vector<uint64_t> mutual(std::max<size_t>(words, 1), 0);
+    if (words > 0) HIPCHK(ctx, hipMemcpy(mutual.data(), ctx->knn_mutual, sizeof(uint64_t) * words, hipMemcpyDeviceToHost));
+    std::vector<double> X((size_t)N * d);
+    HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * (size_t)N * d, hipMemcpyDeviceToHost));
+    mpfmt_csr_host csr;
+    mpfmt_csr_view csr_view;
+    const mpfmt_csr_view* pre_ptr = nullptr;
+    if (mpfmt_csc_transpose_device(ctx, &csr) == MPFMT_OK) { csr_view = {csr.rowptr.data(), csr.colidx.data(), csr.centry.data()}; pre_ptr = &csr_view; }
+    t[4] = now();
+    auto goal_hit = [&](int64_t z) { return mpfmt_is_goal_pt(&X[(size_t)z * d], d, goal_kind, goal_params); };
+    mpfmt_directed_fmt_recursion(N, g.colptr.data(), g.rowval.data(), g.nzval.data(), g.efree.data(), nullptr, checkpts ? F.data() : nullptr,
+                                 init_idx, goal_hit, A, C, path, res, pre_ptr, mutual.data());
     t[5] = now();
     fmt_times(ctx, res, t);
     return MPFMT_OK;
@@ -1669,6 +1787,10 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
         }
         return MPFMT_OK;
     }
+    if (strcmp(name, "knn_pairs_tested") == 0) { *value = ctx->knn_pairs; return MPFMT_OK; }
+    if (strcmp(name, "knn_rounds") == 0) { *value = ctx->knn_rounds; return MPFMT_OK; }
+    if (strcmp(name, "knn_short_columns") == 0) { *value = ctx->knn_short; return MPFMT_OK; }
+    if (strcmp(name, "knn_scan_columns") == 0) { *value = ctx->knn_scan; return MPFMT_OK; }
     if (strcmp(name, "survivors") == 0) { *value = ctx->survivors; return MPFMT_OK; }
     if (strcmp(name, "pairs_tested") == 0) { *value = ctx->pairs_tested; return MPFMT_OK; }
     if (strcmp(name, "nnz") == 0) { *value = ctx->nnz; return MPFMT_OK; }

@@ -170,10 +170,15 @@ int32_t mpfmt_host_fmt_recursion_impl(int64_t N, int32_t d, const double* X, con
 
 // fmt.jl:43-101 over a DIRECTED cost graph (quasi-metric spaces: double integrator, Dubins car): forward sets = rows of the
 // cost matrix (DSF = Dmat', linearquadratic.jl:73), backward sets = its columns (the CSC given).  efree / nseg are per CSC
-// entry (row -> column motion free; segment tests the reference would have counted), F the checkpts bitmap (may be NULL).
+// entry (row -> column motion free; segment tests the reference would have counted; nseg NULL: one each), F the checkpts bitmap
+// (may be NULL).  fwd_mask (per CSC entry, may be NULL: all) restricts the FORWARD sets: the examination loop (fmt.jl:70) walks an
+// entry (row z in column x) only when its bit is set -- the k-nearest graph's mutualknnF(z) = { x : z in knn(x) and x in knn(z) } --
+// while the backward sets stay whole columns: an open y in column x is a candidate parent of x whatever its bit, so the incremental
+// relaxation of open_node and the rescan both ignore the mask.
 void mpfmt_directed_fmt_recursion(int64_t N, const int64_t* colptr_, const int32_t* rowval_, const double* nzval_, const uint64_t* efree_,
                                   const uint8_t* nseg_, const uint64_t* F_, int64_t init_idx, const std::function<bool(int64_t)>& goal_hit,
-                                  int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res, const mpfmt_csr_view* pre)
+                                  int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res, const mpfmt_csr_view* pre,
+                                  const uint64_t* fwd_mask)
 {
     const int64_t nnz = colptr_[N];
     struct view64 { const int64_t* p; int64_t operator[](int64_t i) const { return p[i]; } };
@@ -238,6 +243,7 @@ void mpfmt_directed_fmt_recursion(int64_t N, const int64_t* colptr_, const int32
         for (int64_t a = rowptr[z]; a < rowptr[z + 1]; ++a) {                  // nearF(V, z, r, W), fmt.jl:70
             const int64_t x = colidx[a];
             if (!Wm[x]) continue;
+            if (fwd_mask && !bitp(fwd_mask, centry_at(a))) continue;             // not a forward neighbour of z (mutualknnF)
             if (checkpts && !bitp(F_, x)) continue;
             if (by[x] == -2 || (by[x] >= 0 && !Hm[by[x]])) {                   // nearB(V, x, r, H), fmt.jl:72-74
                 int64_t y_min = -1, e_min = -1; double c_min = 0.0;
@@ -251,7 +257,7 @@ void mpfmt_directed_fmt_recursion(int64_t N, const int64_t* colptr_, const int32
             }
             if (by[x] < 0) continue;
             const int64_t y_min = by[x], e_min = be[x];
-            count += nseg[e_min];                                              // boxesND.jl:26 per tested segment
+            count += nseg_ ? nseg[e_min] : 1;                                             // boxesND.jl:26 per tested segment
             if (bitp(efree_, e_min)) {
                 A[x] = y_min + 1; C[x] = bc[x];
                 heap.push(x, bc[x]);

@@ -19,5 +19,6 @@ int32_t mpfmt_host_fmt_recursion_impl(int64_t N, int32_t d, const double* X, con
                                       const uint8_t* nseg, int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
 void mpfmt_directed_fmt_recursion(int64_t N, const int64_t* colptr, const int32_t* rowval, const double* nzval, const uint64_t* efree,
                                   const uint8_t* nseg, const uint64_t* F, int64_t init_idx, const std::function<bool(int64_t)>& goal_hit,
-                                  int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res, const mpfmt_csr_view* pre);
+                                  int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res, const mpfmt_csr_view* pre,
+                                  const uint64_t* fwd_mask = nullptr);
 int64_t mpfmt_validate_csc(int64_t N, const int64_t* colptr, const int64_t* rowval, char* err, size_t errlen);

@@ -262,6 +262,14 @@ struct mpfmt_ctx {
     unsigned long long* d_pairs = nullptr;   // device counter: candidate pairs tested
     int64_t pairs_tested = 0;
 
+    // ---- k-nearest graph (kernels_knn.hip): installed in colptr / rowval / nzval like an r-disc graph, graph_r = its longest entry ----
+    int64_t knn_k = 0;                   // > 0 with graph_filled: the resident graph is the k-nearest one of this k (never "a filled graph of radius graph_r")
+    uint64_t* knn_mutual = nullptr;      // [ceil(nnz/64)] mutual bit per entry (row y in column x: x in knn(y))
+    double* knn_st = nullptr;            // [2][supertiles][d] boxes of 64 consecutive tiles
+    void* knn_bitmap = nullptr;          // [workgroups][ceil(N/64)] selection bitmaps
+    void* knn_lists = nullptr;           // the rounds' short-column lists and counters
+    int64_t knn_pairs = 0, knn_rounds = 0, knn_short = 0, knn_scan = 0;      // stats of the last build
+
     // ---- steering graphs (double integrator, Dubins, Reeds-Shepp): share colptr / rowval / nzval / graph_free ---------------
     mpfmt_steer steer_kind = MPFMT_STEER_DI;     // which steering graph the steer_* state describes
     double steer_r = 0.0;                // cost radius of the built graph
@@ -375,6 +383,9 @@ int32_t mpfmt_scan_i64_tmp(mpfmt_ctx* ctx, const int64_t* in, int64_t* out, size
 int32_t mpfmt_scan_i64(mpfmt_ctx* ctx, const int64_t* in, int64_t* out, size_t n);                     // tmp from the ctx's scratch buffer
 int32_t mpfmt_launch_rdisc_query(mpfmt_ctx* ctx, int64_t v0, double r, int64_t* k_out,
                                  int64_t* inds_host, double* ds_host, int64_t cap);
+
+// kernels_knn.hip -------------------------------------------------------------------------------
+int32_t mpfmt_knn_build(mpfmt_ctx* ctx, int64_t k);      // exact k-nearest graph + mutual bits, installed as the resident graph
 
 // kernels_sweep.hip -----------------------------------------------------------------------------
 int32_t mpfmt_launch_points_free(mpfmt_ctx* ctx, const int64_t* d_idx1, int64_t n, uint64_t* d_mask);

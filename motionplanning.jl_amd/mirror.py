@@ -460,18 +460,31 @@ def sample_free_(P, N, ensure_goal=True, ensure_goal_ct=5, rng=None, seed=None):
 
 
 # ---- planner (src/planners/fmt.jl) -------------------------------------------------------------------------------------------------
+def default_k(rm, d, N):
+    """The default k of fmtstar! (fmt.jl:6): min(ceil((2 rm)^d (e / d) log N), N - 1)."""
+    return int(min(math.ceil((2 * rm) ** d * (math.e / d) * math.log(N)), N - 1))
+
+
 def fmtstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_idx=1, checkpts=True, rng=None, seed=None,
-             band=None):
+             band=None, k=None):
     """fmtstar!(P, N; rm, connections, r, ensure_goal_ct, init_idx, checkpts)  (fmt.jl:3-119).  Returns
     (status, cost, elapsed) and fills P.solution like the reference.  band = None: the reference's sequential recursion (on the
     host, over GPU-built arrays); band >= 0: the recursion on the device with cost-band batches of that width in units of r
-    (mpfmt_*_fmtstar_wavefront; band = 0 expands only exact cost ties together)."""
+    (mpfmt_*_fmtstar_wavefront; band = 0 expands only exact cost ties together).  connections = "K": k-nearest connections
+    (forward sets = mutual k-nearest, backward sets = k-nearest; k = None: default_k, fmt.jl:6) in Euclidean spaces, host
+    recursion only."""
     t0 = time.time()
     N = len(P.V) if N is None else int(N)
     P.CC.count = 0
-    if connections != "R":
-        raise ValueError("Connection type must be radial (:R); the k-nearest branch of the reference calls "
-                         "undefined functions (fmt.jl:17-19)")
+    if connections not in ("R", "K"):
+        raise ValueError("Connection type must be radial (:R) or k-nearest (:K)")
+    r_given = r
+    if connections == "K":
+        if isinstance(P.SS.dist, (LinearQuadratic, DubinsExact, ReedsSheppExact)):
+            raise ValueError("connections = :K is built for Euclidean state spaces only (not the double integrator or the cars)")
+        if band is not None:
+            raise ValueError("connections = :K runs the recursion on the host only (band = ... is the device recursion)")
+        k = default_k(rm, dim(P.SS), N) if k is None else int(k)
     if r > 0:
         setup_steering(P.SS, r)
     if not is_free_state(P.init, P.CC, P.SS, P.ctx):
@@ -480,7 +493,7 @@ def fmtstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_i
         P.solution = MPSolution(P.status, math.inf, time.time() - t0, {})
         return math.inf
     free_volume_ub = sample_free_(P, N - len(P.V), ensure_goal_ct=ensure_goal_ct, rng=rng, seed=seed)
-    if r == 0:
+    if r == 0 and connections == "R":                       # (the k-nearest planner has no radius: fmt.jl:38-41 is the :R branch's)
         d = dim(P.SS)
         r = rm * 2 * (1 / d * free_volume_ub / (math.pi ** (d / 2) / math.gamma(d / 2 + 1)) * math.log(N) / N) ** (1 / d)
         setup_steering(P.SS, r)
@@ -491,7 +504,9 @@ def fmtstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_i
         # PointGoal(pt) is a WORKSPACE goal (goals.jl:45,111-114: state2workspace(v) == pt); for SE2 states the library's POINT kind
         # means an exact state, so the workspace point goes down as the ball of radius 0 around it (norm(v_ws - pt) <= 0)
         gkind, gpar = _lib.GOAL_BALL, np.concatenate([gpar, [0.0]])
-    if band is not None:
+    if connections == "K":
+        res = ctx.knn_fmtstar(k, gkind, gpar, init_idx=init_idx, checkpts=checkpts)
+    elif band is not None:
         bw = float(band) * r
         if isinstance(P.SS.dist, LinearQuadratic):
             res = ctx.di_fmtstar_wavefront(P.SS.dist.rho, r, gkind, gpar, band=bw, init_idx=init_idx, checkpts=checkpts)
@@ -514,6 +529,8 @@ def fmtstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_i
     path = res["path"]
     meta = {"radius_multiplier": rm, "collision_checks": res["collision_checks"], "num_samples": N, "cost": res["cost"],
             "cumcost": res["C"][path - 1], "planner": "FMTstar", "solved": res["status"] == 1, "tree": res["A"],
-            "path": path, "r": r, "ms_graph": res["ms_graph"], "ms_sweep": res["ms_sweep"], "ms_host_loop": res["ms_host_loop"]}
+            "path": path, "r": r if connections == "R" else r_given, "ms_graph": res["ms_graph"], "ms_sweep": res["ms_sweep"], "ms_host_loop": res["ms_host_loop"]}
+    if connections == "K":
+        meta["k"] = k
     P.solution = MPSolution(P.status, res["cost"], time.time() - t0, meta)
     return P.status, P.solution.cost, P.solution.elapsed
