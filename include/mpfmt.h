@@ -209,6 +209,56 @@ MPFMT_API int32_t mpfmt_host_fmt_recursion(int64_t N, int32_t d, const double* X
                                  const double* ss_hi, int64_t init_idx, int32_t goal_kind, const double* goal_params,
                                  int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
 
+/* ---- roadmap queries (PRM*): exact shortest paths over the free-edge graph.  The reference names the graph planner and never
+ *      built it (src/problems.jl:57, "# TODO: graph (PRM)"); the semantics here are this library's.
+ *      The graph is the ctx's resident graph slot -- r-disc or k-nearest -- in the device-native CSC: entry b of column x with row y
+ *      is the DIRECTED edge y -> x of weight nzval[b]; its free bit is mask bit b = is_free_motion(V[y], V[x]) (the reading of
+ *      mpfmt_host_fmt_recursion).  An edge is USABLE iff its bit is set and, with checkpts != 0, the point bit F[x] of its target is
+ *      set (fmt.jl:71); the source itself is exempt from F.
+ *      Costs for a source s: C[s] = 0; C[x] = the least value of the left-to-right fp64 fold (((0 + w1) + w2) + ...) over all usable
+ *      paths s -> x; C[x] = +Inf when there is none (FMT* writes 0 for unvisited samples; these calls do not).  fl(a + w) is
+ *      nondecreasing in a and w >= 0, so Dijkstra and any chaotic relaxation started from +Inf reach the same least fixed point of
+ *      C[x] = min_y fl(C[y] + w_yx): the values are unique, independent of scheduling, and bit-identical between
+ *      mpfmt_graph_sssp and mpfmt_host_graph_sssp (DESIGN.md "PRM* roadmap queries" has the argument and what it asks of the device).
+ *      Parents: A[x] (1-based; 0 for the source and for unreached samples) = the usable y of lowest (C[y], y) among those with
+ *      fl(C[y] + w_yx) == C[x], found by a final pass over the finished C -- never during relaxation -- so fl(C[A[x]] + w) == C[x]
+ *      holds exactly.  Following A from a reached x arrives at s in fewer than N hops whenever every reached x != s has such a y
+ *      with C[y] < C[x] (always, unless a whole group of equal-cost samples hangs together by zero-length or absorbed edges only).
+ * mpfmt_host_graph_sssp : a binary-heap Dijkstra on the host over the device-native arrays (colptr[N+1] 0-based offsets, rowval
+ *      0-based int32, efree one bit per entry, F the point bitmap or NULL for checkpts = false; source 1-based; A may be NULL).
+ *      No ctx, no device.  MPFMT_ERR_ARG on malformed arrays (colptr[0] != 0, decreasing colptr, a row out of range, a negative or
+ *      NaN weight).
+ * mpfmt_graph_sssp : the same field on the device for nsrc sources (1-based), one after another, over the resident graph and mask
+ *      WITHOUT copying or transposing them.  C / A are nsrc x N, source-major (A may be NULL); info[nsrc] (may be NULL).
+ *      checkpts != 0 sweeps the point bitmap on the device first.  MPFMT_ERR_STATE: no resident r-disc / k-nearest graph, no mask
+ *      for the current graph and obstacle set (a mask goes stale with mpfmt_upload_boxes / mpfmt_upload_shapes2d /
+ *      mpfmt_set_state_bounds: sweep again -- this call never sweeps edges on its own), or a sharded ctx; MPFMT_ERR_ARG: a source
+ *      out of range.  A refused call leaves the ctx as it was.
+ * mpfmt_prmstar / mpfmt_knn_prmstar : the planner: mpfmt_graph_step_device(r) (k-nearest: the build + sweep of mpfmt_knn_fmtstar)
+ *      -- graph and mask are reused when they are resident for this r (k) and obstacle set, a stale mask is swept again --, the
+ *      checkpts sweep, the field from init_idx and goal extraction: the goal node is the reached sample inside the goal region of
+ *      lowest (C, index).  A, C (N entries, C = +Inf for unreached) and path as mpfmt_fmtstar; res->status / cost / z / path_len /
+ *      nnz mean what they mean there (no goal sample reached: status 0, z = init_idx, cost = +Inf, path = (init_idx));
+ *      res->ms_host_loop = the field and the extraction.  res->collision_checks = 0: the planner consults a mask that the step
+ *      swept whole, it asks for no lazy edge test of its own (there is no counterpart of P.CC.count, boxesND.jl:26).
+ *      An infeasible init is MPFMT_ERR_INFEASIBLE as in mpfmt_fmtstar.  Euclidean samples, unsharded ctx.
+ *      Timers: "sssp_relax" (all rounds of one source), "sssp_parents"; stats "sssp_rounds", "sssp_relaxations", "sssp_reached"
+ *      (last source). */
+typedef struct {
+    int64_t reached;           /* samples with C < +Inf, the source included */
+    int64_t rounds;            /* relaxation rounds that ran (the last one changes nothing) */
+    int64_t relaxations;       /* fl(C[y] + w) evaluated, all rounds; scheduling-dependent, unlike C and A */
+    double  ms_device;         /* device time of the source: init, rounds, parent pass */
+} mpfmt_sssp_info;
+MPFMT_API int32_t mpfmt_host_graph_sssp(int64_t N, const int64_t* colptr, const int32_t* rowval, const double* nzval, const uint64_t* efree,
+                              const uint64_t* F, int64_t source, double* C, int64_t* A);
+MPFMT_API int32_t mpfmt_graph_sssp(mpfmt_ctx* ctx, const int64_t* sources, int64_t nsrc, int32_t checkpts, double* C, int64_t* A,
+                         mpfmt_sssp_info* info);
+MPFMT_API int32_t mpfmt_prmstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                      int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
+MPFMT_API int32_t mpfmt_knn_prmstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                          int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
+
 /* ---- Monte-Carlo collision probability of candidate edges (BASELINE.json configs[4]).  The reference
  *      has no implementation (README.md:9-10 cites the papers only); the workload is the one SURVEY 8d defines: per edge
  *      (src[e] -> dst[e], 1-based sample indices) `rollouts` perturbed copies of the 2-point trajectory, each put through

@@ -170,6 +170,45 @@ function fmtstar_hip!(P::MPProblem, r::Float64; init_idx = 1, checkpts = true, b
     P.status, P.solution.cost, P.solution.elapsed
 end
 
+# ---- PRM*: the graph planner the reference leaves open (src/problems.jl:57, "# TODO: graph (PRM)"): exact cost-to-come of every
+#      sample over the free-edge graph, on the device (include/mpfmt.h "roadmap queries").  The symbols are named here once; the C
+#      caller that executes these calls with the same widths is tests/abi_c/abi_caller3.c. ----
+const sym_prmstar = :mpfmt_prmstar
+const sym_knn_prmstar = :mpfmt_knn_prmstar
+const sym_graph_sssp = :mpfmt_graph_sssp
+immutable SsspInfo
+    reached::Int64; rounds::Int64; relaxations::Int64; ms_device::Float64
+end
+# connections = :R (radius r) or :K (k nearest); metadata["cost_to_come"] = the field (Inf = unreachable)
+function hip_prmstar!(P::MPProblem, r::Float64; init_idx = 1, checkpts = true, connections = :R, k = 0)
+    DS = P.V.DS; N = length(P.V)
+    A = Vector{Int}(N); C = Vector{Float64}(N); path = Vector{Int}(N); res = Ref{FmtResult}()
+    g = [P.goal.center; P.goal.radius]           # BallGoal (goals.jl:17-21) = MPFMT_GOAL_BALL
+    rc = connections == :K ?
+        ccall((sym_knn_prmstar, libmpfmt), Int32,
+              (Ptr{Void}, Int64, Int64, Int32, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{FmtResult}),
+              DS.ctx, k, init_idx, checkpts, 1, g, A, C, path, res) :
+        ccall((sym_prmstar, libmpfmt), Int32,
+              (Ptr{Void}, Float64, Int64, Int32, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{FmtResult}),
+              DS.ctx, r, init_idx, checkpts, 1, g, A, C, path, res)
+    rc == -6 && (warn("Initial state is infeasible!"); P.status = :failed; return Inf)
+    chk(DS.ctx, rc)
+    P.status = res[].status == 1 ? :solved : :failed
+    P.solution = MPSolution(P.status, res[].cost, (res[].ms_graph + res[].ms_sweep + res[].ms_host_loop) / 1e3,
+                            Dict("collision_checks" => res[].collision_checks, "tree" => A, "cost" => res[].cost,
+                                 "path" => path[1:res[].path_len], "planner" => "prmstar", "r" => r, "num_samples" => N,
+                                 "cost_to_come" => C))
+    P.status, P.solution.cost, P.solution.elapsed
+end
+# multi-query use: the fields of several sources over the graph and mask a step (or hip_prmstar!) left resident; C is N x nsrc
+function hip_graph_sssp(DS::HIPDistanceDS, N::Int, sources::Vector{Int}; checkpts = true)
+    n = length(sources)
+    C = Matrix{Float64}(N, n); A = Matrix{Int}(N, n); info = Vector{SsspInfo}(n)
+    chk(DS.ctx, ccall((sym_graph_sssp, libmpfmt), Int32, (Ptr{Void}, Ptr{Int64}, Int64, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{SsspInfo}),
+                      DS.ctx, sources, n, checkpts, C, A, info))
+    C, A, info
+end
+
 # ---- multi-GPU: ONE Julia thread, G ctxs (SURVEY 8e); the RCCL exchange lives behind the ABI ------------------------
 function hip_comm_create!(ctxs::Vector{Ptr{Void}})
     id = Vector{UInt8}(128)

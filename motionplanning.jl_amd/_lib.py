@@ -41,6 +41,10 @@ class WfInfo(C.Structure):
                 ("tot_conn", C.c_int64)]
 
 
+class SsspInfo(C.Structure):
+    _fields_ = [("reached", C.c_int64), ("rounds", C.c_int64), ("relaxations", C.c_int64), ("ms_device", C.c_double)]
+
+
 WF_SINGLE, WF_EAGER, WF_LAZY = 1, 2, 4
 COMM_ID_BYTES = 128
 
@@ -76,6 +80,12 @@ SYMBOLS = [
     ("mpfmt_host_fmt_recursion", C.c_int32, [C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p,
                                              c_d_p, c_d_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, c_d_p, c_i64_p,
                                              C.POINTER(FmtResult)]),
+    ("mpfmt_host_graph_sssp", C.c_int32, [C.c_int64, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p, C.c_int64, c_d_p, c_i64_p]),
+    ("mpfmt_graph_sssp", C.c_int32, [C.c_void_p, c_i64_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(SsspInfo)]),
+    ("mpfmt_prmstar", C.c_int32, [C.c_void_p, C.c_double, C.c_int64, C.c_int32, C.c_int32, c_d_p, c_i64_p, c_d_p, c_i64_p,
+                                  C.POINTER(FmtResult)]),
+    ("mpfmt_knn_prmstar", C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_d_p, c_i64_p, c_d_p, c_i64_p,
+                                      C.POINTER(FmtResult)]),
     ("mpfmt_mc_edges_collision", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, c_i64_p]),
     ("mpfmt_mc_edges_collision_is", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("mpfmt_mc_edges_collision_ais", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, C.POINTER(C.c_uint64),
@@ -260,6 +270,25 @@ def host_fmt_recursion(X, colptr0, rowval0, nzval, efree, F, goal_kind, goal_par
         raise MPFMTError(rc, "mpfmt_host_fmt_recursion rejected its arguments")
     return dict(status=int(res.status), cost=float(res.cost), z=int(res.z), collision_checks=int(res.collision_checks),
                 nnz=int(res.nnz), ms_host_loop=float(res.ms_host_loop), A=A, C=Cc, path=path[:res.path_len].copy())
+
+
+def host_graph_sssp(colptr0, rowval0, nzval, efree, F=None, source=1, want_parents=True):
+    """PRM* cost-to-come field of one source (1-based) by a host Dijkstra over the device-native arrays (include/mpfmt.h, "roadmap
+    queries"); host only, no GPU needed.  colptr0 / rowval0 0-based (rowval0 int32), efree / F packed uint64 bit masks (F None:
+    checkpts=false).  Returns (C, A): C = +Inf for unreached samples, A 1-based parents (0 = none; None without want_parents)."""
+    colptr0 = np.ascontiguousarray(colptr0, dtype=np.int64)
+    N = colptr0.size - 1
+    rowval0 = np.ascontiguousarray(rowval0, dtype=np.int32)
+    nzval = np.ascontiguousarray(nzval, dtype=np.float64)
+    efree = np.ascontiguousarray(efree, dtype=np.uint64)
+    Fp = None if F is None else np.ascontiguousarray(F, dtype=np.uint64)
+    Cc = np.empty(max(N, 1), dtype=np.float64)
+    A = np.empty(max(N, 1), dtype=np.int64) if want_parents else None
+    rc = lib().mpfmt_host_graph_sssp(N, _ip(colptr0), rowval0.ctypes.data_as(C.POINTER(C.c_int32)), _dp(nzval), _up(efree), _up(Fp),
+                                     int(source), _dp(Cc), _ip(A))
+    if rc != 0:
+        raise MPFMTError(rc, "mpfmt_host_graph_sssp rejected its arguments")
+    return Cc[:N], (None if A is None else A[:N])
 
 
 class Context:
@@ -491,6 +520,41 @@ class Context:
         res = FmtResult()
         self._chk(self._L.mpfmt_knn_fmtstar(self._h, int(k), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g),
                                             _ip(A), _dp(Cc), _ip(path), C.byref(res)))
+        return self._fmt_out(res, A, Cc, path)
+
+    # ---- PRM* roadmap queries: shortest paths over the resident free-edge graph ------------------------------
+    def graph_sssp(self, sources, checkpts=True, want_parents=True):
+        """Cost-to-come fields over the resident graph and mask (graph_step_device, or knn_graph + knn_graph_edges_free) for the
+        1-based `sources`: dict(C (nsrc, N), +Inf = unreached; A (nsrc, N) 1-based parents or None; info = one dict per source with
+        reached, rounds, relaxations, ms_device)."""
+        src = np.ascontiguousarray(np.atleast_1d(sources), dtype=np.int64)
+        n = src.size
+        Cc = np.empty((max(n, 1), max(self.N, 1)), dtype=np.float64)
+        A = np.empty((max(n, 1), max(self.N, 1)), dtype=np.int64) if want_parents else None
+        info = (SsspInfo * max(n, 1))()
+        self._chk(self._L.mpfmt_graph_sssp(self._h, _ip(src), n, int(bool(checkpts)), _dp(Cc), _ip(A), info))
+        return dict(C=Cc[:n, :self.N], A=None if A is None else A[:n, :self.N],
+                    info=[{k: getattr(info[i], k) for k, _ in SsspInfo._fields_} for i in range(n)])
+
+    def prmstar(self, r, goal_kind, goal_params, init_idx=1, checkpts=True):
+        """PRM*: graph_step_device(r) (reused when resident), then the exact cost-to-come field of init_idx over the free-edge graph and
+        the best goal sample; same dict as fmtstar, with C = +Inf for unreached samples."""
+        g = np.ascontiguousarray(goal_params, dtype=np.float64)
+        A, Cc, path = self._fmt_arrays()
+        res = FmtResult()
+        self._chk(self._L.mpfmt_prmstar(self._h, float(r), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g),
+                                        _ip(A), _dp(Cc), _ip(path), C.byref(res)))
+        self.nnz = int(res.nnz)
+        return self._fmt_out(res, A, Cc, path)
+
+    def knn_prmstar(self, k, goal_kind, goal_params, init_idx=1, checkpts=True):
+        """prmstar over the (directed) k-nearest graph."""
+        g = np.ascontiguousarray(goal_params, dtype=np.float64)
+        A, Cc, path = self._fmt_arrays()
+        res = FmtResult()
+        self._chk(self._L.mpfmt_knn_prmstar(self._h, int(k), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g),
+                                            _ip(A), _dp(Cc), _ip(path), C.byref(res)))
+        self.nnz = int(res.nnz)
         return self._fmt_out(res, A, Cc, path)
 
     def _fmt_arrays(self, want_tree=True):

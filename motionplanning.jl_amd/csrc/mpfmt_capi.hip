@@ -240,6 +240,7 @@ int32_t mpfmt_ctx_destroy(mpfmt_ctx* ctx)
     if (ctx->side_stream) { hipStreamSynchronize(ctx->side_stream); hipStreamDestroy(ctx->side_stream); hipEventDestroy(ctx->ev_fork); hipEventDestroy(ctx->ev_join); }
     for (int k = 0; k < 2; ++k) { if (ctx->copy_stream[k]) hipStreamDestroy(ctx->copy_stream[k]); if (ctx->ev_conv[k]) hipEventDestroy(ctx->ev_conv[k]); if (ctx->ev_copy[k]) hipEventDestroy(ctx->ev_copy[k]); }
     mpfmt_wf_free(ctx);
+    mpfmt_sssp_free(ctx);
     if (ctx->aux) { mpfmt_ctx_destroy(ctx->aux); ctx->aux = nullptr; }
     for (void* b : bufs) if (b) hipFree(b);
     timer_resolve(ctx);
@@ -1300,6 +1301,133 @@ int32_t mpfmt_knn_fmtstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t c
     return MPFMT_OK;
 }
 
+// ---- PRM* roadmap queries: shortest paths over the resident free-edge graph (kernels_sssp.hip) -------------------------------------------
+
+// the checks every roadmap query starts with; nothing in the ctx has been touched when one of them refuses
+static int32_t sssp_ready(mpfmt_ctx* ctx)
+{
+    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "roadmap queries run on an unsharded ctx");
+    if (!ctx->Xo || !ctx->graph_filled) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no resident r-disc or k-nearest graph (mpfmt_graph_step_device, mpfmt_knn_count)");
+    if (!ctx->graph_swept || !ctx->graph_free)
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no free-edge mask for the resident graph and the current obstacle set (sweep it: mpfmt_graph_step_device, "
+                                                "mpfmt_graph_edges_free, mpfmt_knn_graph_edges_free)");
+    return MPFMT_OK;
+}
+
+// the checkpts bitmap of the current samples and obstacle set into ctx->sssp_F
+static int32_t sssp_point_bitmap(mpfmt_ctx* ctx)
+{
+    int32_t rc;
+    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->sssp_F, sizeof(uint64_t) * (size_t)((ctx->N + 63) / 64)))) return rc;
+    return mpfmt_launch_points_free(ctx, nullptr, ctx->N, ctx->sssp_F);
+}
+
+int32_t mpfmt_graph_sssp(mpfmt_ctx* ctx, const int64_t* sources, int64_t nsrc, int32_t checkpts, double* C, int64_t* A, mpfmt_sssp_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (nsrc < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "nsrc < 0");
+    if (nsrc > 0 && (!sources || !C)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "sources / C is NULL");
+    int32_t rc;
+    if ((rc = sssp_ready(ctx))) return rc;
+    if (checkpts && !ctx->have_boxes && ctx->cc_kind == 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "checkpts needs an obstacle set");
+    if ((rc = check_idx(ctx, sources, nsrc, "sources"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (checkpts && nsrc > 0 && (rc = sssp_point_bitmap(ctx))) return rc;
+    const int64_t N = ctx->N;
+    for (int64_t q = 0; q < nsrc; ++q)
+        if ((rc = mpfmt_sssp_device(ctx, sources[q] - 1, checkpts ? ctx->sssp_F : nullptr, C + q * N, A ? A + q * N : nullptr, info ? info + q : nullptr)))
+            return rc;
+    return MPFMT_OK;
+}
+
+// graph + mask (reused when resident), checkpts bitmap, field from init_idx, goal extraction; k > 0: the k-nearest graph
+static int32_t prmstar_impl(mpfmt_ctx* ctx, double r, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                            int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!A || !C || !path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
+    if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
+    if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
+    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "prmstar runs on an unsharded ctx");
+    const int64_t N = ctx->N;
+    const int d = ctx->d;
+    if (init_idx < 1 || init_idx > N) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "init_idx out of range");
+    if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
+    if (k == 0 && (!(r > 0.0) || !std::isfinite(r))) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "radius must be finite and > 0");
+    if (k < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "k must be >= 1");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    memset(res, 0, sizeof *res);
+    res->cost = INFINITY;
+    int32_t rc;
+    stamp t[6];
+    t[0] = now();
+    if ((rc = sssp_point_bitmap(ctx))) return rc;
+    uint64_t init_word = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&init_word, ctx->sssp_F + ((init_idx - 1) >> 6), sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (!((init_word >> ((init_idx - 1) & 63)) & 1ull)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
+    t[1] = now();
+    t[2] = t[1];
+    if (k > 0) {
+        if (!(knn_resident(ctx) && std::min(ctx->knn_k, N - 1) == std::min(k, N - 1))) {
+            if ((rc = mpfmt_knn_build(ctx, k))) return rc;
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        t[2] = now();
+        if (!ctx->graph_swept) { ctx->pend_valid = false; if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc; }
+    } else if (ctx->graph_filled && ctx->graph_r == r && !ctx->knn_k) {
+        if (!ctx->graph_swept) { ctx->pend_valid = false; if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc; }
+    } else {
+        if ((rc = mpfmt_graph_step_device(ctx, r, nullptr))) return rc;
+        t[2] = now();
+        if (!ctx->graph_swept) { ctx->pend_valid = false; if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc; }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    t[3] = now();
+    if ((rc = sssp_ready(ctx))) return rc;
+    t[4] = now();
+    mpfmt_sssp_info inf;
+    if ((rc = mpfmt_sssp_device(ctx, init_idx - 1, checkpts ? ctx->sssp_F : nullptr, C, A, &inf))) return rc;
+    // goal node: the reached sample inside the goal region of lowest (C, index)
+    std::vector<double> X((size_t)N * d);
+    HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * (size_t)N * d, hipMemcpyDeviceToHost));
+    int64_t z = -1;
+    for (int64_t i = 0; i < N; ++i)
+        if (C[i] < INFINITY && (z < 0 || C[i] < C[z]) && mpfmt_is_goal_pt(&X[(size_t)i * d], d, goal_kind, goal_params)) z = i;
+    std::vector<int64_t> rev;
+    if (z >= 0) {
+        int64_t cur = z;
+        rev.push_back(cur + 1);
+        while (cur != init_idx - 1 && (int64_t)rev.size() <= N) {
+            const int64_t p = A[cur];
+            if (p == 0) break;
+            cur = p - 1;
+            rev.push_back(cur + 1);
+        }
+        res->status = 1; res->cost = C[z]; res->z = z + 1;
+    } else {
+        rev.push_back(init_idx);
+        res->status = 0; res->cost = INFINITY; res->z = init_idx;
+    }
+    for (size_t i = 0; i < rev.size() && i < (size_t)N; ++i) path[i] = rev[rev.size() - 1 - i];
+    res->path_len = (int64_t)std::min<size_t>(rev.size(), (size_t)N);
+    res->collision_checks = 0;
+    t[5] = now();
+    fmt_times(ctx, res, t);
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_prmstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                      int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{ return prmstar_impl(ctx, r, 0, init_idx, checkpts, goal_kind, goal_params, A, C, path, res); }
+
+int32_t mpfmt_knn_prmstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                          int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{
+    if (ctx && k < 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "k must be >= 1");
+    return prmstar_impl(ctx, 0.0, k, init_idx, checkpts, goal_kind, goal_params, A, C, path, res);
+}
+
 // ---- steering spaces: double integrator (LinearQuadratic quasi-metric), Dubins and Reeds-Shepp cars (kernels_di.hip, kernels_car.hip)
 
 static int32_t di_check(mpfmt_ctx* ctx, double rho, double r)
@@ -1791,6 +1919,9 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "knn_rounds") == 0) { *value = ctx->knn_rounds; return MPFMT_OK; }
     if (strcmp(name, "knn_short_columns") == 0) { *value = ctx->knn_short; return MPFMT_OK; }
     if (strcmp(name, "knn_scan_columns") == 0) { *value = ctx->knn_scan; return MPFMT_OK; }
+    if (strcmp(name, "sssp_rounds") == 0) { *value = ctx->sssp_rounds; return MPFMT_OK; }
+    if (strcmp(name, "sssp_relaxations") == 0) { *value = ctx->sssp_relax; return MPFMT_OK; }
+    if (strcmp(name, "sssp_reached") == 0) { *value = ctx->sssp_reached; return MPFMT_OK; }
     if (strcmp(name, "survivors") == 0) { *value = ctx->survivors; return MPFMT_OK; }
     if (strcmp(name, "pairs_tested") == 0) { *value = ctx->pairs_tested; return MPFMT_OK; }
     if (strcmp(name, "nnz") == 0) { *value = ctx->nnz; return MPFMT_OK; }

@@ -279,6 +279,70 @@ void mpfmt_directed_fmt_recursion(int64_t N, const int64_t* colptr_, const int32
 }
 
 
+// PRM* cost-to-come field over the free-edge graph (include/mpfmt.h, "roadmap queries"): a binary-heap Dijkstra from one source
+// over the device-native CSC.  Entry b of column x with row y is the edge y -> x, so the scan of a settled y needs its out-edges:
+// the CSR transpose is built here.  A label is the left-to-right fp64 fold of the weights along a path, fl(C[y] + w); fl(a + w) is
+// nondecreasing in a and w >= 0, so the order in which Dijkstra settles does not matter for the values: they are the least fixed
+// point of C[x] = min_y fl(C[y] + w_yx), the same one the device's chaotic relaxation reaches (csrc/kernels_sssp.hip).  Parents are
+// not taken from the relaxation: the final pass below picks, per reached x, the usable y of lowest (C[y], y) with
+// fl(C[y] + w) == C[x] -- the rule of the device's parent kernel, a function of C alone.
+int32_t mpfmt_host_graph_sssp(int64_t N, const int64_t* colptr, const int32_t* rowval, const double* nzval, const uint64_t* efree,
+                              const uint64_t* F, int64_t source, double* C, int64_t* A)
+{
+    if (!colptr || !efree || !C || N < 1 || source < 1 || source > N) return MPFMT_ERR_ARG;
+    if (colptr[0] != 0) return MPFMT_ERR_ARG;
+    for (int64_t j = 0; j < N; ++j) if (colptr[j + 1] < colptr[j]) return MPFMT_ERR_ARG;
+    const int64_t nnz = colptr[N];
+    if (nnz > 0 && (!rowval || !nzval)) return MPFMT_ERR_ARG;
+    for (int64_t e = 0; e < nnz; ++e) if (rowval[e] < 0 || rowval[e] >= N || !(nzval[e] >= 0.0)) return MPFMT_ERR_ARG;
+    auto bitp = [](const uint64_t* m, int64_t i) { return (m[i >> 6] >> (i & 63)) & 1ull; };
+    const int64_t s = source - 1;
+    // out-edges of every sample: the usable entries only (free bit set, target allowed by F)
+    std::vector<int64_t> rowptr((size_t)N + 1, 0);
+    for (int64_t x = 0; x < N; ++x) {
+        if (F && !bitp(F, x)) continue;
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b) if (bitp(efree, b)) rowptr[rowval[b] + 1]++;
+    }
+    for (int64_t i = 0; i < N; ++i) rowptr[i + 1] += rowptr[i];
+    std::vector<int64_t> cur(rowptr.begin(), rowptr.end() - 1);
+    std::vector<int32_t> tgt((size_t)std::max<int64_t>(rowptr[N], 1));
+    std::vector<double> wgt((size_t)std::max<int64_t>(rowptr[N], 1));
+    for (int64_t x = 0; x < N; ++x) {
+        if (F && !bitp(F, x)) continue;
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b)
+            if (bitp(efree, b)) { const int64_t a = cur[rowval[b]]++; tgt[a] = (int32_t)x; wgt[a] = nzval[b]; }
+    }
+    for (int64_t i = 0; i < N; ++i) C[i] = INFINITY;
+    C[s] = 0.0;
+    Heap heap;
+    heap.push(s, 0.0);
+    while (!heap.empty()) {
+        const double cy = heap.pri[0];
+        const int64_t y = heap.pop();
+        if (cy > C[y]) continue;                                               // a stale entry: y was settled at a lower label
+        for (int64_t a = rowptr[y]; a < rowptr[y + 1]; ++a) {
+            const int64_t x = tgt[a];
+            const double c = cy + wgt[a];
+            if (c < C[x]) { C[x] = c; heap.push(x, c); }
+        }
+    }
+    if (!A) return MPFMT_OK;
+    for (int64_t x = 0; x < N; ++x) {
+        A[x] = 0;
+        if (x == s || !(C[x] < INFINITY)) continue;
+        int64_t yb = -1; double cb = 0.0;
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b) {
+            if (!bitp(efree, b)) continue;
+            const int64_t y = rowval[b];
+            const double cy = C[y];
+            if (!(cy + nzval[b] == C[x])) continue;
+            if (yb < 0 || cy < cb || (cy == cb && y < yb)) { yb = y; cb = cy; }
+        }
+        A[x] = yb + 1;
+    }
+    return MPFMT_OK;
+}
+
 // ImmutableNNC(D, r) handed in from outside (mpfmt_graph_import; nearneighbors.jl:23-28): 1-based CSC, monotone colptr,
 // rows in range, strictly ascending inside a column, no self loops.  Returns 0, or the 1-based column at fault (negative:
 // -1 colptr[1] != 1, -2 colptr decreases) with a message in err.

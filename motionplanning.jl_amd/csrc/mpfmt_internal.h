@@ -318,6 +318,16 @@ struct mpfmt_ctx {
     int32_t wf_pos_used = 0;             // stat: the last device solve gathered by position
     int32_t wf_force_sharded = 0;        // option: run the sharded form of the wavefront step (own-column marking, triples, exchange) at world = 1
     void* wf = nullptr;                  // mpfmt_wf: W / H / C / A and the batch lists of a running wavefront solve
+
+    // ---- PRM* shortest-path field (kernels_sssp.hip): labels, parents, the three changed-sample bitmaps, round state, point bitmap ----
+    double* sssp_C = nullptr;            // [N]
+    int64_t* sssp_A = nullptr;           // [N] 1-based parents
+    uint64_t* sssp_bm = nullptr;         // [3][ceil(N/64)]
+    void* sssp_state = nullptr;          // sssp_state (device) and its pinned host mirror
+    void* sssp_state_host = nullptr;
+    uint64_t* sssp_F = nullptr;          // [ceil(N/64)] checkpts bitmap of the call
+    hipEvent_t sssp_ev[2] = {nullptr, nullptr};
+    int64_t sssp_rounds = 0, sssp_relax = 0, sssp_reached = 0;      // stats of the last source
 };
 
 // error helpers ---------------------------------------------------------------------------------
@@ -437,6 +447,12 @@ int32_t mpfmt_wf_run(mpfmt_ctx* ctx);
 int32_t mpfmt_wf_begin_directed(mpfmt_ctx* ctx, int64_t init_idx, int32_t checkpts, const uint64_t* F_host, int32_t goal_kind,
                                 const double* goal_params, int32_t gd, double band, int32_t flags);
 void mpfmt_wf_info_now(mpfmt_ctx* ctx, mpfmt_wf_info* info);
+
+// kernels_sssp.hip ---------------------------------------------------------------------------------
+// one source (0-based) over the resident graph and mask; d_F = point bitmap on the device or nullptr; C_host [N] / A_host [N] (may be
+// nullptr) receive the field; the labels and parents also stay in ctx->sssp_C / sssp_A
+int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, double* C_host, int64_t* A_host, mpfmt_sssp_info* info);
+void mpfmt_sssp_free(mpfmt_ctx* ctx);
 
 // kernels_expand.hip ----------------------------------------------------------------------------
 int32_t mpfmt_launch_expand(mpfmt_ctx* ctx, const uint64_t* d_W, const uint64_t* d_H, const uint64_t* d_F,

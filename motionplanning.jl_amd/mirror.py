@@ -534,3 +534,47 @@ def fmtstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_i
         meta["k"] = k
     P.solution = MPSolution(P.status, res["cost"], time.time() - t0, meta)
     return P.status, P.solution.cost, P.solution.elapsed
+
+
+def prmstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_idx=1, checkpts=True, rng=None, seed=None, k=None):
+    """The graph planner the reference leaves as a TODO (src/problems.jl:57, "# TODO: graph (PRM)"): PRM* over the same samples, radius
+    rule (fmt.jl:38-41) and connection types as fmtstar_.  The whole r-disc (connections = "R") or k-nearest ("K") graph and its
+    free-edge mask are built on the device, then the EXACT cost-to-come of every sample from init over the free-edge graph
+    (mpfmt_prmstar / mpfmt_knn_prmstar); the answer is the goal sample of lowest cost.  Fills P.solution like fmtstar_, with
+    metadata["planner"] = "prmstar" and metadata["cost_to_come"] = the field (inf = unreachable).  Euclidean state spaces."""
+    t0 = time.time()
+    N = len(P.V) if N is None else int(N)
+    P.CC.count = 0
+    if connections not in ("R", "K"):
+        raise ValueError("Connection type must be radial (:R) or k-nearest (:K)")
+    if isinstance(P.SS.dist, (LinearQuadratic, DubinsExact, ReedsSheppExact)):
+        raise ValueError("prmstar_ is built for Euclidean state spaces only (not the double integrator or the cars)")
+    r_given = r
+    if connections == "K":
+        k = default_k(rm, dim(P.SS), N) if k is None else int(k)
+    if not is_free_state(P.init, P.CC, P.SS, P.ctx):
+        warnings.warn("Initial state is infeasible!")
+        P.status = "failed"
+        P.solution = MPSolution(P.status, math.inf, time.time() - t0, {})
+        return math.inf
+    free_volume_ub = sample_free_(P, N - len(P.V), ensure_goal_ct=ensure_goal_ct, rng=rng, seed=seed)
+    if r == 0 and connections == "R":
+        d = dim(P.SS)
+        r = rm * 2 * (1 / d * free_volume_ub / (math.pi ** (d / 2) / math.gamma(d / 2 + 1)) * math.log(N) / N) ** (1 / d)
+    ctx = P.ctx
+    P.CC._bind(ctx, P.SS)
+    gkind, gpar = P.goal.kind, P.goal.params()
+    if connections == "K":
+        res = ctx.knn_prmstar(k, gkind, gpar, init_idx=init_idx, checkpts=checkpts)
+    else:
+        res = ctx.prmstar(r, gkind, gpar, init_idx=init_idx, checkpts=checkpts)
+    P.status = "solved" if res["status"] == 1 else "failed"
+    path = res["path"]
+    meta = {"radius_multiplier": rm, "collision_checks": res["collision_checks"], "num_samples": N, "cost": res["cost"],
+            "cumcost": res["C"][path - 1], "planner": "prmstar", "solved": res["status"] == 1, "tree": res["A"], "path": path,
+            "cost_to_come": res["C"], "r": r if connections == "R" else r_given, "ms_graph": res["ms_graph"], "ms_sweep": res["ms_sweep"],
+            "ms_host_loop": res["ms_host_loop"]}
+    if connections == "K":
+        meta["k"] = k
+    P.solution = MPSolution(P.status, res["cost"], time.time() - t0, meta)
+    return P.status, P.solution.cost, P.solution.elapsed
