@@ -259,6 +259,59 @@ MPFMT_API int32_t mpfmt_prmstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int3
 MPFMT_API int32_t mpfmt_knn_prmstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
                           int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
 
+/* ---- adaptive shortcutting of solution paths (Hsu 2000): shortcut / cut_corner / adaptive_shortcut(!) of src/postprocessors.jl:6-50,
+ *      statement for statement, for ONE path on the host and for a BATCH of paths on the device (one wavefront per path; the tree paths
+ *      that mpfmt_prmstar / mpfmt_graph_sssp leave to every reached sample are the batch).
+ *      free(v, w) is the bit mpfmt_motions_free returns under the ctx's resident checker (N-D AABBs or 2-D SAT shapes), the first-point
+ *      bounds test of statespaces.jl:153-158 included.
+ *        shortcut(p)     : n == 2 -> p; free(p[1], p[n]) -> the two ends; else mid = ceil(n / 2) and
+ *                          shortcut(p[1:mid])[1:end-1] ++ shortcut(p[mid:n])                                    (postprocessors.jl:6-16)
+ *        cut_corner      : m1 = (v1 + v2) / 2, m2 = (v3 + v2) / 2; while !free(m1, m2): both <- their midpoints with v2 (fp64, one add and
+ *                          one halving per coordinate, unfused); the result is the FIRST free level              (:18-26)
+ *        adaptive_shortcut(p, iterations): shortcut to a fixed point (equal length = equal path: shortcut only removes states), then
+ *                          `iterations` times: every interior vertex becomes its two cut points, shortcut to a fixed point   (:28-39)
+ *        cumcost         = cumsum([0; norm.(diff(path))]), norm = sqrt of the left-to-right fold of squares (the graph costs' canon),
+ *                          summed left to right.
+ *      Two guards the reference lacks, identical on host and device:
+ *        max_states : an expansion that would make the working path longer than max_states (2 n - 2 > max_states) stops the path: it
+ *                     returns as it stood after the last completed iteration, status TRUNCATED.
+ *        stuck      : a halving that changes neither m1 nor m2 while the segment is not free (an interior vertex inside an obstacle) would
+ *                     loop forever: the path returns as it stood after the last completed iteration, status STUCK.  Corners are cut in
+ *                     order, so the counts cover the corners before the stuck one, its own tests, and nothing after it.
+ *      info: iterations_done = completed iterations; max_working_len = longest working path (the input and every completed expansion);
+ *      max_halvings = most halvings of one cut_corner loop; collision_checks = the tests the SEQUENTIAL loop asks for whose first point
+ *      lies inside the state bounds (what P.CC.count gains: boxesND.jl:26 behind statespaces.jl:155) -- a function of the resolved
+ *      recursion, not of scheduling; tests_evaluated = tests actually run (the device tests the whole split tree and blocks of
+ *      cut_corner levels speculatively; on the host: every test asked).
+ *      Paths: d x n column-major; a batch is the concatenation with offsets[B + 1] (0-based state offsets, offsets[0] = 0).  out_P /
+ *      cumcost have room for out_cap states (sum of n_out > out_cap: MPFMT_ERR_CAPACITY, info and out_offsets are still written; B *
+ *      max_states always suffices); out_offsets[B + 1] as offsets.
+ *      MPFMT_ERR_ARG: a path of fewer than 2 states, a non-finite coordinate, iterations < 0, max_states below a path's length (or above
+ *      2^20); MPFMT_ERR_STATE: no resident checker, a sharded ctx.  A refused call leaves the ctx as it was.  A path of 2 states comes
+ *      back unchanged with 0 checks.  Timer "shortcut_batch"; stats "shortcut_tests_evaluated", "shortcut_checks" (last batch).
+ *      mpfmt_host_adaptive_shortcut: one path against the AABB checker given as arrays (lohi (2 d) x M as mpfmt_upload_boxes, ss_lo /
+ *      ss_hi or both NULL); no ctx, no device: the CPU baseline and the checker of the device result (bit-equal). */
+#define MPFMT_SHORTCUT_DONE      0
+#define MPFMT_SHORTCUT_TRUNCATED 1
+#define MPFMT_SHORTCUT_STUCK     2
+typedef struct {
+    int32_t status;            /* MPFMT_SHORTCUT_DONE / _TRUNCATED / _STUCK */
+    int32_t iterations_done;
+    int64_t n_out;             /* states of the returned path */
+    int64_t max_working_len;
+    int64_t max_halvings;
+    int64_t collision_checks;
+    int64_t tests_evaluated;
+} mpfmt_shortcut_info;
+MPFMT_API int32_t mpfmt_host_adaptive_shortcut(const double* P, int64_t n, int32_t d, const double* lohi, int32_t M, const double* ss_lo,
+                                     const double* ss_hi, int32_t iterations, int64_t max_states, double* out_P, int64_t out_cap,
+                                     double* cumcost, mpfmt_shortcut_info* info);
+MPFMT_API int32_t mpfmt_adaptive_shortcut_batch(mpfmt_ctx* ctx, const double* P, const int64_t* offsets, int64_t B, int32_t iterations,
+                                      int64_t max_states, double* out_P, int64_t* out_offsets, int64_t out_cap, double* cumcost,
+                                      mpfmt_shortcut_info* info);
+MPFMT_API int32_t mpfmt_adaptive_shortcut(mpfmt_ctx* ctx, const double* P, int64_t n, int32_t iterations, int64_t max_states, double* out_P,
+                                int64_t out_cap, double* cumcost, mpfmt_shortcut_info* info);
+
 /* ---- Monte-Carlo collision probability of candidate edges (BASELINE.json configs[4]).  The reference
  *      has no implementation (README.md:9-10 cites the papers only); the workload is the one SURVEY 8d defines: per edge
  *      (src[e] -> dst[e], 1-based sample indices) `rollouts` perturbed copies of the 2-point trajectory, each put through

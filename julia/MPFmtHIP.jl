@@ -209,6 +209,31 @@ function hip_graph_sssp(DS::HIPDistanceDS, N::Int, sources::Vector{Int}; checkpt
     C, A, info
 end
 
+# ---- post-processing: adaptive_shortcut!(P, iterations) (src/postprocessors.jl:41-50) on the device; the checker of P.V.DS.ctx is the
+#      one the last upload bound (hip_bind! / the planner calls).  max_states bounds the working path (include/mpfmt.h).
+const sym_adaptive_shortcut = :mpfmt_adaptive_shortcut
+immutable ShortcutInfo
+    status::Int32; iterations_done::Int32; n_out::Int64; max_working_len::Int64; max_halvings::Int64; collision_checks::Int64
+    tests_evaluated::Int64
+end
+function hip_adaptive_shortcut!(P::MPProblem, iterations::Int = 10; max_states::Int = 256)
+    P.status == :solved || error("Cannot post-process unsolved problem! (adaptive-shortcut)")
+    isa(P.SS.dist, Euclidean) || error("Adaptive-shortcut requires Euclidean SS")
+    DS = P.V.DS; S = P.solution
+    path = P.V.V[S.metadata["path"]]                       # Vector{SVector{d,Float64}} = d x n column-major in memory
+    d = length(path[1])
+    out = Matrix{Float64}(d, max_states); cum = Vector{Float64}(max_states); info = Ref{ShortcutInfo}()
+    chk(DS.ctx, ccall((sym_adaptive_shortcut, libmpfmt), Int32,
+                      (Ptr{Void}, Ptr{Float64}, Int64, Int32, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{ShortcutInfo}),
+                      DS.ctx, path, length(path), iterations, max_states, out, max_states, cum, info))
+    n = info[].n_out
+    P.CC.count += info[].collision_checks
+    S.metadata["smoothed_path"] = [typeof(path[1])(out[:, i]) for i in 1:n]
+    S.metadata["smoothed_cumcost"] = cum[1:n]
+    S.metadata["smoothed_cost"] = cum[n]
+    cum[n]
+end
+
 # ---- multi-GPU: ONE Julia thread, G ctxs (SURVEY 8e); the RCCL exchange lives behind the ABI ------------------------
 function hip_comm_create!(ctxs::Vector{Ptr{Void}})
     id = Vector{UInt8}(128)

@@ -45,6 +45,12 @@ class SsspInfo(C.Structure):
     _fields_ = [("reached", C.c_int64), ("rounds", C.c_int64), ("relaxations", C.c_int64), ("ms_device", C.c_double)]
 
 
+class ShortcutInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations_done", C.c_int32), ("n_out", C.c_int64), ("max_working_len", C.c_int64),
+                ("max_halvings", C.c_int64), ("collision_checks", C.c_int64), ("tests_evaluated", C.c_int64)]
+
+
+SHORTCUT_DONE, SHORTCUT_TRUNCATED, SHORTCUT_STUCK = 0, 1, 2
 WF_SINGLE, WF_EAGER, WF_LAZY = 1, 2, 4
 COMM_ID_BYTES = 128
 
@@ -86,6 +92,11 @@ SYMBOLS = [
                                   C.POINTER(FmtResult)]),
     ("mpfmt_knn_prmstar", C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_d_p, c_i64_p, c_d_p, c_i64_p,
                                       C.POINTER(FmtResult)]),
+    ("mpfmt_host_adaptive_shortcut", C.c_int32, [c_d_p, C.c_int64, C.c_int32, c_d_p, C.c_int32, c_d_p, c_d_p, C.c_int32, C.c_int64, c_d_p, C.c_int64,
+                                                 c_d_p, C.POINTER(ShortcutInfo)]),
+    ("mpfmt_adaptive_shortcut_batch", C.c_int32, [C.c_void_p, c_d_p, c_i64_p, C.c_int64, C.c_int32, C.c_int64, c_d_p, c_i64_p, C.c_int64, c_d_p,
+                                                  C.POINTER(ShortcutInfo)]),
+    ("mpfmt_adaptive_shortcut", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, C.c_int32, C.c_int64, c_d_p, C.c_int64, c_d_p, C.POINTER(ShortcutInfo)]),
     ("mpfmt_mc_edges_collision", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, c_i64_p]),
     ("mpfmt_mc_edges_collision_is", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("mpfmt_mc_edges_collision_ais", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, C.POINTER(C.c_uint64),
@@ -289,6 +300,32 @@ def host_graph_sssp(colptr0, rowval0, nzval, efree, F=None, source=1, want_paren
     if rc != 0:
         raise MPFMTError(rc, "mpfmt_host_graph_sssp rejected its arguments")
     return Cc[:N], (None if A is None else A[:N])
+
+
+def _shortcut_info(i):
+    return dict(status=int(i.status), iterations_done=int(i.iterations_done), n_out=int(i.n_out), max_working_len=int(i.max_working_len),
+                max_halvings=int(i.max_halvings), collision_checks=int(i.collision_checks), tests_evaluated=int(i.tests_evaluated))
+
+
+def host_adaptive_shortcut(path, lohi, ss_lo=None, ss_hi=None, iterations=10, max_states=256):
+    """adaptive_shortcut (src/postprocessors.jl:28-39) of one path (n, d) against the AABB checker lohi (M, 2, d) on the host: no GPU
+    needed; the CPU baseline and the checker of Context.adaptive_shortcut (include/mpfmt.h, "adaptive shortcutting").
+    Returns (smoothed path (n_out, d), cumcost (n_out,), info dict)."""
+    P = np.ascontiguousarray(path, dtype=np.float64)
+    if P.ndim != 2:
+        raise ValueError("path must be (n, d)")
+    n, d = P.shape
+    lohi = np.ascontiguousarray(lohi, dtype=np.float64).reshape(-1, 2, d)
+    lo = None if ss_lo is None else np.ascontiguousarray(ss_lo, dtype=np.float64)
+    hi = None if ss_hi is None else np.ascontiguousarray(ss_hi, dtype=np.float64)
+    cap = max(int(max_states), n, 2)
+    out = np.empty((cap, d), dtype=np.float64); cc = np.empty(cap, dtype=np.float64)
+    info = ShortcutInfo()
+    rc = lib().mpfmt_host_adaptive_shortcut(_dp(P), n, d, _dp(lohi), lohi.shape[0], _dp(lo), _dp(hi), int(iterations), int(max_states), _dp(out), cap,
+                                            _dp(cc), C.byref(info))
+    if rc != 0:
+        raise MPFMTError(rc, "mpfmt_host_adaptive_shortcut rejected its arguments")
+    return out[:info.n_out].copy(), cc[:info.n_out].copy(), _shortcut_info(info)
 
 
 class Context:
@@ -799,6 +836,46 @@ class Context:
         nzval = np.ascontiguousarray(nzval, dtype=np.float64)
         self._chk(self._L.mpfmt_graph_import(self._h, float(r), _ip(colptr), _ip(rowval), _dp(nzval)))
         self.nnz = int(colptr[-1] - 1)
+
+    def adaptive_shortcut(self, paths, iterations=10, max_states=256):
+        """adaptive_shortcut (src/postprocessors.jl:28-39) of a batch of paths under the resident checker, one wavefront per path
+        (include/mpfmt.h, "adaptive shortcutting").  paths: a list of (n_i, d) arrays -> a list of (path, cumcost, info) triples; one
+        (n, d) array -> one triple."""
+        single = isinstance(paths, np.ndarray) and paths.ndim == 2
+        plist = [paths] if single else list(paths)
+        plist = [np.ascontiguousarray(p, dtype=np.float64) for p in plist]
+        for p in plist:
+            if p.ndim != 2:
+                raise ValueError("every path must be (n, d)")
+        B = len(plist)
+        d = plist[0].shape[1] if B else max(self.dw, 1)
+        for p in plist:
+            if p.shape[1] != d:
+                raise ValueError("paths of different dimensions")
+        off = np.zeros(B + 1, dtype=np.int64)
+        off[1:] = np.cumsum([p.shape[0] for p in plist])
+        P = np.ascontiguousarray(np.concatenate(plist, axis=0)) if B else np.zeros((1, d))
+        if B and self.dw and d != self.dw:
+            raise ValueError("paths have dimension %d, the checker's workspace %d" % (d, self.dw))
+        info = (ShortcutInfo * max(B, 1))()
+        out_off = np.zeros(B + 1, dtype=np.int64)
+        if single:
+            cap = max(int(max_states), 2)
+            out = np.empty((cap, d), dtype=np.float64); cc = np.empty(cap, dtype=np.float64)
+            self._chk(self._L.mpfmt_adaptive_shortcut(self._h, _dp(P), P.shape[0], int(iterations), int(max_states), _dp(out), cap, _dp(cc), info))
+            n = int(info[0].n_out)
+            return out[:n].copy(), cc[:n].copy(), _shortcut_info(info[0])
+        cap = max(int(off[-1]), 1)                       # most outputs are shorter than their inputs; grow once when they are not
+        for _ in range(2):
+            out = np.empty((cap, d), dtype=np.float64); cc = np.empty(cap, dtype=np.float64)
+            rc = self._L.mpfmt_adaptive_shortcut_batch(self._h, _dp(P), _ip(off), B, int(iterations), int(max_states), _dp(out), _ip(out_off), cap,
+                                                       _dp(cc), info)
+            if rc == ERR_CAPACITY and int(out_off[-1]) > cap:
+                cap = int(out_off[-1])
+                continue
+            self._chk(rc)
+            break
+        return [(out[out_off[b]:out_off[b + 1]].copy(), cc[out_off[b]:out_off[b + 1]].copy(), _shortcut_info(info[b])) for b in range(B)]
 
     def path_free(self, P):
         """is_free_path(p, CC, SS) for the states P (n, d): (free, per-segment bits)."""

@@ -1340,6 +1340,46 @@ int32_t mpfmt_graph_sssp(mpfmt_ctx* ctx, const int64_t* sources, int64_t nsrc, i
     return MPFMT_OK;
 }
 
+// ---- adaptive shortcutting of solution paths (kernels_shortcut.hip; host reference: mpfmt_host_adaptive_shortcut) ------------------------
+
+int32_t mpfmt_adaptive_shortcut_batch(mpfmt_ctx* ctx, const double* P, const int64_t* offsets, int64_t B, int32_t iterations, int64_t max_states,
+                                      double* out_P, int64_t* out_offsets, int64_t out_cap, double* cumcost, mpfmt_shortcut_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (B < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "adaptive_shortcut: B < 0");
+    if (!offsets || !out_offsets) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "adaptive_shortcut: offsets / out_offsets is NULL");
+    if (B > 0 && (!P || !out_P || !cumcost || !info)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "adaptive_shortcut: P / out_P / cumcost / info is NULL");
+    if (iterations < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "adaptive_shortcut: iterations < 0");
+    if (max_states < 2 || max_states > (1 << 20)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "adaptive_shortcut: max_states must lie in [2, 2^20]");
+    if (out_cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "adaptive_shortcut: out_cap < 0");
+    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "adaptive_shortcut runs on an unsharded ctx");
+    if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes / mpfmt_upload_shapes2d)");
+    const int d = ctx->dw;
+    if (offsets[0] != 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "adaptive_shortcut: offsets[0] must be 0");
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t n = offsets[b + 1] - offsets[b];
+        if (n < 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "adaptive_shortcut: path %lld has %lld states (a path has at least 2)", (long long)(b + 1), (long long)n);
+        if (n > max_states) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "adaptive_shortcut: path %lld has %lld states > max_states = %lld", (long long)(b + 1), (long long)n, (long long)max_states);
+    }
+    const int64_t total = offsets[B];
+    for (int64_t i = 0; i < total * d; ++i)
+        if (!std::isfinite(P[i])) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "adaptive_shortcut: non-finite coordinate in state %lld", (long long)(i / d + 1));
+    out_offsets[0] = 0;
+    if (B == 0) return MPFMT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return mpfmt_shortcut_batch_device(ctx, P, offsets, B, iterations, max_states, out_P, out_offsets, out_cap, cumcost, info);
+}
+
+int32_t mpfmt_adaptive_shortcut(mpfmt_ctx* ctx, const double* P, int64_t n, int32_t iterations, int64_t max_states, double* out_P, int64_t out_cap,
+                                double* cumcost, mpfmt_shortcut_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (n < 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "adaptive_shortcut: a path has at least 2 states");
+    const int64_t offsets[2] = {0, n};
+    int64_t out_offsets[2] = {0, 0};
+    return mpfmt_adaptive_shortcut_batch(ctx, P, offsets, 1, iterations, max_states, out_P, out_offsets, out_cap, cumcost, info);
+}
+
 // graph + mask (reused when resident), checkpts bitmap, field from init_idx, goal extraction; k > 0: the k-nearest graph
 static int32_t prmstar_impl(mpfmt_ctx* ctx, double r, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
                             int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
@@ -1922,6 +1962,8 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "sssp_rounds") == 0) { *value = ctx->sssp_rounds; return MPFMT_OK; }
     if (strcmp(name, "sssp_relaxations") == 0) { *value = ctx->sssp_relax; return MPFMT_OK; }
     if (strcmp(name, "sssp_reached") == 0) { *value = ctx->sssp_reached; return MPFMT_OK; }
+    if (strcmp(name, "shortcut_tests_evaluated") == 0) { *value = ctx->shortcut_tests; return MPFMT_OK; }
+    if (strcmp(name, "shortcut_checks") == 0) { *value = ctx->shortcut_checks; return MPFMT_OK; }
     if (strcmp(name, "survivors") == 0) { *value = ctx->survivors; return MPFMT_OK; }
     if (strcmp(name, "pairs_tested") == 0) { *value = ctx->pairs_tested; return MPFMT_OK; }
     if (strcmp(name, "nnz") == 0) { *value = ctx->nnz; return MPFMT_OK; }

@@ -359,3 +359,142 @@ int64_t mpfmt_validate_csc(int64_t N, const int64_t* colptr, const int64_t* rowv
         }
     return 0;
 }
+
+// ---- adaptive shortcutting of one path (src/postprocessors.jl:6-39) against the AABB checker: the CPU baseline and the checker of
+// mpfmt_adaptive_shortcut_batch (kernels_shortcut.hip).  The recursion is the reference's, on index ranges of the working path instead
+// of copies; the scalar predicates restate boxesND.jl:42-56 in the operation order of sweep_predicates.h.
+namespace {
+
+struct ShortcutWorld {
+    int d; const double* lohi; int M; const double* ss_lo; const double* ss_hi;
+    int64_t checks = 0, tests = 0;
+
+    // free(v, w) = in_state_space(v) && is_free_motion(v, w, boxes) (statespaces.jl:153-158); the checker -- and its count, boxesND.jl:26
+    // -- is reached only when the first point lies inside the bounds
+    bool free(const double* v, const double* w)
+    {
+        ++tests;
+        if (ss_lo) {
+            bool in = true;
+            for (int i = 0; i < d; ++i) in = in && (ss_lo[i] <= v[i]) && (v[i] <= ss_hi[i]);
+            if (!in) return false;
+        }
+        ++checks;
+        double l[MPFMT_MAX_DIM], h[MPFMT_MAX_DIM], v_to_w[MPFMT_MAX_DIM];
+        for (int i = 0; i < d; ++i) {
+            l[i] = (w[i] < v[i]) ? w[i] : v[i];                                  // map(min, v, w)
+            h[i] = (v[i] < w[i]) ? w[i] : v[i];                                  // map(max, v, w)
+            v_to_w[i] = w[i] - v[i];
+        }
+        for (int k = 0; k < M; ++k) {
+            const double* lo = lohi + (size_t)k * 2 * d;
+            const double* hi = lo + d;
+            bool sep = false;                                                    // boxesND.jl:44-45
+            for (int i = 0; i < d; ++i) sep = sep || (hi[i] < l[i]) || (lo[i] > h[i]);
+            if (sep) continue;
+            for (int i = 0; i < d; ++i) {                                        // boxesND.jl:46-51
+                const double corner = (v[i] < lo[i]) ? lo[i] : hi[i];            // blend(v .< lo, lo, hi)
+                const double lambda = (corner - v[i]) / v_to_w[i];               // IEEE: may be +-Inf / NaN
+                bool all = true;
+                for (int j = 0; j < d; ++j) {
+                    if (j == i) continue;
+                    const double prod = v_to_w[j] * lambda;
+                    const double x = v[j] + prod;                                // unfused
+                    all = all && (lo[j] <= x) && (x <= hi[j]);
+                }
+                if (all) return false;
+            }
+        }
+        return true;
+    }
+
+    // shortcut(path[lo..hi]) (postprocessors.jl:6-16): appends the kept states after path[lo] to `keep`
+    void shortcut(const std::vector<double>& p, int64_t lo, int64_t hi, std::vector<int64_t>& keep)
+    {
+        const int64_t N = hi - lo + 1;
+        if (N == 2) { keep.push_back(hi); return; }
+        if (free(&p[(size_t)lo * d], &p[(size_t)hi * d])) { keep.push_back(hi); return; }
+        const int64_t mid = lo + (N + 1) / 2 - 1;                                // ceil(Int, N/2), 1-based inside the range
+        shortcut(p, lo, mid, keep);
+        shortcut(p, mid, hi, keep);
+    }
+
+    // `while (short_path = shortcut(path, CC)) != path` (:29-31, :34-36)
+    void shortcut_fixed_point(std::vector<double>& p)
+    {
+        std::vector<int64_t> keep;
+        std::vector<double> q;
+        for (;;) {
+            const int64_t n = (int64_t)(p.size() / d);
+            keep.clear();
+            keep.push_back(0);
+            shortcut(p, 0, n - 1, keep);
+            if ((int64_t)keep.size() == n) return;
+            q.resize(keep.size() * d);
+            for (size_t a = 0; a < keep.size(); ++a) memcpy(&q[a * d], &p[(size_t)keep[a] * d], sizeof(double) * d);
+            p.swap(q);
+        }
+    }
+};
+
+}  // namespace
+
+int32_t mpfmt_host_adaptive_shortcut(const double* P, int64_t n, int32_t d, const double* lohi, int32_t M, const double* ss_lo,
+                                     const double* ss_hi, int32_t iterations, int64_t max_states, double* out_P, int64_t out_cap,
+                                     double* cumcost, mpfmt_shortcut_info* info)
+{
+    if (!P || !out_P || !cumcost || !info || (M > 0 && !lohi)) return MPFMT_ERR_ARG;
+    if (n < 2 || d < 1 || d > MPFMT_MAX_DIM || M < 0 || iterations < 0 || max_states < n || max_states > (1 << 20)) return MPFMT_ERR_ARG;
+    if ((ss_lo == nullptr) != (ss_hi == nullptr)) return MPFMT_ERR_ARG;
+    for (int64_t i = 0; i < n * d; ++i) if (!std::isfinite(P[i])) return MPFMT_ERR_ARG;
+    ShortcutWorld W{d, lohi, M, ss_lo, ss_hi};
+    std::vector<double> path(P, P + (size_t)n * d), next;
+    memset(info, 0, sizeof *info);
+    info->max_working_len = n;
+    W.shortcut_fixed_point(path);
+    double a[MPFMT_MAX_DIM], b[MPFMT_MAX_DIM], na[MPFMT_MAX_DIM], nb[MPFMT_MAX_DIM];
+    for (int32_t it = 0; it < iterations; ++it) {
+        const int64_t m = (int64_t)(path.size() / d);
+        if (2 * m - 2 > max_states) { info->status = MPFMT_SHORTCUT_TRUNCATED; break; }
+        next.assign(path.begin(), path.begin() + d);                             // path[1:1]
+        bool stuck = false;
+        for (int64_t j = 1; j + 1 < m && !stuck; ++j) {                          // cut_corner(path[j-1:j+1]..., CC)[2:3]
+            const double *v1 = &path[(size_t)(j - 1) * d], *v2 = &path[(size_t)j * d], *v3 = &path[(size_t)(j + 1) * d];
+            for (int i = 0; i < d; ++i) { const double s = v1[i] + v2[i]; a[i] = s / 2; const double t = v3[i] + v2[i]; b[i] = t / 2; }
+            int64_t halvings = 0;
+            while (!W.free(a, b)) {
+                bool same = true;
+                for (int i = 0; i < d; ++i) {
+                    const double s = a[i] + v2[i]; na[i] = s / 2;
+                    const double t = b[i] + v2[i]; nb[i] = t / 2;
+                    same = same && na[i] == a[i] && nb[i] == b[i];
+                }
+                ++halvings;
+                if (same) { stuck = true; break; }
+                memcpy(a, na, sizeof(double) * d); memcpy(b, nb, sizeof(double) * d);
+            }
+            if (halvings > info->max_halvings) info->max_halvings = halvings;
+            next.insert(next.end(), a, a + d);
+            next.insert(next.end(), b, b + d);
+        }
+        if (stuck) { info->status = MPFMT_SHORTCUT_STUCK; break; }
+        next.insert(next.end(), path.end() - d, path.end());                     // path[end:end]
+        path.swap(next);
+        if ((int64_t)(path.size() / d) > info->max_working_len) info->max_working_len = (int64_t)(path.size() / d);
+        W.shortcut_fixed_point(path);
+        ++info->iterations_done;
+    }
+    const int64_t n_out = (int64_t)(path.size() / d);
+    info->n_out = n_out;
+    info->collision_checks = W.checks;
+    info->tests_evaluated = W.tests;
+    if (n_out > out_cap) return MPFMT_ERR_CAPACITY;
+    memcpy(out_P, path.data(), sizeof(double) * path.size());
+    cumcost[0] = 0.0;
+    for (int64_t i = 1; i < n_out; ++i) {                                        // cumsum([0; map(norm, diff(path))])
+        double s = 0.0;
+        for (int c = 0; c < d; ++c) { const double t = path[(size_t)i * d + c] - path[(size_t)(i - 1) * d + c]; const double tt = t * t; s = (c == 0) ? tt : s + tt; }
+        cumcost[i] = cumcost[i - 1] + std::sqrt(s);
+    }
+    return MPFMT_OK;
+}

@@ -328,6 +328,9 @@ struct mpfmt_ctx {
     uint64_t* sssp_F = nullptr;          // [ceil(N/64)] checkpts bitmap of the call
     hipEvent_t sssp_ev[2] = {nullptr, nullptr};
     int64_t sssp_rounds = 0, sssp_relax = 0, sssp_reached = 0;      // stats of the last source
+
+    // ---- adaptive shortcutting (kernels_shortcut.hip): stats of the last batch ----
+    int64_t shortcut_tests = 0, shortcut_checks = 0;
 };
 
 // error helpers ---------------------------------------------------------------------------------
@@ -453,6 +456,11 @@ void mpfmt_wf_info_now(mpfmt_ctx* ctx, mpfmt_wf_info* info);
 // nullptr) receive the field; the labels and parents also stay in ctx->sssp_C / sssp_A
 int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, double* C_host, int64_t* A_host, mpfmt_sssp_info* info);
 void mpfmt_sssp_free(mpfmt_ctx* ctx);
+
+// kernels_shortcut.hip -----------------------------------------------------------------------------
+// the batch on the device; arguments already validated (mpfmt_adaptive_shortcut_batch, mpfmt_capi.hip)
+int32_t mpfmt_shortcut_batch_device(mpfmt_ctx* ctx, const double* P, const int64_t* offsets, int64_t B, int32_t iterations, int64_t max_states,
+                                    double* out_P, int64_t* out_offsets, int64_t out_cap, double* cumcost, mpfmt_shortcut_info* info);
 
 // kernels_expand.hip ----------------------------------------------------------------------------
 int32_t mpfmt_launch_expand(mpfmt_ctx* ctx, const uint64_t* d_W, const uint64_t* d_H, const uint64_t* d_F,

@@ -578,3 +578,67 @@ def prmstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_i
         meta["k"] = k
     P.solution = MPSolution(P.status, res["cost"], time.time() - t0, meta)
     return P.status, P.solution.cost, P.solution.elapsed
+
+
+# ---- post-processing (src/postprocessors.jl) ---------------------------------------------------------------------------------------
+def tree_paths(A, nodes, root=1):
+    """The tree paths root -> node (1-based sample indices) out of a parent array A (metadata["tree"]: A[i - 1] = parent of i, 0 =
+    none).  A node that does not hang on the root raises."""
+    out = []
+    for v in nodes:
+        p = [int(v)]
+        while p[-1] != root:
+            a = int(A[p[-1] - 1])
+            if a == 0 or len(p) > len(A):
+                raise ValueError("sample %d is not connected to sample %d in the tree" % (int(v), root))
+            p.append(a)
+        out.append(np.array(p[::-1], dtype=np.int64))
+    return out
+
+
+def _require_smoothable(P, what):
+    if P.status != "solved":
+        raise RuntimeError("Cannot post-process unsolved problem! (%s)" % what)                   # postprocessors.jl:42,55
+    if not isinstance(P.SS.dist, Euclidean):
+        raise RuntimeError("Adaptive-shortcut requires Euclidean SS")                              # postprocessors.jl:43
+
+
+def adaptive_shortcut_(P, iterations=10, max_states=256):
+    """adaptive_shortcut!(P, iterations) (postprocessors.jl:41-50) on the device: fills metadata["smoothed_path"] (n, d),
+    ["smoothed_cumcost"], ["smoothed_cost"], adds the checks to P.CC.count (boxesND.jl:26) and returns the smoothed cost.
+    metadata["smoothed_info"] holds the call's status and counts (include/mpfmt.h, "adaptive shortcutting")."""
+    _require_smoothable(P, "adaptive-shortcut")
+    S = P.solution
+    P.CC._bind(P.ctx, P.SS)
+    path, cum, info = P.ctx.adaptive_shortcut(np.ascontiguousarray(P.V.V[S.metadata["path"] - 1]), iterations, max_states)
+    P.CC.count += info["collision_checks"]
+    S.metadata["smoothed_path"] = path
+    S.metadata["smoothed_cumcost"] = cum
+    S.metadata["smoothed_cost"] = float(cum[-1])
+    S.metadata["smoothed_info"] = info
+    return float(cum[-1])
+
+
+def smooth_solution_(P):
+    """smooth_solution!(P) (postprocessors.jl:54-57): adaptive_shortcut! for a Euclidean space, nothing (None) for any other."""
+    if P.status != "solved":
+        raise RuntimeError("Cannot post-process unsolved problem! (adaptive-shortcut)")
+    if isinstance(P.SS.dist, Euclidean):
+        return adaptive_shortcut_(P)
+    return None
+
+
+def shortcut_paths_(P, nodes, iterations=10, max_states=256):
+    """The multi-query use after prmstar_ / fmtstar_: the tree paths from init to every sample of `nodes` (1-based; out of
+    metadata["tree"]) smoothed as ONE batch on the device.  Returns a list of (path, cumcost, info), one per node, and adds all
+    checks to P.CC.count.  A node the tree does not reach raises."""
+    if P.solution is None or "tree" not in P.solution.metadata:
+        raise RuntimeError("Cannot post-process unsolved problem! (adaptive-shortcut)")
+    if not isinstance(P.SS.dist, Euclidean):
+        raise RuntimeError("Adaptive-shortcut requires Euclidean SS")
+    root = int(P.solution.metadata["path"][0])
+    idx = tree_paths(P.solution.metadata["tree"], nodes, root)
+    P.CC._bind(P.ctx, P.SS)
+    out = P.ctx.adaptive_shortcut([np.ascontiguousarray(P.V.V[p - 1]) for p in idx], iterations, max_states)
+    P.CC.count += sum(i["collision_checks"] for _, _, i in out)
+    return out
