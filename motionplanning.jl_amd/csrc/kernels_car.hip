@@ -651,10 +651,10 @@ int32_t mpfmt_car_build(mpfmt_ctx* ctx, mpfmt_steer kind, double rt, double sp, 
     // (2) exact Dubins cost per candidate edge
     mpfmt_timed tm1(ctx);
     const int64_t cw = (cnnz + 63) / 64;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->valtmp, sizeof(double) * (size_t)std::max<int64_t>(cnnz, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->car_keep, sizeof(uint64_t) * (size_t)std::max<int64_t>(cw, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->deg, sizeof(int64_t) * (size_t)(N + 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->colptr, sizeof(int64_t) * (size_t)(N + 1)))) return rc;
+    if ((rc = ctx->valtmp.ensure(ctx, sizeof(double) * (size_t)std::max<int64_t>(cnnz, 1)))) return rc;
+    if ((rc = ctx->car_keep.ensure(ctx, sizeof(uint64_t) * (size_t)std::max<int64_t>(cw, 1)))) return rc;
+    if ((rc = ctx->deg.ensure(ctx, sizeof(int64_t) * (size_t)(N + 1)))) return rc;
+    if ((rc = ctx->colptr.ensure(ctx, sizeof(int64_t) * (size_t)(N + 1)))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->deg, 0, sizeof(int64_t) * (size_t)(N + 1), ctx->stream));
     ctx->deg_zero_valid = false;
     if (cnnz > 0) {
@@ -672,8 +672,8 @@ int32_t mpfmt_car_build(mpfmt_ctx* ctx, mpfmt_steer kind, double rt, double sp, 
     HIPCHK(ctx, hipMemcpyAsync(&nnz, ctx->colptr + N, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // (3) ordered compaction
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rowval, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->nzval, sizeof(double) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
+    if ((rc = ctx->rowval.ensure(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
+    if ((rc = ctx->nzval.ensure(ctx, sizeof(double) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
     if (cnnz > 0) {
         hipLaunchKernelGGL(k_car_compact, dim3((unsigned)std::min<int64_t>(N, 1 << 20)), dim3(64), 0, ctx->stream, ax->colptr, ax->rowval,
                            ctx->valtmp, ctx->car_keep, N, ctx->colptr, ctx->rowval, ctx->nzval);
@@ -700,8 +700,8 @@ int32_t mpfmt_car_sweep(mpfmt_ctx* ctx)
     if (ctx->ss.has && ctx->ss.d != 3) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "state-space bounds must have 3 dims for SE2 states");
     int32_t rc;
     const int64_t nnz = ctx->nnz, words = (nnz + 63) / 64;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->graph_free, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->steer_nseg, (size_t)std::max<int64_t>(nnz, 1)))) return rc;
+    if ((rc = ctx->graph_free.ensure(ctx, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1)))) return rc;
+    if ((rc = ctx->steer_nseg.ensure(ctx, (size_t)std::max<int64_t>(nnz, 1)))) return rc;
     mpfmt_timed tm2(ctx);
     HIPCHK(ctx, hipMemsetAsync(ctx->graph_free, 0, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1), ctx->stream));
     if (nnz > 0) {

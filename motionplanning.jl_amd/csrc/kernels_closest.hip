@@ -419,17 +419,6 @@ __global__ __launch_bounds__(CL_THREADS) void k_cl_fill(const double* __restrict
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
 namespace {
-struct Tmp {
-    std::vector<void*> p;
-    ~Tmp() { for (void* q : p) if (q) hipFree(q); }
-    template <class T> hipError_t get(T** out, size_t bytes)
-    {
-        void* q = nullptr;
-        const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-        if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
-        return e;
-    }
-};
 
 bool chol2(const double W[2][2], double U[2][2])
 {
@@ -570,7 +559,7 @@ int32_t mpfmt_closest(mpfmt_ctx* ctx, const double* P, int64_t n, const double* 
     if (!d2min || !vmin || !kmin) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output array");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int d = s.d;
-    Tmp tmp;
+    mpfmt_tmp tmp;
     double *dP, *d2all, *dd2, *dv; int64_t* dk; unsigned long long* dfail;
     HIPCHK(ctx, tmp.get(&dP, sizeof(double) * (size_t)n * d));
     HIPCHK(ctx, tmp.get(&d2all, sizeof(double) * (size_t)n * (s.M > 0 ? s.M : 1)));
@@ -616,7 +605,7 @@ int32_t mpfmt_closeR(mpfmt_ctx* ctx, const double* P, int64_t n, const double* W
     if (n == 0) return MPFMT_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int d = s.d;
-    Tmp tmp;
+    mpfmt_tmp tmp;
     double *dP, *d2all; int64_t *dcnt, *dptr; unsigned long long* dfail;
     HIPCHK(ctx, tmp.get(&dP, sizeof(double) * (size_t)n * d));
     HIPCHK(ctx, tmp.get(&d2all, sizeof(double) * (size_t)n * (s.M > 0 ? s.M : 1)));

@@ -405,10 +405,10 @@ int32_t mpfmt_di_count(mpfmt_ctx* ctx, double rho, double r)
     if (ntiles > 0) S = (int)std::min<int64_t>(64, std::max<int64_t>(1, ((mf ? 32768 : 8192) + ntiles - 1) / ntiles));
     S = (int)std::min<int64_t>(S, std::max<int64_t>(1, N / 64));
     ctx->di_S = S;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->slice_cnt, sizeof(int32_t) * (size_t)S * std::max<int64_t>(npad, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->deg, sizeof(int64_t) * (N + 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->colptr, sizeof(int64_t) * (N + 1)))) return rc;
-    if (!ctx->d_pairs) HIPCHK(ctx, hipMalloc((void**)&ctx->d_pairs, 514 * sizeof(unsigned long long)));     // (512 pair counters + the Euclidean build's longest-column word: one size everywhere)
+    if ((rc = ctx->slice_cnt.ensure(ctx, sizeof(int32_t) * (size_t)S * std::max<int64_t>(npad, 1)))) return rc;
+    if ((rc = ctx->deg.ensure(ctx, sizeof(int64_t) * (N + 1)))) return rc;
+    if ((rc = ctx->colptr.ensure(ctx, sizeof(int64_t) * (N + 1)))) return rc;
+    if ((rc = mpfmt_own_pairs(ctx))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_pairs, 0, 2 * sizeof(unsigned long long), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->deg, 0, sizeof(int64_t) * (N + 1), ctx->stream));
     ctx->deg_zero_valid = false;         // (this build writes every column's degree: a sharded r-disc step must not trust its own zeros any more)
@@ -458,10 +458,10 @@ int32_t mpfmt_di_count(mpfmt_ctx* ctx, double rho, double r)
         const double bytes = (double)capc * (double)ntiles * S * 64.0 * 20.0;
         if (bytes <= 64e9) {
             const size_t cap = (size_t)capc * (size_t)ntiles * S * 64;
-            if ((rc = mpfmt_ensure(ctx, (void**)&ctx->di_pool_i, sizeof(int32_t) * cap))) return rc;
-            if ((rc = mpfmt_ensure(ctx, (void**)&ctx->di_pool_c, sizeof(double) * cap))) return rc;
-            if ((rc = mpfmt_ensure(ctx, (void**)&ctx->di_pool_t, sizeof(double) * cap))) return rc;
-            if (!ctx->pool_flag) HIPCHK(ctx, hipMalloc((void**)&ctx->pool_flag, sizeof(int32_t)));
+            if ((rc = ctx->di_pool_i.ensure(ctx, sizeof(int32_t) * cap))) return rc;
+            if ((rc = ctx->di_pool_c.ensure(ctx, sizeof(double) * cap))) return rc;
+            if ((rc = ctx->di_pool_t.ensure(ctx, sizeof(double) * cap))) return rc;
+            if ((rc = mpfmt_own_pool_flag(ctx))) return rc;
             HIPCHK(ctx, hipMemsetAsync(ctx->pool_flag, 0, sizeof(int32_t), ctx->stream));
             a.pool_i = ctx->di_pool_i; a.pool_c = ctx->di_pool_c; a.pool_t = ctx->di_pool_t; a.pool_cap = capc; a.pool_flag = ctx->pool_flag;
             ctx->di_pool_cap = capc;
@@ -501,12 +501,12 @@ int32_t mpfmt_di_fill(mpfmt_ctx* ctx)
     const int64_t N = ctx->N, nnz = ctx->nnz;
     const int m = ctx->d / 2;
     int32_t rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rowtmp, sizeof(int32_t) * (size_t)nnz))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->valtmp, sizeof(double) * (size_t)nnz))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->tvaltmp, sizeof(double) * (size_t)nnz))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rowval, sizeof(int32_t) * (size_t)nnz))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->nzval, sizeof(double) * (size_t)nnz))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->tval, sizeof(double) * (size_t)nnz))) return rc;
+    if ((rc = ctx->rowtmp.ensure(ctx, sizeof(int32_t) * (size_t)nnz))) return rc;
+    if ((rc = ctx->valtmp.ensure(ctx, sizeof(double) * (size_t)nnz))) return rc;
+    if ((rc = ctx->tvaltmp.ensure(ctx, sizeof(double) * (size_t)nnz))) return rc;
+    if ((rc = ctx->rowval.ensure(ctx, sizeof(int32_t) * (size_t)nnz))) return rc;
+    if ((rc = ctx->nzval.ensure(ctx, sizeof(double) * (size_t)nnz))) return rc;
+    if ((rc = ctx->tval.ensure(ctx, sizeof(double) * (size_t)nnz))) return rc;
     const int64_t ntiles = (N + 63) / 64;
     di_args a;
     a.X = ctx->Xo; a.N = N; a.rho = ctx->di_rho; a.r = ctx->steer_r;
@@ -552,8 +552,8 @@ int32_t mpfmt_di_sweep(mpfmt_ctx* ctx)
     if (lds > 60 * 1024) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "double-integrator sweep supports at most %d boxes", (int)(60 * 1024 / (16 * m)));
     const int64_t nnz = ctx->nnz, words = (nnz + 63) / 64;
     int32_t rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->graph_free, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->steer_nseg, (size_t)std::max<int64_t>(nnz, 1)))) return rc;
+    if ((rc = ctx->graph_free.ensure(ctx, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1)))) return rc;
+    if ((rc = ctx->steer_nseg.ensure(ctx, (size_t)std::max<int64_t>(nnz, 1)))) return rc;
     if (nnz > 0) {
         mpfmt_timed tm3(ctx);
         const unsigned nb = (unsigned)((nnz + 255) / 256);

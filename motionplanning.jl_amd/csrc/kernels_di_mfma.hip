@@ -370,10 +370,10 @@ int32_t mpfmt_di_mf_build_operands(mpfmt_ctx* ctx, double sp, double sv, const d
     const int64_t N = ctx->N, npad = ((N + 63) / 64) * 64;
     int32_t rc;
     // opsT | opsS | the centre: one grow-only buffer
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->di_ops, 64 * (size_t)npad + 64))) return rc;
-    double* pcd = (double*)((char*)ctx->di_ops + 64 * (size_t)npad);
+    if ((rc = ctx->di_ops.ensure(ctx, 64 * (size_t)npad + 64))) return rc;
+    double* pcd = (double*)((char*)ctx->di_ops.get() + 64 * (size_t)npad);
     HIPCHK(ctx, hipMemcpyAsync(pcd, pc_host, sizeof(double) * 2, hipMemcpyHostToDevice, ctx->stream));
-    uint4* T = (uint4*)ctx->di_ops;
+    uint4* T = (uint4*)ctx->di_ops.get();
     uint4* S = T + 2 * npad;
     const int B = 256;
     if (m == 1) hipLaunchKernelGGL((k_di_make_ops<1>), dim3((unsigned)((npad + B - 1) / B)), dim3(B), 0, ctx->stream, ctx->Xo, N, npad, sp, sv, pcd, T, S);
@@ -389,7 +389,7 @@ int32_t mpfmt_di_mf_launch(mpfmt_ctx* ctx, const di_args& a, int mode, float neg
     dimf_args g;
     g.a = a;
     g.npad = a.ntiles * 64;
-    g.opsT = (const uint4*)ctx->di_ops;
+    g.opsT = (const uint4*)ctx->di_ops.get();
     g.opsS = g.opsT + 2 * g.npad;
     g.negT = negT;
 #define LAUNCH(MM, MODE) hipLaunchKernelGGL((k_di_pairs_mf<MM, MODE>), dim3(nblk), dim3(64), 0, ctx->stream, g)

@@ -300,11 +300,11 @@ int32_t mpfmt_knn_build(mpfmt_ctx* ctx, int64_t k)
     ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
     ctx->pool_valid = false; ctx->rowpos_valid = false; ctx->pend_valid = false; ctx->spec_ready = false; ctx->tptr_valid = false;
     ctx->knn_pairs = 0; ctx->knn_rounds = 0; ctx->knn_short = 0; ctx->knn_scan = 0;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->colptr, sizeof(int64_t) * (size_t)(N + 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rowval, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->nzval, sizeof(double) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
+    if ((rc = ctx->colptr.ensure(ctx, sizeof(int64_t) * (size_t)(N + 1)))) return rc;
+    if ((rc = ctx->rowval.ensure(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
+    if ((rc = ctx->nzval.ensure(ctx, sizeof(double) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
     const int64_t mwords = (nnz + 63) / 64;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->knn_mutual, sizeof(uint64_t) * (size_t)std::max<int64_t>(mwords, 1)))) return rc;
+    if ((rc = ctx->knn_mutual.ensure(ctx, sizeof(uint64_t) * (size_t)std::max<int64_t>(mwords, 1)))) return rc;
     hipLaunchKernelGGL(k_knn_colptr, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, ctx->stream, ctx->colptr, N, std::max<int64_t>(keff, 0));
     double longest = 0.0;
     if (nnz > 0) {
@@ -323,7 +323,7 @@ int32_t mpfmt_knn_build(mpfmt_ctx* ctx, int64_t k)
             mpfmt_timed tc(ctx);
             if ((rc = mpfmt_build_grid(ctx, std::isfinite(rho0) ? rho0 : 0.0, true))) return rc;
             const int64_t nst = (ctx->ntiles + KNN_ST - 1) / KNN_ST;
-            if ((rc = mpfmt_ensure(ctx, (void**)&ctx->knn_st, sizeof(double) * 2 * (size_t)nst * d))) return rc;
+            if ((rc = ctx->knn_st.ensure(ctx, sizeof(double) * 2 * (size_t)nst * d))) return rc;
             hipLaunchKernelGGL(k_knn_supertiles, dim3((unsigned)nst), dim3(64), 0, ctx->stream, (const double*)ctx->tile_lo, (const double*)ctx->tile_hi,
                                ctx->ntiles, d, ctx->knn_st, ctx->knn_st + nst * d);
             tc.end("knn_candidates");
@@ -332,10 +332,10 @@ int32_t mpfmt_knn_build(mpfmt_ctx* ctx, int64_t k)
         const int64_t nwords = (N + 63) / 64;
         const int64_t maxwg = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)8 * ctx->num_cus));
         const bool use_bitmap = keff > KNN_LDS_K;               // (columns of at most KNN_LDS_K entries are ordered in LDS)
-        if (use_bitmap && (rc = mpfmt_ensure(ctx, (void**)&ctx->knn_bitmap, sizeof(uint64_t) * (size_t)maxwg * (size_t)nwords))) return rc;
+        if (use_bitmap && (rc = ctx->knn_bitmap.ensure(ctx, sizeof(uint64_t) * (size_t)maxwg * (size_t)nwords))) return rc;
         // short lists A | B, then their counters and the two statistics words
-        if ((rc = mpfmt_ensure(ctx, (void**)&ctx->knn_lists, sizeof(int32_t) * 2 * (size_t)N + 64))) return rc;
-        int32_t* listA = (int32_t*)ctx->knn_lists;
+        if ((rc = ctx->knn_lists.ensure(ctx, sizeof(int32_t) * 2 * (size_t)N + 64))) return rc;
+        int32_t* listA = (int32_t*)ctx->knn_lists.get();
         int32_t* listB = listA + N;
         char* tail = (char*)(listB + N);
         tail += (8 - ((uintptr_t)tail & 7)) & 7;
@@ -347,7 +347,7 @@ int32_t mpfmt_knn_build(mpfmt_ctx* ctx, int64_t k)
         a.Xt = ctx->Xt; a.Xo = ctx->Xo; a.perm = ctx->perm; a.tile_lo = ctx->tile_lo; a.tile_hi = ctx->tile_hi;
         a.st_lo = ctx->knn_st; a.st_hi = ctx->knn_st + nst * d;
         a.N = N; a.ntiles = ctx->ntiles; a.nst = nst; a.d = d; a.keff = keff;
-        a.bitmap = use_bitmap ? (unsigned long long*)ctx->knn_bitmap : nullptr; a.nwords = nwords;
+        a.bitmap = use_bitmap ? (unsigned long long*)ctx->knn_bitmap.get() : nullptr; a.nwords = nwords;
         a.rowval = ctx->rowval; a.nzval = ctx->nzval; a.stats = stats;
         mpfmt_timed ts(ctx);
         const double radius[3] = {rho0, 2.0 * rho0, INFINITY};
@@ -382,7 +382,7 @@ int32_t mpfmt_knn_build(mpfmt_ctx* ctx, int64_t k)
         longest = std::sqrt(maxd2);
         mpfmt_timed tmu(ctx);
         hipLaunchKernelGGL(k_knn_mutual, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t*)ctx->rowval, keff, N, nnz,
-                           (unsigned long long*)ctx->knn_mutual);
+                           (unsigned long long*)ctx->knn_mutual.get());
         HIPCHK(ctx, hipGetLastError());
         tmu.end("knn_mutual");
     }

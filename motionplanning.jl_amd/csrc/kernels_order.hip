@@ -364,7 +364,7 @@ int32_t mpfmt_mask_preset(mpfmt_ctx* ctx, int64_t entries)
 {
     int32_t rc;
     const int64_t words = (entries + 63) / 64;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->graph_free, sizeof(uint64_t) * (size_t)(words + 1)))) return rc;
+    if ((rc = ctx->graph_free.ensure(ctx, sizeof(uint64_t) * (size_t)(words + 1)))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->graph_free, 0xFF, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1), ctx->stream));
     ctx->mask_preset_words = words;
     return MPFMT_OK;
@@ -382,16 +382,16 @@ int32_t mpfmt_order_logs(mpfmt_ctx* ctx, const int32_t* spec_fail, int64_t mask_
         // (sized with the slack a following speculative step asks for, so that it finds the mask in place)
         const int64_t words = (std::max<int64_t>(ctx->nnz, mask_entries) + 63) / 64;
         const int64_t words_alloc = (std::max<int64_t>((int64_t)((double)ctx->nnz * 1.02) + 4096, mask_entries) + 63) / 64 + 1;
-        if ((rc = mpfmt_ensure(ctx, (void**)&ctx->graph_free, sizeof(uint64_t) * (size_t)words_alloc))) return rc;
+        if ((rc = ctx->graph_free.ensure(ctx, sizeof(uint64_t) * (size_t)words_alloc))) return rc;
         // preset to ones (blocked entries are cleared); an empty graph keeps one zero word
         if (!(ctx->mask_preset_words == words && ctx->nnz > 0))
             HIPCHK(ctx, hipMemsetAsync(ctx->graph_free, ctx->nnz > 0 ? 0xFF : 0, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1), ctx->stream));
     }
     ctx->mask_preset_words = -1;
     if (ctx->nnz == 0 || nt <= 0) { if ((rc = mpfmt_side_join(ctx))) return rc; if (recbits) { ctx->graph_swept = true; ctx->sweep_in_order = true; } return MPFMT_OK; }
-    // option sweep_sorted: also keep every row's cell-sorted position, so the whole sweep can gather from Xs (see kernels_sweep.hip)
-    const bool want_rowpos = ctx->sweep_sorted && !pend && !recbits;
-    if (want_rowpos && (rc = mpfmt_ensure(ctx, (void**)&ctx->rowpos, sizeof(int32_t) * (size_t)std::max<int64_t>(std::max(ctx->nnz, ctx->nnz_cap), 1)))) return rc;
+    // also keep every row's cell-sorted position, so the whole sweep can gather from Xs (see kernels_sweep.hip)
+    const bool want_rowpos = !pend && !recbits;
+    if (want_rowpos && (rc = ctx->rowpos.ensure(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(std::max(ctx->nnz, ctx->nnz_cap), 1)))) return rc;
     const size_t lds = (size_t)ORD_STG * 12 + sizeof(ord_shared);
     // (the attribute belongs to the kernel ON A DEVICE: set per launch -- a cached flag would cover the first device of a process
     // that drives several, and be written by concurrent ctx threads)
@@ -413,8 +413,8 @@ int32_t mpfmt_order_logs(mpfmt_ctx* ctx, const int32_t* spec_fail, int64_t mask_
         // one segment of the item array per workgroup; workgroups take every nb-th quarter tile, so their shares are even: 1.5x the mean + 4096
         const int64_t entries = std::max<int64_t>(ctx->nnz, ctx->nnz_cap);
         ctx->pend_wcap = ctx->debug_small_lists ? 8 : entries * 3 / (2 * (int64_t)nb) + 4096;
-        if ((rc = mpfmt_ensure(ctx, (void**)&ctx->pend_items, sizeof(uint4) * (size_t)ctx->pend_wcap * nb))) return rc;
-        if ((rc = mpfmt_ensure(ctx, (void**)&ctx->pend_cnt, sizeof(int32_t) * (size_t)(nb + 1)))) return rc;
+        if ((rc = ctx->pend_items.ensure(ctx, sizeof(uint4) * (size_t)ctx->pend_wcap * nb))) return rc;
+        if ((rc = ctx->pend_cnt.ensure(ctx, sizeof(int32_t) * (size_t)(nb + 1)))) return rc;
         ctx->pend_over = ctx->pend_cnt + nb;
         HIPCHK(ctx, hipMemsetAsync(ctx->pend_over, 0, sizeof(int32_t), ctx->stream));
     }
@@ -424,8 +424,8 @@ int32_t mpfmt_order_logs(mpfmt_ctx* ctx, const int32_t* spec_fail, int64_t mask_
     a.rowval = ctx->rowval; a.nzval = ctx->nzval; a.rowpos = want_rowpos ? ctx->rowpos : nullptr;
     a.bucket_mul = ctx->N > 128 ? (uint32_t)((128ull << 32) / (uint64_t)ctx->N) : 0u;
     a.spec_fail = spec_fail;
-    a.mask = (unsigned long long*)ctx->graph_free; a.nnz_dev = ctx->colptr + ctx->N;
-    a.pend_items = pend ? (uint4*)ctx->pend_items : nullptr; a.pend_wcap = ctx->pend_wcap; a.pend_cnt = ctx->pend_cnt; a.pend_over = ctx->pend_over;
+    a.mask = (unsigned long long*)ctx->graph_free.get(); a.nnz_dev = ctx->colptr + ctx->N;
+    a.pend_items = pend ? (uint4*)ctx->pend_items.get() : nullptr; a.pend_wcap = ctx->pend_wcap; a.pend_cnt = ctx->pend_cnt; a.pend_over = ctx->pend_over;
     a.rec_bits = recbits ? 1 : 0;
     a.deg_clear = ctx->world > 1 ? ctx->deg : nullptr;
     a.qctr = draw ? ctx->ord_ctr : nullptr;

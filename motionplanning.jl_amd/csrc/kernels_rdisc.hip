@@ -429,7 +429,6 @@ __global__ __launch_bounds__(256) void k_build_tiles(const double* __restrict__ 
     for (int t = lane; t < 64 * d; t += 64) out[t] = rows[t];
 }
 
-static inline int32_t ensure(mpfmt_ctx* ctx, void** p, size_t bytes) { return mpfmt_ensure(ctx, p, bytes); }
 
 
 // shard boundaries as fractions of the cell-sorted order, at equal ESTIMATED WORK rather than equal sample counts: a column's work
@@ -562,27 +561,27 @@ int32_t mpfmt_build_grid(mpfmt_ctx* ctx, double r, bool whole)
     }
 
     int32_t rc;
-    if ((rc = ensure(ctx, (void**)&ctx->perm, sizeof(int32_t) * npad))) return rc;
-    if ((rc = ensure(ctx, (void**)&ctx->iperm, sizeof(int32_t) * N))) return rc;
-    if ((rc = ensure(ctx, (void**)&ctx->cellkey, sizeof(uint32_t) * N))) return rc;
+    if ((rc = ctx->perm.ensure(ctx, sizeof(int32_t) * npad))) return rc;
+    if ((rc = ctx->iperm.ensure(ctx, sizeof(int32_t) * N))) return rc;
+    if ((rc = ctx->cellkey.ensure(ctx, sizeof(uint32_t) * N))) return rc;
     const size_t arena_cells = sizeof(int32_t) * (size_t)(G.ncells + 2);
     const size_t arena_bytes = arena_cells + (size_t)std::max<int64_t>(ctx->ntiles, 1);
-    if ((rc = ensure(ctx, (void**)&ctx->idx_arena, arena_bytes))) return rc;
-    ctx->cellstart = (int32_t*)ctx->idx_arena;
+    if ((rc = ctx->idx_arena.ensure(ctx, arena_bytes))) return rc;
+    ctx->cellstart = (int32_t*)ctx->idx_arena.get();
     ctx->list_max = ctx->cellstart + (G.ncells + 1);
-    ctx->tileneed_buf = (uint8_t*)ctx->idx_arena + arena_cells;
-    if ((rc = ensure(ctx, (void**)&ctx->Xt, sizeof(double) * npad * d))) return rc;
-    if ((rc = ensure(ctx, (void**)&ctx->Xs, sizeof(double) * std::max<int64_t>(npad, 1) * d))) return rc;
-    if ((rc = ensure(ctx, (void**)&ctx->tile_lo, sizeof(double) * ctx->ntiles * d))) return rc;
-    if ((rc = ensure(ctx, (void**)&ctx->tile_hi, sizeof(double) * ctx->ntiles * d))) return rc;
-    if ((rc = ensure(ctx, (void**)&ctx->tile_sub, sizeof(double) * ctx->ntiles * 4 * d))) return rc;
-    if ((rc = ensure(ctx, (void**)&ctx->tile_sub32, sizeof(float) * ctx->ntiles * 4 * d))) return rc;
+    ctx->tileneed_buf = (uint8_t*)ctx->idx_arena.get() + arena_cells;
+    if ((rc = ctx->Xt.ensure(ctx, sizeof(double) * npad * d))) return rc;
+    if ((rc = ctx->Xs.ensure(ctx, sizeof(double) * std::max<int64_t>(npad, 1) * d))) return rc;
+    if ((rc = ctx->tile_lo.ensure(ctx, sizeof(double) * ctx->ntiles * d))) return rc;
+    if ((rc = ctx->tile_hi.ensure(ctx, sizeof(double) * ctx->ntiles * d))) return rc;
+    if ((rc = ctx->tile_sub.ensure(ctx, sizeof(double) * ctx->ntiles * 4 * d))) return rc;
+    if ((rc = ctx->tile_sub32.ensure(ctx, sizeof(float) * ctx->ntiles * 4 * d))) return rc;
 
     // the matrix-core pair kernel's operands are written by the tile pass when that kernel is going to run
     bool mf = false;
     float negT = 0.f;
     if (ctx->rdisc_path != 1 && (rc = mpfmt_mfma_prepare(ctx, r, &negT, &mf))) return rc;
-    if (mf && (rc = ensure(ctx, (void**)&ctx->ops, 32 * (size_t)std::max<int64_t>(npad, 1)))) return rc;
+    if (mf && (rc = ctx->ops.ensure(ctx, 32 * (size_t)std::max<int64_t>(npad, 1)))) return rc;
 
     // shard + halo index: the matrix-core path reads candidates only through its chunk lists, which the empty boxes of unbuilt tiles
     // keep them out of; the exact VALU kernel walks cell runs directly and needs every tile.  The halo search visits 3^(gridded
@@ -626,7 +625,7 @@ int32_t mpfmt_build_grid(mpfmt_ctx* ctx, double r, bool whole)
         int32_t* cnt = ctx->cellstart;
         if (cstride > 1) {
             const size_t need = sizeof(int32_t) * (size_t)(G.ncells + 2) * (size_t)cstride;
-            if ((rc = ensure(ctx, (void**)&ctx->cellcnt_pad, need))) return rc;
+            if ((rc = ctx->cellcnt_pad.ensure(ctx, need))) return rc;
             HIPCHK(ctx, hipMemsetAsync(ctx->cellcnt_pad, 0, need, ctx->stream));
             cnt = ctx->cellcnt_pad;
         }
@@ -998,21 +997,19 @@ int32_t mpfmt_rdisc_count_launch(mpfmt_ctx* ctx, double r, bool spec)
     const size_t za_need = ZA_BYTES + sizeof(int32_t) * (size_t)std::max<int64_t>(nt * 4, 1);
     bool counters_zeroed = false;
     auto zero_counters = [&]() -> int32_t {
-        if ((!ctx->zarena && !ctx->d_pairs && !ctx->pool_flag && !ctx->pair_cnt && !ctx->qlen) || (ctx->zarena && ctx->zarena_bytes < za_need)) {
-            if (ctx->zarena) HIPCHK(ctx, hipFree(ctx->zarena));
-            ctx->zarena = nullptr;
-            HIPCHK(ctx, hipMalloc((void**)&ctx->zarena, za_need));
-            ctx->zarena_bytes = za_need;
-            ctx->d_pairs = (unsigned long long*)((char*)ctx->zarena + ZA_PAIRS);
-            ctx->pool_flag = (int32_t*)((char*)ctx->zarena + ZA_FLAG);
-            ctx->pair_cnt = (int32_t*)((char*)ctx->zarena + ZA_PCNT);
-            ctx->qlen = (int32_t*)((char*)ctx->zarena + ZA_QLEN);
-            ctx->ord_ctr = (int32_t*)((char*)ctx->zarena + ZA_OCTR);
+        if ((!ctx->zarena && !ctx->d_pairs && !ctx->pool_flag && !ctx->pair_cnt && !ctx->qlen) || (ctx->zarena && ctx->zarena.bytes() < za_need)) {
+            if ((rc = ctx->zarena.ensure(ctx, za_need))) return rc;
+            char* za = (char*)ctx->zarena.get();
+            ctx->d_pairs = (unsigned long long*)(za + ZA_PAIRS);
+            ctx->pool_flag = (int32_t*)(za + ZA_FLAG);
+            ctx->pair_cnt = (int32_t*)(za + ZA_PCNT);
+            ctx->qlen = (int32_t*)(za + ZA_QLEN);
+            ctx->ord_ctr = (int32_t*)(za + ZA_OCTR);
         }
         if (ctx->zarena) {
             HIPCHK(ctx, hipMemsetAsync(ctx->zarena, 0, za_need, ctx->stream));
         } else {
-            if (!ctx->d_pairs) HIPCHK(ctx, hipMalloc((void**)&ctx->d_pairs, 514 * sizeof(unsigned long long)));
+            if ((rc = mpfmt_own_pairs(ctx))) return rc;
             HIPCHK(ctx, hipMemsetAsync(ctx->d_pairs, 0, 514 * sizeof(unsigned long long), ctx->stream));
         }
         counters_zeroed = true;
@@ -1062,7 +1059,7 @@ int32_t mpfmt_rdisc_count_launch(mpfmt_ctx* ctx, double r, bool spec)
             hipStream_t main_s;
             if ((rc = mpfmt_side_fork(ctx, &main_s))) return rc;
             // (an arena in place -- nothing is freed under the lists -- is cleared by the masks' kernel itself)
-            const bool arena = ctx->zarena && ctx->zarena_bytes >= za_need;
+            const bool arena = ctx->zarena && ctx->zarena.bytes() >= za_need;
             const int32_t rc2 = mpfmt_launch_sample_masks(ctx, r, arena ? ctx->zarena : nullptr, arena ? za_need : 0, &counters_zeroed);
             if ((rc = mpfmt_side_back(ctx, main_s)) || (rc = rc2)) return rc;
             ctx->masks_early = true;
@@ -1083,11 +1080,11 @@ int32_t mpfmt_rdisc_count_launch(mpfmt_ctx* ctx, double r, bool spec)
     if (!mf) half = false;
     ctx->S = S;
     const int64_t npad = ctx->ntiles * 64;
-    if ((rc = ensure(ctx, (void**)&ctx->slice_cnt, sizeof(int32_t) * (size_t)S * npad))) return rc;      // (per-slice counts: the two-pass forms)
-    { const int64_t* was = ctx->deg; if ((rc = ensure(ctx, (void**)&ctx->deg, sizeof(int64_t) * (N + 1)))) return rc; if (ctx->deg != was) ctx->deg_zero_valid = false; }
-    if ((rc = ensure(ctx, (void**)&ctx->colptr, sizeof(int64_t) * (N + 1)))) return rc;
-    if ((rc = ensure(ctx, (void**)&ctx->degs, sizeof(int64_t) * (npad + 1)))) return rc;
-    if ((rc = ensure(ctx, (void**)&ctx->tptr, sizeof(int64_t) * (npad + 1)))) return rc;
+    if ((rc = ctx->slice_cnt.ensure(ctx, sizeof(int32_t) * (size_t)S * npad))) return rc;      // (per-slice counts: the two-pass forms)
+    { const int64_t* was = ctx->deg; if ((rc = ctx->deg.ensure(ctx, sizeof(int64_t) * (N + 1)))) return rc; if (ctx->deg != was) ctx->deg_zero_valid = false; }
+    if ((rc = ctx->colptr.ensure(ctx, sizeof(int64_t) * (N + 1)))) return rc;
+    if ((rc = ctx->degs.ensure(ctx, sizeof(int64_t) * (npad + 1)))) return rc;
+    if ((rc = ctx->tptr.ensure(ctx, sizeof(int64_t) * (npad + 1)))) return rc;
     if (!counters_zeroed && (rc = zero_counters())) return rc;
     const bool sparse_deg = ctx->world > 1 || nt <= 0;         // (unsharded: the degree kernels write every entry, the scans' extra last ones too)
     if (sparse_deg) {
@@ -1130,11 +1127,12 @@ int32_t mpfmt_rdisc_count_launch(mpfmt_ctx* ctx, double r, bool spec)
         if ((double)qcap * (double)nt * 4.0 * 12.0 > 96e9) pool = false;      // cap the logs at 96 GB of the 288
         else {
             const size_t nq = (size_t)nt * 4;
-            if ((rc = ensure(ctx, (void**)&ctx->qkey, sizeof(uint32_t) * (size_t)qcap * nq))) return rc;
-            if ((rc = ensure(ctx, (void**)&ctx->qd2, sizeof(double) * (size_t)qcap * nq))) return rc;
+            if ((rc = ctx->qkey.ensure(ctx, sizeof(uint32_t) * (size_t)qcap * nq))) return rc;
+            if ((rc = ctx->qd2.ensure(ctx, sizeof(double) * (size_t)qcap * nq))) return rc;
             if (!ctx->zarena) {                                    // (a ctx with separately allocated counters: their own fills)
-                if ((rc = ensure(ctx, (void**)&ctx->qlen, sizeof(int32_t) * nq))) return rc;
-                if (!ctx->pool_flag) HIPCHK(ctx, hipMalloc((void**)&ctx->pool_flag, sizeof(int32_t)));
+                if ((rc = ctx->qlen_own.ensure(ctx, sizeof(int32_t) * nq))) return rc;
+                ctx->qlen = ctx->qlen_own;
+                if ((rc = mpfmt_own_pool_flag(ctx))) return rc;
                 HIPCHK(ctx, hipMemsetAsync(ctx->pool_flag, 0, sizeof(int32_t), ctx->stream));
                 HIPCHK(ctx, hipMemsetAsync(ctx->qlen, 0, sizeof(int32_t) * nq, ctx->stream));
             }
@@ -1182,9 +1180,10 @@ int32_t mpfmt_rdisc_count_launch(mpfmt_ctx* ctx, double r, bool spec)
         } else units = 4.0;
         units = std::min(4.0, units * 1.5 + 0.25);
         ctx->pair_icap = ctx->debug_small_lists ? 8 : (int64_t)(std::min(6.0, units * (double)ctx->pair_slack) * pairs_est / 1024.0) + 4096;      // (option debug_small_lists: the overflow path, for the tests)
-        if ((rc = ensure(ctx, (void**)&ctx->pair_items, 16 * (size_t)ctx->pair_icap * 1024))) return rc;
+        if ((rc = ctx->pair_items.ensure(ctx, 16 * (size_t)ctx->pair_icap * 1024))) return rc;
         if (!ctx->zarena) {
-            if ((rc = ensure(ctx, (void**)&ctx->pair_cnt, sizeof(int32_t) * (1024 + 1)))) return rc;
+            if ((rc = ctx->pair_cnt_own.ensure(ctx, sizeof(int32_t) * (1024 + 1)))) return rc;
+            ctx->pair_cnt = ctx->pair_cnt_own;
             HIPCHK(ctx, hipMemsetAsync(ctx->pair_cnt, 0, sizeof(int32_t) * (1024 + 1), ctx->stream));
         }
         ctx->pair_over = ctx->pair_cnt + 1024;
@@ -1255,15 +1254,16 @@ int32_t mpfmt_rdisc_count_finish(mpfmt_ctx* ctx, double r, bool* spec_failed)
     const bool pool = ctx->cnt_pool;
     const int64_t nt = ctx->tile_end - ctx->tile_begin;
     if (spec_failed) *spec_failed = false;
-    { int32_t rcj; if ((rcj = mpfmt_side_join(ctx))) return rcj; }
-    if (!ctx->rb_dev) HIPCHK(ctx, hipMalloc(&ctx->rb_dev, sizeof(count_readback)));
-    if (!ctx->rb_host) HIPCHK(ctx, hipHostMalloc(&ctx->rb_host, sizeof(count_readback), hipHostMallocDefault));
+    int32_t rc;
+    if ((rc = mpfmt_side_join(ctx))) return rc;
+    if ((rc = ctx->rb_dev.ensure(ctx, sizeof(count_readback)))) return rc;
+    if ((rc = ctx->rb_host.ensure(ctx, sizeof(count_readback)))) return rc;
     hipLaunchKernelGGL(k_count_readback, dim3(1), dim3(512), 0, ctx->stream, ctx->d_pairs, ctx->colptr + N, pool ? ctx->pool_flag : nullptr,
-                       (ctx->spec_lists && nt > 0) ? ctx->list_max : nullptr, (const int32_t*)(ctx->d_pairs + 512), (count_readback*)ctx->rb_dev,
+                       (ctx->spec_lists && nt > 0) ? ctx->list_max : nullptr, (const int32_t*)(ctx->d_pairs + 512), (count_readback*)ctx->rb_dev.get(),
                        ctx->sweep_in_order ? (const int32_t*)ctx->pair_over : (ctx->pend_valid && ctx->sweep_pending_used) ? (const int32_t*)ctx->pend_over : nullptr);
     HIPCHK(ctx, hipMemcpyAsync(ctx->rb_host, ctx->rb_dev, sizeof(count_readback), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const count_readback* rb = (const count_readback*)ctx->rb_host;
+    const count_readback* rb = (const count_readback*)ctx->rb_host.get();
     const int64_t nnz = rb->nnz;
     ctx->pend_overflowed = rb->pad_ != 0;
     const int32_t pool_over = rb->pool_over, list_mx = rb->list_mx;
@@ -1317,13 +1317,13 @@ int32_t mpfmt_launch_rdisc_fill(mpfmt_ctx* ctx, double r)
     int32_t rc;
     const int64_t nnz = ctx->nnz;
     if (!(ctx->rdisc_path_used == 2 && ctx->pool_valid)) {        // the staging CSC is only needed by the two-pass forms
-        if ((rc = ensure(ctx, (void**)&ctx->rowtmp, sizeof(int32_t) * (size_t)nnz))) return rc;
-        if ((rc = ensure(ctx, (void**)&ctx->valtmp, sizeof(double) * (size_t)nnz))) return rc;
+        if ((rc = ctx->rowtmp.ensure(ctx, sizeof(int32_t) * (size_t)nnz))) return rc;
+        if ((rc = ctx->valtmp.ensure(ctx, sizeof(double) * (size_t)nnz))) return rc;
     }
     // (with the slack a following speculative step of the same (N, r) allocates for -- it then finds its arrays in place)
     const size_t nnz_alloc = (size_t)((double)nnz * 1.02) + 4096;
-    if ((rc = ensure(ctx, (void**)&ctx->rowval, sizeof(int32_t) * nnz_alloc))) return rc;
-    if ((rc = ensure(ctx, (void**)&ctx->nzval, sizeof(double) * nnz_alloc))) return rc;
+    if ((rc = ctx->rowval.ensure(ctx, sizeof(int32_t) * nnz_alloc))) return rc;
+    if ((rc = ctx->nzval.ensure(ctx, sizeof(double) * nnz_alloc))) return rc;
     if (ctx->tile_end > ctx->tile_begin && nnz > 0) {
         int done = 0;
         if (ctx->rdisc_path_used == 2 && ctx->pool_valid) {
@@ -1423,9 +1423,9 @@ int32_t mpfmt_graph_step_launch_impl(mpfmt_ctx* ctx, double r)
         ctx->preset_entries = -1;
         if (rc) return rc;
         if (ctx->cnt_mf && ctx->cnt_pool) {
-            if ((rc = ensure(ctx, (void**)&ctx->rowval, sizeof(int32_t) * (size_t)cap))) return rc;
-            if ((rc = ensure(ctx, (void**)&ctx->nzval, sizeof(double) * (size_t)cap))) return rc;
-            if (!ctx->spec_fail) HIPCHK(ctx, hipMalloc((void**)&ctx->spec_fail, sizeof(int32_t)));
+            if ((rc = ctx->rowval.ensure(ctx, sizeof(int32_t) * (size_t)cap))) return rc;
+            if ((rc = ctx->nzval.ensure(ctx, sizeof(double) * (size_t)cap))) return rc;
+            if ((rc = ctx->spec_fail.ensure(ctx, sizeof(int32_t)))) return rc;
             const int64_t nt = ctx->tile_end - ctx->tile_begin;
             // (behind the degree count and its scan -- colptr -- on whichever stream they ran; the join then covers the check too)
             hipLaunchKernelGGL(k_spec_check, dim3(1), dim3(1), 0, ctx->side_pending ? ctx->side_stream : ctx->stream, ctx->pool_flag,

@@ -465,12 +465,12 @@ int32_t mpfmt_launch_sample_masks(mpfmt_ctx* ctx, double r, void* zero, size_t z
     const int64_t nt = ctx->ntiles;
     int32_t rc;
     // (per-sample masks [npad], then the four survivor words of every tile)
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->smask, sizeof(unsigned long long) * (size_t)std::max<int64_t>(ctx->ntiles * 68, 1)))) return rc;
+    if ((rc = ctx->smask.ensure(ctx, sizeof(unsigned long long) * (size_t)std::max<int64_t>(ctx->ntiles * 68, 1)))) return rc;
     if (nt <= 0 || ctx->tile_end <= ctx->tile_begin) return MPFMT_OK;
     const double rpad = r * (1.0 + 1e-9) + 1e-300;
     void* const zp = (zero && zero_bytes % 8 == 0 && ctx->d >= 1 && ctx->d <= 12) ? zero : nullptr;
 #define CASE(DD) case DD: hipLaunchKernelGGL((k_sample_masks<DD>), dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, ctx->stream, ctx->Xs, ctx->tile_lo, ctx->tile_hi, \
-        (int64_t)0, nt, rpad, ctx->boxes, ctx->M, (unsigned long long*)ctx->smask, (unsigned long long*)ctx->smask + ctx->ntiles * 64, (const uint8_t*)ctx->tileneed, \
+        (int64_t)0, nt, rpad, ctx->boxes, ctx->M, (unsigned long long*)ctx->smask.get(), (unsigned long long*)ctx->smask.get() + ctx->ntiles * 64, (const uint8_t*)ctx->tileneed, \
         (unsigned long long*)zp, (int64_t)(zero_bytes / 8)); break;
     switch (ctx->d) { CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) default: break; }
 #undef CASE
@@ -1223,7 +1223,7 @@ int32_t mpfmt_mfma_build_operands(mpfmt_ctx* ctx)
 {
     const int64_t npad = ctx->ntiles * 64;
     int32_t rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->ops, 32 * (size_t)npad))) return rc;
+    if ((rc = ctx->ops.ensure(ctx, 32 * (size_t)npad))) return rc;
     if (npad == 0) return MPFMT_OK;
     const int B = 256;
     hipLaunchKernelGGL(k_make_ops, dim3((unsigned)((npad + B - 1) / B)), dim3(B), 0, ctx->stream,
@@ -1248,24 +1248,24 @@ int32_t mpfmt_mfma_build_lists(mpfmt_ctx* ctx, double r, bool* usable, bool spec
     const bool small = (ctx->tile_end - ctx->tile_begin) < 16 * (int64_t)ctx->num_cus;
     int64_t cap = std::min<int64_t>(ctx->ntiles, std::max<int64_t>(ctx->list_cap, small ? 3072 : 8192));
     const double rpad = r * (1.0 + 1e-9) + 1e-300;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->list_len, sizeof(int32_t) * (size_t)(nt + 1)))) return rc;
+    if ((rc = ctx->list_len.ensure(ctx, sizeof(int32_t) * (size_t)(nt + 1)))) return rc;
     for (int attempt = 0; attempt < 4; ++attempt) {
         if ((double)cap * (double)nt * 4.0 > 32e9) { *usable = false; return MPFMT_OK; }
-        if ((rc = mpfmt_ensure(ctx, (void**)&ctx->lists, sizeof(uint32_t) * (size_t)cap * (size_t)nt))) return rc;
+        if ((rc = ctx->lists.ensure(ctx, sizeof(uint32_t) * (size_t)cap * (size_t)nt))) return rc;
         // (the longest list's word lives in the index arena: zeroed by the index build's one fill, again here only when used since)
         if (!ctx->list_max_clean) HIPCHK(ctx, hipMemsetAsync(ctx->list_max, 0, sizeof(int32_t), ctx->stream));
         ctx->list_max_clean = false;
         const mpfmt_grid& G = ctx->grid;
         // few tiles (a small shard): four wavefronts per tile, kept ids staged in LDS (4 x cap x 4 bytes) -- in a global scratch area when
         // the lists are longer than LDS takes at a useful occupancy (a shard's lists hold every chunk of the OTHER shards: ~4 500 entries)
-        const bool wide = ctx->lists_wide >= 0 ? ctx->lists_wide != 0 : nt < 16 * (int64_t)ctx->num_cus;
+        const bool wide = nt < 16 * (int64_t)ctx->num_cus;
         const bool gst = wide && cap > 3072;
-        if (gst && (rc = mpfmt_ensure(ctx, (void**)&ctx->lists_stage, sizeof(uint32_t) * (size_t)cap * 4 * (size_t)nt))) return rc;
-        uint32_t* const gstage = gst ? (uint32_t*)ctx->lists_stage : nullptr;
+        if (gst && (rc = ctx->lists_stage.ensure(ctx, sizeof(uint32_t) * (size_t)cap * 4 * (size_t)nt))) return rc;
+        uint32_t* const gstage = gst ? (uint32_t*)ctx->lists_stage.get() : nullptr;
 #define CASE(DD) case DD: if (wide) hipLaunchKernelGGL((k_chunk_lists<DD, 4>), dim3((unsigned)nt), dim3(256), gst ? (size_t)0 : (size_t)cap * 16, ctx->stream, ctx->cellstart, \
-            ctx->tile_lo, ctx->tile_hi, ctx->tile_sub, ctx->tile_sub32, G, rpad, ctx->tile_begin, nt, cap, (uint32_t*)ctx->lists, ctx->list_len, ctx->list_max, half ? 1 : 0, ctx->cellkey, ctx->cell_fb, gstage); \
+            ctx->tile_lo, ctx->tile_hi, ctx->tile_sub, ctx->tile_sub32, G, rpad, ctx->tile_begin, nt, cap, (uint32_t*)ctx->lists.get(), ctx->list_len, ctx->list_max, half ? 1 : 0, ctx->cellkey, ctx->cell_fb, gstage); \
         else hipLaunchKernelGGL((k_chunk_lists<DD, 1>), dim3((unsigned)nt), dim3(64), 0, ctx->stream, ctx->cellstart, \
-            ctx->tile_lo, ctx->tile_hi, ctx->tile_sub, ctx->tile_sub32, G, rpad, ctx->tile_begin, nt, cap, (uint32_t*)ctx->lists, ctx->list_len, ctx->list_max, half ? 1 : 0, ctx->cellkey, ctx->cell_fb, (uint32_t*)nullptr); break;
+            ctx->tile_lo, ctx->tile_hi, ctx->tile_sub, ctx->tile_sub32, G, rpad, ctx->tile_begin, nt, cap, (uint32_t*)ctx->lists.get(), ctx->list_len, ctx->list_max, half ? 1 : 0, ctx->cellkey, ctx->cell_fb, (uint32_t*)nullptr); break;
         switch (ctx->d) {
             CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12)
             default: return mpfmt_fail(ctx, MPFMT_ERR_ARG, "MFMA r-disc path supports d <= 12 (got %d)", ctx->d);
@@ -1377,7 +1377,7 @@ template <int MODE>
 int32_t mpfmt_launch_rdisc_mfma(mpfmt_ctx* ctx, double r, float negT)
 {
     mf_args a;
-    a.ops = (const uint4*)ctx->ops; a.Xs = ctx->Xs; a.perm = ctx->perm; a.cellstart = ctx->cellstart;
+    a.ops = (const uint4*)ctx->ops.get(); a.Xs = ctx->Xs; a.perm = ctx->perm; a.cellstart = ctx->cellstart;
     a.tile_lo = ctx->tile_lo; a.tile_hi = ctx->tile_hi;
     a.r2 = r * r; a.rpad = r * (1.0 + 1e-9) + 1e-300; a.negT = negT;
     a.S = ctx->S;
@@ -1396,7 +1396,7 @@ int32_t mpfmt_launch_rdisc_mfma(mpfmt_ctx* ctx, double r, float negT)
     a.xcd_mode = ctx->mf_xcd_mode >= 0 ? ctx->mf_xcd_mode : (a.nitems >= 32768 ? 256 : 64);
     a.npad = ctx->ntiles * 64; a.ntiles = ctx->ntiles;
     a.slice_cnt = ctx->slice_cnt; a.tptr = ctx->tptr; a.rowtmp = ctx->rowtmp; a.valtmp = ctx->valtmp;
-    a.lists = (const uint32_t*)ctx->lists; a.list_len = ctx->list_len; a.list_cap = ctx->list_cap;
+    a.lists = (const uint32_t*)ctx->lists.get(); a.list_len = ctx->list_len; a.list_cap = ctx->list_cap;
     a.pairs = (MODE == 1) ? nullptr : ctx->d_pairs;              // 256 x {tested, survivors} sharded counters
     a.survivors = nullptr;
     a.pool_flag = ctx->pool_flag; a.qcap = ctx->qcap;
@@ -1404,11 +1404,11 @@ int32_t mpfmt_launch_rdisc_mfma(mpfmt_ctx* ctx, double r, float negT)
     a.half = (MODE == 2 && ctx->half_used) ? 1 : 0;
     a.ntiles_shard = ctx->tile_end - ctx->tile_begin;
     a.fb = (MODE == 2 && ctx->broad_in_drain) ? (ctx->bits_in_records ? 2 : 1) : 0; a.M = ctx->M; a.boxes = ctx->boxes;
-    a.smask = (const unsigned long long*)ctx->smask;
+    a.smask = (const unsigned long long*)ctx->smask.get();
     a.st_C = ctx->st_C; a.st_H = (const unsigned long long*)ctx->st_H; a.st_free = ctx->st_free;
     a.st_ss_has = (int32_t)(ctx->ss.has != 0); a.st_ss = ctx->rt_ss;
-    a.st_best = (unsigned long long*)ctx->st_best; a.st_besti = ctx->st_besti; a.st_nfree = ctx->st_nfree;
-    a.pitems = (uint4*)ctx->pair_items; a.pcnt = ctx->pair_cnt; a.icap = ctx->pair_icap; a.pend_over = ctx->pair_over;
+    a.st_best = (unsigned long long*)ctx->st_best.get(); a.st_besti = ctx->st_besti; a.st_nfree = ctx->st_nfree;
+    a.pitems = (uint4*)ctx->pair_items.get(); a.pcnt = ctx->pair_cnt; a.icap = ctx->pair_icap; a.pend_over = ctx->pair_over;
     if (MODE != 2 && ctx->lists_half) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "two-pass r-disc kernels need whole chunk lists");
     if (a.nitems <= 0) return MPFMT_OK;
     const int64_t gran = NXCD * (int64_t)std::max(1, a.xcd_mode);
@@ -1501,10 +1501,10 @@ int32_t mpfmt_rdisc_stream_impl(mpfmt_ctx* ctx, double r, const double* C_host, 
     if (!ok) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "chunk lists exceed 32 GB");
     const int S = mpfmt_slices_for(ctx, nt, true);
     ctx->S = S;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->slice_cnt, sizeof(int32_t) * (size_t)S * std::max<int64_t>(npad, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->st_best, sizeof(uint64_t) * (size_t)S * std::max<int64_t>(npad, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->st_besti, sizeof(int32_t) * (size_t)S * std::max<int64_t>(npad, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->st_nfree, sizeof(int32_t) * (size_t)S * std::max<int64_t>(npad, 1)))) return rc;
+    if ((rc = ctx->slice_cnt.ensure(ctx, sizeof(int32_t) * (size_t)S * std::max<int64_t>(npad, 1)))) return rc;
+    if ((rc = ctx->st_best.ensure(ctx, sizeof(uint64_t) * (size_t)S * std::max<int64_t>(npad, 1)))) return rc;
+    if ((rc = ctx->st_besti.ensure(ctx, sizeof(int32_t) * (size_t)S * std::max<int64_t>(npad, 1)))) return rc;
+    if ((rc = ctx->st_nfree.ensure(ctx, sizeof(int32_t) * (size_t)S * std::max<int64_t>(npad, 1)))) return rc;
     // scratch: C[N], H words, deg[N], nfree[N], parent[N], cost[N], total
     const size_t w = (size_t)(N + 63) / 64;
     const size_t o_C = 0, o_H = o_C + 8 * (size_t)std::max<int64_t>(N, 1), o_deg = o_H + 8 * std::max<size_t>(w, 1), o_nf = o_deg + 8 * (size_t)std::max<int64_t>(N, 1),
@@ -1516,7 +1516,7 @@ int32_t mpfmt_rdisc_stream_impl(mpfmt_ctx* ctx, double r, const double* C_host, 
     if (H_host && N > 0) HIPCHK(ctx, hipMemcpyAsync(sc + o_H, H_host, 8 * w, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(sc + o_tot, 0, 16, ctx->stream));
     if (want_free && (rc = mpfmt_sweep_prepare_ss(ctx))) return rc;
-    if (!ctx->d_pairs) HIPCHK(ctx, hipMalloc((void**)&ctx->d_pairs, 514 * sizeof(unsigned long long)));
+    if ((rc = mpfmt_own_pairs(ctx))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_pairs, 0, 512 * sizeof(unsigned long long), ctx->stream));
     ctx->st_C = C_host ? (const double*)(sc + o_C) : nullptr;
     ctx->st_H = (C_host && H_host) ? (const uint64_t*)(sc + o_H) : nullptr;
@@ -1530,7 +1530,7 @@ int32_t mpfmt_rdisc_stream_impl(mpfmt_ctx* ctx, double r, const double* C_host, 
         if ((rc = mpfmt_launch_rdisc_mfma<3>(ctx, r, negT))) return rc;
         tk.end("stream_kernel");
         const int B = 256;
-        hipLaunchKernelGGL(k_stream_reduce, dim3((unsigned)((npad + B - 1) / B)), dim3(B), 0, ctx->stream, ctx->slice_cnt, (const unsigned long long*)ctx->st_best,
+        hipLaunchKernelGGL(k_stream_reduce, dim3((unsigned)((npad + B - 1) / B)), dim3(B), 0, ctx->stream, ctx->slice_cnt, (const unsigned long long*)ctx->st_best.get(),
                            ctx->st_besti, ctx->st_nfree, S, npad, (int64_t)0, npad, ctx->perm, (int64_t*)(sc + o_deg), (int64_t*)(sc + o_nf), (int64_t*)(sc + o_par),
                            (double*)(sc + o_cost), (unsigned long long*)(sc + o_tot));
         HIPCHK(ctx, hipGetLastError());

@@ -134,14 +134,13 @@ static int32_t sample_free_impl(mpfmt_ctx* ctx, uint64_t seed, int64_t N, const 
         if (!std::isfinite(ctx->ss.lo[i]) || !std::isfinite(ctx->ss.hi[i])) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "state-space bounds must be finite");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
+    mpfmt_tmp tmp;
     double* W = nullptr;                    // [N][d] on the device
-    HIPCHK(ctx, hipMalloc((void**)&W, sizeof(double) * (size_t)N * d));
-    struct guard { double* p; ~guard() { if (p) hipFree(p); } } gW{W};
+    HIPCHK(ctx, tmp.get(&W, sizeof(double) * (size_t)N * d));
     int64_t have = 0;
     if (init) { HIPCHK(ctx, hipMemcpyAsync(W, init, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream)); have = 1; }
     long long* d_att = nullptr;
-    HIPCHK(ctx, hipMalloc((void**)&d_att, sizeof(long long)));
-    struct guard2 { long long* p; ~guard2() { if (p) hipFree(p); } } gA{d_att};
+    HIPCHK(ctx, tmp.get(&d_att, sizeof(long long)));
     HIPCHK(ctx, hipMemsetAsync(d_att, 0, sizeof(long long), ctx->stream));
     uint64_t c0 = 0;
     mpfmt_timed tm1(ctx);

@@ -96,7 +96,7 @@ int32_t mpfmt_upload_shapes2d(mpfmt_ctx* ctx, int32_t n_shapes, const int32_t* k
     }
     if (n_shapes == 0) box.xr[0] = box.xr[1] = box.yr[0] = box.yr[1] = 0.0;                                // SAT2D.jl:90
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->shapes2d, sizeof(mpfmt_shape2d) * S.size()))) return rc;
+    if ((rc = ctx->shapes2d.ensure(ctx, sizeof(mpfmt_shape2d) * S.size()))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ctx->shapes2d, S.data(), sizeof(mpfmt_shape2d) * S.size(), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->M = n_shapes; ctx->dw = 2; ctx->have_boxes = true; ctx->cc_kind = 1; ctx->aabb2d = box;

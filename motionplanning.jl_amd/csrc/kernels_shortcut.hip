@@ -417,17 +417,6 @@ __global__ __launch_bounds__(256) void k_shortcut_gather(const double* __restric
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 namespace {
-struct ScTmp {
-    std::vector<void*> p;
-    ~ScTmp() { for (void* q : p) if (q) hipFree(q); }
-    template <class T> hipError_t get(T** out, size_t bytes)
-    {
-        void* q = nullptr;
-        const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-        if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
-        return e;
-    }
-};
 }  // namespace
 
 template <int D>
@@ -451,7 +440,7 @@ int32_t mpfmt_shortcut_batch_device(mpfmt_ctx* ctx, const double* P, const int64
     // paths per launch: the slabs of one launch stay below 1 GiB
     const size_t per_path = sizeof(double) * 2 * (size_t)ms * d + sizeof(int32_t) * (size_t)SC_INTS * ms + sizeof(int32_t) * (size_t)std::max(M, 1);
     const int64_t chunk = std::max<int64_t>(SC_WAVES, std::min<int64_t>(B, (int64_t)(((size_t)1 << 30) / per_path) / SC_WAVES * SC_WAVES));
-    ScTmp tmp;
+    mpfmt_tmp tmp;
     double *dP = nullptr, *dwp = nullptr, *dout = nullptr, *dcc = nullptr;
     int64_t *doff = nullptr, *dooff = nullptr;
     int32_t *dints = nullptr, *dsurv = nullptr;

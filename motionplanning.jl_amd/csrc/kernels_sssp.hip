@@ -144,29 +144,22 @@ __global__ __launch_bounds__(256) void k_sssp_parents(int64_t N, int64_t src, co
 
 void mpfmt_sssp_free(mpfmt_ctx* ctx)
 {
-    if (ctx->sssp_C) hipFree(ctx->sssp_C);
-    if (ctx->sssp_A) hipFree(ctx->sssp_A);
-    if (ctx->sssp_bm) hipFree(ctx->sssp_bm);
-    if (ctx->sssp_state) hipFree(ctx->sssp_state);
-    if (ctx->sssp_F) hipFree(ctx->sssp_F);
-    if (ctx->sssp_state_host) hipHostFree(ctx->sssp_state_host);
     for (int k = 0; k < 2; ++k) if (ctx->sssp_ev[k]) hipEventDestroy(ctx->sssp_ev[k]);
-    ctx->sssp_C = nullptr; ctx->sssp_A = nullptr; ctx->sssp_bm = nullptr; ctx->sssp_state = nullptr; ctx->sssp_F = nullptr;
-    ctx->sssp_state_host = nullptr; ctx->sssp_ev[0] = ctx->sssp_ev[1] = nullptr;
+    ctx->sssp_ev[0] = ctx->sssp_ev[1] = nullptr;
 }
 
 int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, double* C_host, int64_t* A_host, mpfmt_sssp_info* info)
 {
     const int64_t N = ctx->N, words = (N + 63) / 64;
     int32_t rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->sssp_C, sizeof(double) * (size_t)N))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->sssp_A, sizeof(int64_t) * (size_t)N))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->sssp_bm, sizeof(uint64_t) * 3 * (size_t)words))) return rc;
-    if ((rc = mpfmt_ensure(ctx, &ctx->sssp_state, sizeof(sssp_state)))) return rc;
-    if (!ctx->sssp_state_host) HIPCHK(ctx, hipHostMalloc(&ctx->sssp_state_host, sizeof(sssp_state)));
+    if ((rc = ctx->sssp_C.ensure(ctx, sizeof(double) * (size_t)N))) return rc;
+    if ((rc = ctx->sssp_A.ensure(ctx, sizeof(int64_t) * (size_t)N))) return rc;
+    if ((rc = ctx->sssp_bm.ensure(ctx, sizeof(uint64_t) * 3 * (size_t)words))) return rc;
+    if ((rc = ctx->sssp_state.ensure(ctx, sizeof(sssp_state)))) return rc;
+    if ((rc = ctx->sssp_state_host.ensure(ctx, sizeof(sssp_state)))) return rc;
     for (int k = 0; k < 2; ++k) if (!ctx->sssp_ev[k]) HIPCHK(ctx, hipEventCreate(&ctx->sssp_ev[k]));
-    sssp_state* st = (sssp_state*)ctx->sssp_state;
-    sssp_state* sh = (sssp_state*)ctx->sssp_state_host;
+    sssp_state* st = (sssp_state*)ctx->sssp_state.get();
+    sssp_state* sh = (sssp_state*)ctx->sssp_state_host.get();
     // one wavefront per column, grid-stride: enough waves to fill the chip several times over (a skipped column costs one load)
     const int64_t blocks_all = (N + 3) / 4;
     const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks_all, (int64_t)ctx->num_cus * 16));

@@ -1108,7 +1108,7 @@ int32_t mpfmt_launch_exact_pairs(mpfmt_ctx* ctx, const int32_t* spec_fail)
     if (ctx->tile_end <= ctx->tile_begin || d > 12) return MPFMT_OK;
     const size_t lds = (size_t)SWEEP_CHUNK * 2 * d * sizeof(double);
     mpfmt_timed tk(ctx);
-#define CASE(DD) case DD: hipLaunchKernelGGL((k_exact_pairs<DD>), dim3(1024, 4), dim3(256), lds, ctx->stream, (const uint4*)ctx->pair_items, (const int32_t*)ctx->pair_cnt, \
+#define CASE(DD) case DD: hipLaunchKernelGGL((k_exact_pairs<DD>), dim3(1024, 4), dim3(256), lds, ctx->stream, (const uint4*)ctx->pair_items.get(), (const int32_t*)ctx->pair_cnt, \
         (long long)ctx->pair_icap, nitems, (const int32_t*)ctx->pair_over, ctx->Xs, ctx->boxes, ctx->M, ctx->qkey, (long long)ctx->qcap, ctx->tile_begin * 4, spec_fail); break;
     switch (d) { CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) default: break; }
 #undef CASE
@@ -1121,9 +1121,9 @@ template <int D>
 static int32_t launch_sweep_pending_d(mpfmt_ctx* ctx, double rpad, const int32_t* spec_fail)
 {
     const size_t lds = (size_t)SWEEP_CHUNK * 2 * D * sizeof(double);
-    hipLaunchKernelGGL((k_sweep_pending<D>), dim3((unsigned)ctx->pend_nseg, 8), dim3(256), lds, ctx->stream, (const uint4*)ctx->pend_items,
+    hipLaunchKernelGGL((k_sweep_pending<D>), dim3((unsigned)ctx->pend_nseg, 8), dim3(256), lds, ctx->stream, (const uint4*)ctx->pend_items.get(),
                        (const int32_t*)ctx->pend_cnt, ctx->pend_wcap, (const int32_t*)ctx->pend_over, ctx->Xo, ctx->Xs, rpad, ctx->boxes, ctx->M,
-                       (unsigned long long*)ctx->graph_free, ctx->colptr + ctx->N, spec_fail);
+                       (unsigned long long*)ctx->graph_free.get(), ctx->colptr + ctx->N, spec_fail);
     HIPCHK(ctx, hipGetLastError());
     return MPFMT_OK;
 }
@@ -1798,7 +1798,7 @@ static int32_t launch_graph_sweep_d(mpfmt_ctx* ctx, size_t lds, double rpad, int
     const int64_t ntasks = (sp_end - sp_begin + tc - 1) / tc;
     const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ntasks + waves - 1) / waves, resident));
     hipLaunchKernelGGL(tc == 4 ? k4 : k8, dim3(nb), dim3(SWEEP_GT(D)), lds, ctx->stream, ctx->Xo, ctx->colptr, ctx->rowval, ctx->N,
-                       rpad, ctx->boxes, ctx->M, chunk, ctx->ss, (unsigned long long*)ctx->graph_free, ctx->sweep_ctr, sweep_perm,
+                       rpad, ctx->boxes, ctx->M, chunk, ctx->ss, (unsigned long long*)ctx->graph_free.get(), ctx->sweep_ctr, sweep_perm,
                        sp_begin, sp_end, spec_fail, sorted_rows ? ctx->Xs : ctx->Xo, sorted_rows ? ctx->rowpos : ctx->rowval,
                        sorted_rows ? 1 : 0);
     HIPCHK(ctx, hipGetLastError());
@@ -1820,7 +1820,7 @@ static int32_t launch_sweep_rt_d(mpfmt_ctx* ctx, size_t lds, double rpad, const 
     const unsigned nb = (unsigned)std::max<int64_t>(1, std::min(resident, need));
     hipLaunchKernelGGL(kk, dim3(nb), dim3(SWEEP_GT(D)), lds, ctx->stream, ctx->Xo, ctx->colptr, ctx->N,
                        sorted_rows ? ctx->Xs : ctx->Xo, sorted_rows ? ctx->rowpos : ctx->rowval, rpad, ctx->boxes, ctx->M,
-                       (int)(ctx->ss.has && !ctx->ssflag_all_in), ctx->rt_ss, (unsigned long long*)ctx->graph_free, (const sweep_rd*)ctx->rt_table, ctx->rt_total, ctx->sweep_ctr, spec_fail,
+                       (int)(ctx->ss.has && !ctx->ssflag_all_in), ctx->rt_ss, (unsigned long long*)ctx->graph_free.get(), (const sweep_rd*)ctx->rt_table.get(), ctx->rt_total, ctx->sweep_ctr, spec_fail,
                        sorted_rows ? 1 : 0);
     HIPCHK(ctx, hipGetLastError());
     return MPFMT_OK;
@@ -1831,7 +1831,7 @@ static int32_t launch_sweep_rt_d(mpfmt_ctx* ctx, size_t lds, double rpad, const 
 int32_t mpfmt_sweep_prepare_ss(mpfmt_ctx* ctx)
 {
     int32_t rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rt_ss, sizeof(double) * 2 * MPFMT_MAX_DIM))) return rc;
+    if ((rc = ctx->rt_ss.ensure(ctx, sizeof(double) * 2 * MPFMT_MAX_DIM))) return rc;
     if (!ctx->rt_ss_valid || memcmp(&ctx->rt_ss_host, &ctx->ss, sizeof(mpfmt_ss)) != 0) {
         double b[2 * MPFMT_MAX_DIM];
         for (int i = 0; i < MPFMT_MAX_DIM; ++i) { b[i] = ctx->ss.lo[i]; b[MPFMT_MAX_DIM + i] = ctx->ss.hi[i]; }
@@ -1858,19 +1858,19 @@ static int32_t launch_graph_sweep_rt(mpfmt_ctx* ctx, double rpad, const int32_t*
     const int d = ctx->d;
     const int64_t ncol = sp_end - sp_begin;
     const int64_t cap = entries / 16 + ncol + 8;                          // quarters: every column adds at most one partial quarter (+ padding of the last round)
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rt_cnt, sizeof(int64_t) * (size_t)(ncol + 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rt_off, sizeof(int64_t) * (size_t)(ncol + 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rt_table, sizeof(sweep_rd) * (size_t)cap))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rt_total, sizeof(int64_t)))) return rc;
+    if ((rc = ctx->rt_cnt.ensure(ctx, sizeof(int64_t) * (size_t)(ncol + 1)))) return rc;
+    if ((rc = ctx->rt_off.ensure(ctx, sizeof(int64_t) * (size_t)(ncol + 1)))) return rc;
+    if ((rc = ctx->rt_table.ensure(ctx, sizeof(sweep_rd) * (size_t)cap))) return rc;
+    if ((rc = ctx->rt_total.ensure(ctx, sizeof(int64_t)))) return rc;
     if ((rc = mpfmt_sweep_prepare_ss(ctx))) return rc;
     const size_t tmp_bytes = mpfmt_scan_tmp_bytes((size_t)(ncol + 1));
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rt_tmp, tmp_bytes))) return rc;
+    if ((rc = ctx->rt_tmp.ensure(ctx, tmp_bytes))) return rc;
     const unsigned nbk = (unsigned)((ncol + 1 + 255) / 256);
     hipLaunchKernelGGL(k_round_count, dim3(nbk), dim3(256), 0, ctx->stream, ctx->colptr, sweep_perm, sp_begin, sp_end, ctx->rt_cnt, spec_fail);
     if ((rc = mpfmt_scan_i64_tmp(ctx, ctx->rt_cnt, ctx->rt_off, (size_t)(ncol + 1), ctx->rt_tmp))) return rc;
     const unsigned nbf = (unsigned)((((ncol + 63) / 64 + 1) * 64 + 255) / 256);       // one wavefront per 64 columns + the one that pads and totals
     hipLaunchKernelGGL(k_round_fill, dim3(nbf), dim3(256), 0, ctx->stream, ctx->colptr, sweep_perm, sp_begin, sp_end, ctx->rt_off,
-                       (sweep_rd*)ctx->rt_table, cap, ctx->rt_total, spec_fail);
+                       (sweep_rd*)ctx->rt_table.get(), cap, ctx->rt_total, spec_fail);
     HIPCHK(ctx, hipGetLastError());
     const int waves = SWEEP_GT(d) / 64;
     const size_t lds = (size_t)SWEEP_CHUNK * 2 * d * sizeof(double) + (size_t)waves * (d + 2) * SWEEP_QCAP * sizeof(double);
@@ -1888,7 +1888,7 @@ int32_t mpfmt_launch_graph_sweep(mpfmt_ctx* ctx, const int32_t* spec_fail, int64
     if ((rc = check_boxes(ctx, ctx->d))) return rc;
     if (!ctx->graph_filled) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "graph sweep before the r-disc graph is filled");
     const int64_t words = (std::max<int64_t>(ctx->nnz, mask_entries) + 63) / 64;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->graph_free, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1)))) return rc;
+    if ((rc = ctx->graph_free.ensure(ctx, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1)))) return rc;
     if (ctx->cc_kind == 1) {                                         // 2-D SAT world: lane = entry, whole words written
         mpfmt_timed tm6(ctx);
         HIPCHK(ctx, hipMemsetAsync(ctx->graph_free, 0, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1), ctx->stream));
@@ -1926,12 +1926,12 @@ int32_t mpfmt_launch_graph_sweep(mpfmt_ctx* ctx, const int32_t* spec_fail, int64
         // persistent workgroups (one resident set): boxes are staged once per workgroup, tasks of SWEEP_TC columns
         // are claimed from a counter per obstacle chunk
         const int nchunks = std::max(1, (ctx->M + chunk - 1) / chunk);
-        if ((rc = mpfmt_ensure(ctx, (void**)&ctx->sweep_ctr, sizeof(int) * 8 * (size_t)nchunks))) return rc;
+        if ((rc = ctx->sweep_ctr.ensure(ctx, sizeof(int) * 8 * (size_t)nchunks))) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->sweep_ctr, 0, sizeof(int) * 8 * (size_t)nchunks, ctx->stream));
         // unsharded: all columns in caller order; sharded: only this shard's cell-sorted positions (via perm)
         // the single-pass build also knows every row by its cell-sorted position: rows are then gathered from Xs and the
         // columns visited in cell-sorted order, one contiguous range per XCD
-        const bool sorted_rows = ctx->sweep_sorted && ctx->rowpos_valid && ctx->pool_valid && ctx->rdisc_path_used == 2 && ctx->rowpos && ctx->Xs &&
+        const bool sorted_rows = ctx->rowpos_valid && ctx->pool_valid && ctx->rdisc_path_used == 2 && ctx->rowpos && ctx->Xs &&
                                  ctx->perm != nullptr && ctx->tile_end > ctx->tile_begin;
         const bool sharded = ctx->world > 1 && ctx->perm != nullptr && ctx->tile_end > ctx->tile_begin;
         const bool by_perm = sharded || sorted_rows;

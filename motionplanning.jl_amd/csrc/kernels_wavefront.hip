@@ -59,34 +59,32 @@ struct wf_trip { int32_t x, y; double c; };
 #define WF_XCAP 16384             // triples per rank and exchange round (256 KB): a wavefront rarely connects more per rank
 
 struct mpfmt_wf {
-    int64_t N = 0, words = 0;
-    uint64_t *W = nullptr, *H = nullptr, *Z = nullptr, *Zp = nullptr, *Hn = nullptr, *cand = nullptr, *F = nullptr, *WF = nullptr;
+    int64_t N = 0, words = 0;     // the sample count of the current solve (plain data: every buffer below knows its own capacity)
+    mpfmt_dbuf<uint64_t> W, H, Z, Zp, Hn, cand, F, WF;
     // The sets the mark / connect passes GATHER from, kept a second time by CELL-SORTED POSITION (unsharded Euclidean graphs): a column's
     // rows are spatial neighbours, so by position their bits sit in ~14 cache lines instead of ~103 by caller index (north star, measured
     // on the host) and their costs in ~60 instead of ~106.  WFs: unvisited and valid; Hs: open (Hns: opened during this step); cands:
     // candidates of this step; Cs: cost-to-come.  The graph's rows by position: ctx->rowpos.
-    uint64_t *WFs = nullptr, *Hs = nullptr, *Hns = nullptr, *cands = nullptr;
-    double* Cs = nullptr;
+    mpfmt_dbuf<uint64_t> WFs, Hs, Hns, cands;
+    mpfmt_dbuf<double> Cs;
     int64_t pwords = 0;
     int32_t pos_space = 0;
-    double* C = nullptr;
-    int32_t* A = nullptr;
-    int32_t *zlist = nullptr, *xlist = nullptr;                   // batch nodes / candidates of the step, compacted from the masks
-    int64_t* rowptr = nullptr; int32_t* colidx = nullptr;         // directed cost graphs: forward sets (CSR of the resident CSC)
-    int64_t csr_nnz = 0; bool directed = false;
-    double* part_c = nullptr; int64_t* part_i = nullptr;          // per-block lexicographic minima of the open set
-    double* last_c = nullptr; int64_t* last_i = nullptr;          // per-block lexicographic maxima of the batch (last node in pop order)
-    int64_t* stats = nullptr;     // [WF_MAXBLK][4] per-block cumulative statistics
-    double* boxT = nullptr;       // obstacle set transposed [2*d][mpad]: lane = obstacle reads are coalesced
-    int mpad = 0, boxT_cap = 0;
-    wf_trip* mytrips = nullptr;   // [N] connections of this rank in the current step (sharded)
-    wf_trip* xbuf = nullptr;      // [world][WF_XCAP + 1] exchange slots: header (x = the rank's total count) + one round's triples
-    wf_trip* hdr_host = nullptr;  // pinned [world] headers of the last exchange round
-    int world_alloc = 0;
-    wf_ctr* ctr = nullptr;        // device
-    wf_ctr* ctr_host = nullptr;   // pinned
+    mpfmt_dbuf<double> C;
+    mpfmt_dbuf<int32_t> A;
+    mpfmt_dbuf<int32_t> zlist, xlist;                             // batch nodes / candidates of the step, compacted from the masks
+    mpfmt_dbuf<int64_t> rowptr; mpfmt_dbuf<int32_t> colidx;       // directed cost graphs: forward sets (CSR of the resident CSC)
+    bool directed = false;
+    mpfmt_dbuf<double> part_c; mpfmt_dbuf<int64_t> part_i;        // per-block lexicographic minima of the open set
+    mpfmt_dbuf<int64_t> stats;    // [WF_MAXBLK][4] per-block cumulative statistics
+    mpfmt_dbuf<double> boxT;      // obstacle set transposed [2*d][mpad]: lane = obstacle reads are coalesced
+    int mpad = 0;
+    mpfmt_dbuf<wf_trip> mytrips;  // [N] connections of this rank in the current step (sharded)
+    mpfmt_dbuf<wf_trip> xbuf;     // [world][WF_XCAP + 1] exchange slots: header (x = the rank's total count) + one round's triples
+    mpfmt_hbuf<wf_trip> hdr_host; // pinned [world] headers of the last exchange round
+    mpfmt_dbuf<wf_ctr> ctr;       // device
+    mpfmt_hbuf<wf_ctr> ctr_host;  // pinned
     int64_t prev_tot[4] = {0, 0, 0, 0};
-    int64_t* path_dev = nullptr;
+    mpfmt_dbuf<int64_t> path_dev;
     wf_goal goal;
     double band = 0.0;
     int32_t single = 0, checkpts = 1, use_mask = 0, sharded = 0;
@@ -720,53 +718,33 @@ __global__ void k_wf_A_to_i64(const int32_t* __restrict__ A, int64_t N, int64_t*
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-static mpfmt_wf* wf_of(mpfmt_ctx* ctx) { return (mpfmt_wf*)ctx->wf; }
+static mpfmt_wf* wf_of(mpfmt_ctx* ctx) { return ctx->wf; }
 
 void mpfmt_wf_free(mpfmt_ctx* ctx)
 {
-    mpfmt_wf* s = wf_of(ctx);
-    if (!s) return;
-    void* bufs[] = {s->W, s->H, s->Z, s->Zp, s->Hn, s->cand, s->F, s->WF, s->WFs, s->Hs, s->Hns, s->cands, s->Cs, s->C, s->A, s->zlist, s->xlist, s->rowptr, s->colidx, s->part_c, s->part_i, s->stats, s->boxT, s->mytrips, s->xbuf,
-                    s->ctr, s->path_dev};
-    for (void* b : bufs) if (b) hipFree(b);
-    if (s->ctr_host) hipHostFree(s->ctr_host);
-    if (s->hdr_host) hipHostFree(s->hdr_host);
-    delete s;
+    delete ctx->wf;
     ctx->wf = nullptr;
 }
 
 static int32_t wf_alloc(mpfmt_ctx* ctx, mpfmt_wf* s, int64_t N, int world)
 {
-    const int64_t words = (N + 63) / 64;
-    if (s->N != N) {
-        void** bufs[] = {(void**)&s->W, (void**)&s->H, (void**)&s->Z, (void**)&s->Zp, (void**)&s->Hn, (void**)&s->cand, (void**)&s->F, (void**)&s->WF,
-                         (void**)&s->WFs, (void**)&s->Hs, (void**)&s->Hns, (void**)&s->cands, (void**)&s->Cs,
-                         (void**)&s->C, (void**)&s->A, (void**)&s->zlist, (void**)&s->xlist, (void**)&s->path_dev, (void**)&s->mytrips};
-        for (void** b : bufs) if (*b) { HIPCHK(ctx, hipFree(*b)); *b = nullptr; }
-        HIPCHK(ctx, hipMalloc((void**)&s->W, 8 * words)); HIPCHK(ctx, hipMalloc((void**)&s->H, 8 * words));
-        HIPCHK(ctx, hipMalloc((void**)&s->Z, 8 * words)); HIPCHK(ctx, hipMalloc((void**)&s->Zp, 8 * words));
-        HIPCHK(ctx, hipMalloc((void**)&s->Hn, 8 * words));
-        HIPCHK(ctx, hipMalloc((void**)&s->cand, 8 * words)); HIPCHK(ctx, hipMalloc((void**)&s->F, 8 * words)); HIPCHK(ctx, hipMalloc((void**)&s->WF, 8 * words));
-        HIPCHK(ctx, hipMalloc((void**)&s->C, 8 * N)); HIPCHK(ctx, hipMalloc((void**)&s->A, 4 * N));
-        HIPCHK(ctx, hipMalloc((void**)&s->zlist, 4 * N)); HIPCHK(ctx, hipMalloc((void**)&s->xlist, 4 * N));
-        HIPCHK(ctx, hipMalloc((void**)&s->path_dev, 8 * (N + 1)));
-        HIPCHK(ctx, hipMalloc((void**)&s->WFs, 8 * words)); HIPCHK(ctx, hipMalloc((void**)&s->Hs, 8 * words));      // (ceil(N / 64) words = one per tile)
-        HIPCHK(ctx, hipMalloc((void**)&s->Hns, 8 * words)); HIPCHK(ctx, hipMalloc((void**)&s->cands, 8 * words));
-        HIPCHK(ctx, hipMalloc((void**)&s->Cs, 8 * 64 * words));
-        s->N = N; s->words = words;
-    }
-    if (!s->part_c) { HIPCHK(ctx, hipMalloc((void**)&s->part_c, 8 * WF_MAXPARTS)); HIPCHK(ctx, hipMalloc((void**)&s->part_i, 8 * WF_MAXPARTS)); }
-    if (!s->stats) HIPCHK(ctx, hipMalloc((void**)&s->stats, 8 * 4 * WF_MAXBLK));
-    if (!s->ctr) { HIPCHK(ctx, hipMalloc((void**)&s->ctr, sizeof(wf_ctr))); HIPCHK(ctx, hipHostMalloc((void**)&s->ctr_host, sizeof(wf_ctr))); }
+    const size_t words = (size_t)((N + 63) / 64);            // (ceil(N / 64) words = one per tile)
+    const size_t n = (size_t)N;
+    int32_t rc;
+    for (mpfmt_dbuf<uint64_t>* b : {&s->W, &s->H, &s->Z, &s->Zp, &s->Hn, &s->cand, &s->F, &s->WF, &s->WFs, &s->Hs, &s->Hns, &s->cands})
+        if ((rc = b->ensure(ctx, 8 * words))) return rc;
+    if ((rc = s->Cs.ensure(ctx, 8 * 64 * words))) return rc;
+    if ((rc = s->C.ensure(ctx, 8 * n)) || (rc = s->A.ensure(ctx, 4 * n))) return rc;
+    if ((rc = s->zlist.ensure(ctx, 4 * n)) || (rc = s->xlist.ensure(ctx, 4 * n))) return rc;
+    if ((rc = s->path_dev.ensure(ctx, 8 * (n + 1)))) return rc;
+    s->N = N; s->words = (int64_t)words;
+    if ((rc = s->part_c.ensure(ctx, 8 * WF_MAXPARTS)) || (rc = s->part_i.ensure(ctx, 8 * WF_MAXPARTS))) return rc;
+    if ((rc = s->stats.ensure(ctx, 8 * 4 * WF_MAXBLK))) return rc;
+    if ((rc = s->ctr.ensure(ctx, sizeof(wf_ctr))) || (rc = s->ctr_host.ensure(ctx, sizeof(wf_ctr)))) return rc;
     if (world > 1) {
-        if (!s->mytrips) HIPCHK(ctx, hipMalloc((void**)&s->mytrips, sizeof(wf_trip) * (size_t)N));
-        if (s->world_alloc < world) {
-            if (s->xbuf) { HIPCHK(ctx, hipFree(s->xbuf)); s->xbuf = nullptr; }
-            if (s->hdr_host) { HIPCHK(ctx, hipHostFree(s->hdr_host)); s->hdr_host = nullptr; }
-            HIPCHK(ctx, hipMalloc((void**)&s->xbuf, sizeof(wf_trip) * (size_t)(WF_XCAP + 1) * (size_t)world));
-            HIPCHK(ctx, hipHostMalloc((void**)&s->hdr_host, sizeof(wf_trip) * (size_t)world));
-            s->world_alloc = world;
-        }
+        if ((rc = s->mytrips.ensure(ctx, sizeof(wf_trip) * n))) return rc;
+        if ((rc = s->xbuf.ensure(ctx, sizeof(wf_trip) * (size_t)(WF_XCAP + 1) * (size_t)world))) return rc;
+        if ((rc = s->hdr_host.ensure(ctx, sizeof(wf_trip) * (size_t)world))) return rc;
     }
     return MPFMT_OK;
 }
@@ -779,7 +757,7 @@ static int32_t wf_enqueue_local(mpfmt_ctx* ctx, mpfmt_wf* s)
     hipStream_t st = ctx->stream;
     const int d = ctx->d;
     const bool pos = s->pos_space != 0;
-    wf_pos PA{pos ? s->pwords : 0, (unsigned long long*)s->Hs, s->Hns, s->cands, s->zlist, ctx->iperm};
+    wf_pos PA{pos ? s->pwords : 0, (unsigned long long*)s->Hs.get(), s->Hns, s->cands, s->zlist, ctx->iperm};
     hipLaunchKernelGGL(k_wf_apply_min, dim3(nparts), dim3(256), 0, st, words, s->H, s->Z, s->Zp, s->Hn, s->cand, s->W, s->checkpts ? s->F : nullptr, s->WF, s->C,
                        s->part_c, s->part_i, s->ctr, PA);
     hipLaunchKernelGGL(k_wf_select, dim3(nparts), dim3(256), 0, st, words, nparts, s->H, s->Z, s->C, ctx->Xo, d, s->part_c, s->part_i, s->band,
@@ -790,16 +768,16 @@ static int32_t wf_enqueue_local(mpfmt_ctx* ctx, mpfmt_wf* s)
         // forward sets: the column itself for a metric (nearneighbors.jl:200-203), the row of the cost matrix otherwise.  Position space:
         // the same kernel over the rows as positions, the position-indexed unvisited-and-valid and candidate masks
         if (pos) hipLaunchKernelGGL(k_wf_mark, dim3(grid), dim3(256), 0, st, s->zlist, ctx->colptr, (const int32_t*)ctx->rowpos, s->WFs,
-                                    (unsigned long long*)s->cands, s->ctr);
+                                    (unsigned long long*)s->cands.get(), s->ctr);
         else hipLaunchKernelGGL(k_wf_mark, dim3(grid), dim3(256), 0, st, s->zlist, s->directed ? s->rowptr : ctx->colptr,
-                                s->directed ? s->colidx : ctx->rowval, s->WF, (unsigned long long*)s->cand, s->ctr);
+                                s->directed ? s->colidx : ctx->rowval, s->WF, (unsigned long long*)s->cand.get(), s->ctr);
     } else {
         const int64_t pb = std::min<int64_t>(ctx->tile_begin * 64, ctx->N), pe = std::min<int64_t>(ctx->tile_end * 64, ctx->N);
         hipLaunchKernelGGL(k_wf_mark_owned, dim3(ctx->num_cus * 8), dim3(256), 0, st, ctx->perm, pb, pe, ctx->colptr, ctx->rowval, s->W, F, s->Z,
-                           (unsigned long long*)s->cand, s->ctr);
+                           (unsigned long long*)s->cand.get(), s->ctr);
     }
-    if (pos) hipLaunchKernelGGL(k_wf_compact, dim3(nparts), dim3(64), 0, st, s->pwords, (const unsigned long long*)s->cands, s->xlist, s->ctr);
-    else hipLaunchKernelGGL(k_wf_compact, dim3(nparts), dim3(64), 0, st, words, (const unsigned long long*)s->cand, s->xlist, s->ctr);
+    if (pos) hipLaunchKernelGGL(k_wf_compact, dim3(nparts), dim3(64), 0, st, s->pwords, (const unsigned long long*)s->cands.get(), s->xlist, s->ctr);
+    else hipLaunchKernelGGL(k_wf_compact, dim3(nparts), dim3(64), 0, st, words, (const unsigned long long*)s->cand.get(), s->xlist, s->ctr);
     const uint64_t* gfree = s->use_mask ? ctx->graph_free : nullptr;
     const uint8_t* nseg = s->directed ? ctx->steer_nseg : nullptr;
     // (a directed steering graph's validity bits are its own sweep's: gfree is set there too -- the mask form)
@@ -808,7 +786,7 @@ static int32_t wf_enqueue_local(mpfmt_ctx* ctx, mpfmt_wf* s)
     // wait for a slot starts its share of the candidates when the others are done with theirs.  The runtime's occupancy query counts
     // registers in eights; the device clock at the entry of every wavefront says sixteens: the mask form's 71 registers fit six to a
     // SIMD, not the seven the query answers -- one workgroup per CU started 40 us late and the widest launch took 80 us instead of 60)
-    wf_posc PC{ctx->perm, ctx->rowpos, (const unsigned long long*)s->Hs, s->Cs, (unsigned long long*)s->WFs, (unsigned long long*)s->Hns};
+    wf_posc PC{ctx->perm, ctx->rowpos, (const unsigned long long*)s->Hs.get(), s->Cs, (unsigned long long*)s->WFs.get(), (unsigned long long*)s->Hns.get()};
 #define WF_CONNECT(MODE_, GEOM_, POS_, TRIPS_) DISPATCH_D(d, { int per_cu = 0; \
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_connect<DD, MODE_, GEOM_, POS_>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4; \
         hipFuncAttributes fa_; \
@@ -816,7 +794,7 @@ static int32_t wf_enqueue_local(mpfmt_ctx* ctx, mpfmt_wf* s)
             per_cu = std::max(1, std::min(per_cu, 512 / (((fa_.numRegs + 15) / 16) * 16))); \
         const int cgrid = ctx->num_cus * std::min(per_cu, 8); \
         hipLaunchKernelGGL((k_wf_connect<DD, MODE_, GEOM_, POS_>), dim3(cgrid), dim3(256), 0, st, s->xlist, ctx->colptr, \
-        ctx->rowval, ctx->nzval, s->H, s->C, s->A, (unsigned long long*)s->W, (unsigned long long*)s->Hn, ctx->Xo, s->boxT, ctx->M, s->mpad, ctx->ss, gfree, nseg, \
+        ctx->rowval, ctx->nzval, s->H, s->C, s->A, (unsigned long long*)s->W.get(), (unsigned long long*)s->Hn.get(), ctx->Xo, s->boxT, ctx->M, s->mpad, ctx->ss, gfree, nseg, \
         TRIPS_, s->stats, s->ctr, s->all_in, PC); })
     if (!s->sharded) {
         if (pos) { if (geom) { WF_CONNECT(0, true, true, (wf_trip*)nullptr); } else { WF_CONNECT(0, false, true, (wf_trip*)nullptr); } }
@@ -841,8 +819,8 @@ static int32_t wf_exchange(mpfmt_ctx* ctx, mpfmt_wf* s)
         wf_trip* myslot = s->xbuf + (size_t)rank * (WF_XCAP + 1);
         hipLaunchKernelGGL(k_wf_pack, dim3((WF_XCAP + 255) / 256), dim3(256), 0, st, s->mytrips, round, myslot, s->stats, s->ctr);
         if ((rc = mpfmt_comm_allgather_inplace(ctx, s->xbuf, slot_bytes, st))) return rc;
-        hipLaunchKernelGGL(k_wf_commit, dim3(64), dim3(256), 0, st, s->xbuf, world, round, s->C, s->A, (unsigned long long*)s->W,
-                           (unsigned long long*)s->Hn, s->stats, s->ctr);
+        hipLaunchKernelGGL(k_wf_commit, dim3(64), dim3(256), 0, st, s->xbuf, world, round, s->C, s->A, (unsigned long long*)s->W.get(),
+                           (unsigned long long*)s->Hn.get(), s->stats, s->ctr);
         HIPCHK(ctx, hipMemcpy2DAsync(s->hdr_host, sizeof(wf_trip), s->xbuf, slot_bytes, sizeof(wf_trip), (size_t)world, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
         int64_t mx = 0;
@@ -946,11 +924,7 @@ int32_t mpfmt_wf_begin(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t check
     }
     if (!s->use_mask) {                                    // obstacle table transposed for lane = obstacle reads
         const int mpad = std::max(64, ((ctx->M + 63) / 64) * 64);
-        if (s->boxT_cap < 2 * d * mpad) {
-            if (s->boxT) { HIPCHK(ctx, hipFree(s->boxT)); s->boxT = nullptr; }
-            HIPCHK(ctx, hipMalloc((void**)&s->boxT, sizeof(double) * 2 * (size_t)d * (size_t)mpad));
-            s->boxT_cap = 2 * d * mpad;
-        }
+        if ((rc = s->boxT.ensure(ctx, sizeof(double) * 2 * (size_t)d * (size_t)mpad))) return rc;
         s->mpad = mpad;
         if (ctx->M > 0)
             hipLaunchKernelGGL(k_wf_box_transpose, dim3((unsigned)((mpad * 2 * d + 255) / 256)), dim3(256), 0, ctx->stream, ctx->boxes, ctx->M, 2 * d, mpad, s->boxT);
@@ -978,7 +952,7 @@ int32_t mpfmt_wf_begin(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t check
     if (s->pos_space) {
         s->pwords = s->words;
         if (!ctx->rowpos_valid) {
-            if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rowpos, sizeof(int32_t) * (size_t)std::max<int64_t>(std::max(ctx->nnz, ctx->nnz_cap), 1)))) return rc;
+            if ((rc = ctx->rowpos.ensure(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(std::max(ctx->nnz, ctx->nnz_cap), 1)))) return rc;
             hipLaunchKernelGGL(k_wf_rowpos, dim3((unsigned)((ctx->nnz + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t*)ctx->rowval, (const int32_t*)ctx->iperm,
                                ctx->nnz, ctx->rowpos);
             ctx->rowpos_valid = true;
@@ -1096,8 +1070,8 @@ int32_t mpfmt_wf_commit(mpfmt_ctx* ctx, int64_t n, const int64_t* x, const int64
             t[k + 1].x = (int32_t)(x[o + k] - 1); t[k + 1].y = (int32_t)(y[o + k] - 1); t[k + 1].c = c[o + k];
         }
         HIPCHK(ctx, hipMemcpy(s->xbuf, t.data(), sizeof(wf_trip) * (size_t)(m + 1), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_wf_commit, dim3(64), dim3(256), 0, ctx->stream, s->xbuf, 1, 0, s->C, s->A, (unsigned long long*)s->W,
-                           (unsigned long long*)s->Hn, s->stats, s->ctr);
+        hipLaunchKernelGGL(k_wf_commit, dim3(64), dim3(256), 0, ctx->stream, s->xbuf, 1, 0, s->C, s->A, (unsigned long long*)s->W.get(),
+                           (unsigned long long*)s->Hn.get(), s->stats, s->ctr);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -1225,13 +1199,8 @@ extern "C++" int32_t mpfmt_wf_begin_directed(mpfmt_ctx* ctx, int64_t init_idx, i
     HIPCHK(ctx, hipMemcpyAsync(s->F, F_host, 8 * (size_t)s->words, hipMemcpyHostToDevice, ctx->stream));
     // forward sets
     const int64_t nnz = ctx->nnz;
-    if (s->csr_nnz < std::max<int64_t>(nnz, 1) || !s->rowptr) {
-        if (s->rowptr) { HIPCHK(ctx, hipFree(s->rowptr)); s->rowptr = nullptr; }
-        if (s->colidx) { HIPCHK(ctx, hipFree(s->colidx)); s->colidx = nullptr; }
-        HIPCHK(ctx, hipMalloc((void**)&s->rowptr, sizeof(int64_t) * (size_t)(N + 1)));
-        HIPCHK(ctx, hipMalloc((void**)&s->colidx, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)));
-        s->csr_nnz = std::max<int64_t>(nnz, 1);
-    }
+    if ((rc = s->rowptr.ensure(ctx, sizeof(int64_t) * (size_t)(N + 1)))) return rc;
+    if ((rc = s->colidx.ensure(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
     if ((rc = mpfmt_csc_transpose_resident(ctx, s->rowptr, s->colidx))) return rc;
     s->ms_graph = 0.0; s->ms_sweep = 0.0;
     hipLaunchKernelGGL(k_wf_init, dim3(256), dim3(64), 0, ctx->stream, N, s->words, s->init, s->W, s->H, s->Z, s->Zp, s->Hn, s->cand, s->C, s->A,

@@ -27,25 +27,9 @@ int32_t mpfmt_fail(mpfmt_ctx* ctx, int32_t code, const char* fmt, ...)
 
 int32_t mpfmt_scratch(mpfmt_ctx* ctx, size_t bytes, void** out)
 {
-    if (bytes > ctx->scratch_bytes) {
-        if (ctx->scratch) HIPCHK(ctx, hipFree(ctx->scratch));
-        ctx->scratch = nullptr; ctx->scratch_bytes = 0;
-        size_t want = bytes + bytes / 4 + 4096;
-        HIPCHK(ctx, hipMalloc(&ctx->scratch, want));
-        ctx->scratch_bytes = want;
-    }
+    int32_t rc;
+    if (bytes > ctx->scratch.bytes() && (rc = ctx->scratch.ensure(ctx, bytes + bytes / 4 + 4096))) return rc;
     *out = ctx->scratch;
-    return MPFMT_OK;
-}
-
-int32_t mpfmt_ensure(mpfmt_ctx* ctx, void** p, size_t bytes)
-{
-    if (bytes == 0) bytes = 16;
-    auto it = ctx->caps.find((void*)p);
-    if (*p && it != ctx->caps.end() && it->second >= bytes) return MPFMT_OK;
-    if (*p) { HIPCHK(ctx, hipFree(*p)); *p = nullptr; }
-    HIPCHK(ctx, hipMalloc(p, bytes));
-    ctx->caps[(void*)p] = bytes;
     return MPFMT_OK;
 }
 
@@ -53,19 +37,19 @@ int32_t mpfmt_ensure(mpfmt_ctx* ctx, void** p, size_t bytes)
 //      pending intervals are resolved when a timing is queried.  A small stack lets groups nest.
 #define TIMER_DEPTH 4
 struct timer_rec { std::string name; hipEvent_t a, b; };
-struct timer_state {
+struct mpfmt_timer_state {
     std::vector<hipEvent_t> free_events;
     std::vector<timer_rec> pending;
     hipEvent_t open_a[TIMER_DEPTH];
     int depth = 0;
 };
-static timer_state& timers_of(mpfmt_ctx* ctx)
+static mpfmt_timer_state& timers_of(mpfmt_ctx* ctx)
 {
-    if (!ctx->timer_state) ctx->timer_state = new timer_state();
-    return *(timer_state*)ctx->timer_state;
+    if (!ctx->timer_state) ctx->timer_state = new mpfmt_timer_state();
+    return *ctx->timer_state;
 }
 
-static hipEvent_t timer_event(timer_state& t)
+static hipEvent_t timer_event(mpfmt_timer_state& t)
 {
     if (!t.free_events.empty()) { hipEvent_t e = t.free_events.back(); t.free_events.pop_back(); return e; }
     hipEvent_t e = nullptr;
@@ -76,7 +60,7 @@ static hipEvent_t timer_event(timer_state& t)
 static void timer_resolve(mpfmt_ctx* ctx)
 {
     if (!ctx->timer_state) return;
-    timer_state& t = timers_of(ctx);
+    mpfmt_timer_state& t = timers_of(ctx);
     for (timer_rec& r : t.pending) {
         hipEventSynchronize(r.b);
         float ms = 0.f;
@@ -130,7 +114,7 @@ int32_t mpfmt_side_join(mpfmt_ctx* ctx)
 void mpfmt_time_begin(mpfmt_ctx* ctx)
 {
     if (!ctx->timing_enabled) return;
-    timer_state& t = timers_of(ctx);
+    mpfmt_timer_state& t = timers_of(ctx);
     if (t.depth < TIMER_DEPTH) {
         t.open_a[t.depth] = timer_event(t);
         hipEventRecord(t.open_a[t.depth], ctx->stream);
@@ -141,7 +125,7 @@ void mpfmt_time_begin(mpfmt_ctx* ctx)
 void mpfmt_time_end(mpfmt_ctx* ctx, const char* name)
 {
     if (!ctx->timing_enabled) return;
-    timer_state& t = timers_of(ctx);
+    mpfmt_timer_state& t = timers_of(ctx);
     if (t.depth <= 0) return;
     --t.depth;
     if (t.depth >= TIMER_DEPTH) return;
@@ -155,24 +139,11 @@ void mpfmt_time_end(mpfmt_ctx* ctx, const char* name)
 void mpfmt_time_abandon(mpfmt_ctx* ctx)
 {
     if (!ctx->timing_enabled) return;
-    timer_state& t = timers_of(ctx);
+    mpfmt_timer_state& t = timers_of(ctx);
     if (t.depth <= 0) return;
     --t.depth;
     if (t.depth < TIMER_DEPTH) t.free_events.push_back(t.open_a[t.depth]);
 }
-
-// ---- temporaries of one ABI call: device buffers freed on every exit path -----------------------------------
-struct DevTmp {
-    std::vector<void*> p;
-    ~DevTmp() { for (void* q : p) if (q) hipFree(q); }
-    template <class T> hipError_t get(T** out, size_t bytes)
-    {
-        void* q = nullptr;
-        const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-        if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
-        return e;
-    }
-};
 
 // ---- small conversion kernels --------------------------------------------------------------------------
 __global__ void k_add1_i64(const int64_t* __restrict__ in, int64_t n, int64_t* __restrict__ out)
@@ -229,29 +200,20 @@ int32_t mpfmt_ctx_destroy(mpfmt_ctx* ctx)
     hipDeviceSynchronize();
     // (refused while another thread's open group still has to post this ctx's gather: the ctx stays whole and usable)
     { const int32_t rc = mpfmt_comm_destroy(ctx); if (rc) return rc; }
-    if (ctx->zarena) { hipFree(ctx->zarena); ctx->d_pairs = nullptr; ctx->pool_flag = nullptr; ctx->pair_cnt = nullptr; ctx->qlen = nullptr; }      // (they point into it)
-    void* bufs[] = {ctx->Xo, ctx->perm, ctx->iperm, ctx->cellkey, ctx->idx_arena, ctx->Xt, ctx->tile_lo, ctx->tile_hi, ctx->tile_sub, ctx->tile_sub32,
-                    ctx->slice_cnt, ctx->deg, ctx->colptr, ctx->rowtmp, ctx->valtmp, ctx->rowval, ctx->nzval,
-                    ctx->graph_free, ctx->d_pairs, ctx->boxes, ctx->scratch, ctx->degs, ctx->tptr, ctx->Xs, ctx->ops, ctx->di_ops, ctx->Xo_next, ctx->cellcnt_pad,
-                    ctx->knn_mutual, ctx->knn_st, ctx->knn_bitmap, ctx->knn_lists, ctx->tvaltmp, ctx->tval, ctx->steer_nseg, ctx->rowpos, ctx->pool_flag, ctx->qkey, ctx->qd2, ctx->qlen, ctx->smask, ctx->st_best, ctx->st_besti, ctx->st_nfree, ctx->pend_items, ctx->pend_cnt, ctx->pair_items, ctx->pair_cnt, ctx->lists, ctx->list_len, ctx->lists_stage, ctx->sweep_ctr, ctx->rt_cnt, ctx->rt_off, ctx->rt_tmp, ctx->rt_table, ctx->rt_total, ctx->rt_ss, ctx->ssflag_dev, ctx->shapes2d, ctx->car_keep, ctx->di_pool_i, ctx->di_pool_c, ctx->di_pool_t, ctx->spec_fail, ctx->rb_dev, ctx->bb_dev};
-    if (ctx->rb_host) hipHostFree(ctx->rb_host);
-    if (ctx->export_arena) hipHostFree(ctx->export_arena);
-    if (ctx->bb_host) hipHostFree(ctx->bb_host);
     if (ctx->side_stream) { hipStreamSynchronize(ctx->side_stream); hipStreamDestroy(ctx->side_stream); hipEventDestroy(ctx->ev_fork); hipEventDestroy(ctx->ev_join); }
     for (int k = 0; k < 2; ++k) { if (ctx->copy_stream[k]) hipStreamDestroy(ctx->copy_stream[k]); if (ctx->ev_conv[k]) hipEventDestroy(ctx->ev_conv[k]); if (ctx->ev_copy[k]) hipEventDestroy(ctx->ev_copy[k]); }
     mpfmt_wf_free(ctx);
     mpfmt_sssp_free(ctx);
     if (ctx->aux) { mpfmt_ctx_destroy(ctx->aux); ctx->aux = nullptr; }
-    for (void* b : bufs) if (b) hipFree(b);
     timer_resolve(ctx);
     if (ctx->timer_state) {
-        timer_state* t = (timer_state*)ctx->timer_state;
-        for (hipEvent_t e : t->free_events) hipEventDestroy(e);
-        delete t;
-        ctx->timer_state = nullptr;
+        for (hipEvent_t e : ctx->timer_state->free_events) hipEventDestroy(e);
+        delete ctx->timer_state;
     }
-    if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
+    // the ctx's buffers release themselves: on ctx->device (the aux ctx lives there too), and before the stream they were used on goes
+    const hipStream_t own = ctx->own_stream;
     delete ctx;
+    if (own) hipStreamDestroy(own);
     return MPFMT_OK;
 }
 
@@ -325,15 +287,15 @@ static int32_t adopt_samples(mpfmt_ctx* ctx, const double* src, bool src_on_host
     int32_t rc;
     constexpr int NB = 256;
     struct bb_block { double part[NB][2][MPFMT_MAX_DIM]; int32_t bad; int32_t pad_; };
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->bb_dev, sizeof(bb_block)))) return rc;
-    if (!ctx->bb_host) HIPCHK(ctx, hipHostMalloc(&ctx->bb_host, sizeof(bb_block), hipHostMallocDefault));
-    bb_block* dev = (bb_block*)ctx->bb_dev;
+    if ((rc = ctx->bb_dev.ensure(ctx, sizeof(bb_block)))) return rc;
+    if ((rc = ctx->bb_host.ensure(ctx, sizeof(bb_block)))) return rc;
+    bb_block* dev = (bb_block*)ctx->bb_dev.get();
     // blocks x threads rounded up to a multiple of d: a thread then stays on one axis (k_bbox_partials)
     const int nb = (int)std::min<int64_t>(NB, (N * d + BBOX_THREADS - 1) / BBOX_THREADS);
     const int64_t stride = std::max<int64_t>(((int64_t)std::max(nb, 1) * BBOX_THREADS / d) * d, d);      // (rounded DOWN: every residue below it has a thread)
     double lo[MPFMT_MAX_DIM], hi[MPFMT_MAX_DIM];
     for (int i = 0; i < d; ++i) { lo[i] = 0.0; hi[i] = 0.0; }
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->Xo_next, sizeof(double) * (size_t)N * d))) return rc;
+    if ((rc = ctx->Xo_next.ensure(ctx, sizeof(double) * (size_t)N * d))) return rc;
     if (N > 0) {
         HIPCHK(ctx, hipMemsetAsync(&dev->bad, 0, sizeof(int32_t), ctx->stream));
         // host samples: the PCIe copy, then the reduction over the copy; device samples: the reduction IS the copy
@@ -345,7 +307,7 @@ static int32_t adopt_samples(mpfmt_ctx* ctx, const double* src, bool src_on_host
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (N > 0) {
-        const bb_block* h = (const bb_block*)ctx->bb_host;
+        const bb_block* h = (const bb_block*)ctx->bb_host.get();
         if (h->bad) {
             if (src_on_host)                                         // (name the sample, as the host check used to)
                 for (int64_t p = 0; p < N; ++p)
@@ -356,18 +318,14 @@ static int32_t adopt_samples(mpfmt_ctx* ctx, const double* src, bool src_on_host
         }
     }
     // accepted: the new buffer becomes the ctx's sample set (the two members change places, capacities with them)
-    {
-        std::swap(ctx->Xo, ctx->Xo_next);
-        const size_t ca = ctx->caps[(void*)&ctx->Xo], cb = ctx->caps[(void*)&ctx->Xo_next];
-        ctx->caps[(void*)&ctx->Xo] = cb; ctx->caps[(void*)&ctx->Xo_next] = ca;
-    }
+    ctx->Xo.swap(ctx->Xo_next);
     ctx->samples_epoch += 1;
     ctx->grid_r = -1.0; ctx->graph_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0;
     ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
     ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
     ctx->nnz = 0;
     if (N > 0) {
-        const bb_block* h = (const bb_block*)ctx->bb_host;
+        const bb_block* h = (const bb_block*)ctx->bb_host.get();
         for (int i = 0; i < d; ++i) { lo[i] = INFINITY; hi[i] = -INFINITY; }
         for (int b = 0; b < nb; ++b)
             for (int i = 0; i < d; ++i) { lo[i] = std::min(lo[i], h->part[b][0][i]); hi[i] = std::max(hi[i], h->part[b][1][i]); }
@@ -417,7 +375,7 @@ int32_t mpfmt_upload_boxes(mpfmt_ctx* ctx, const double* lohi, int32_t M, int32_
     if (ss_lo && (d_state < 1 || d_state > MPFMT_MAX_DIM)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "d_state = %d out of range", d_state);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->boxes, sizeof(double) * (size_t)M * 2 * dw))) return rc;
+    if ((rc = ctx->boxes.ensure(ctx, sizeof(double) * (size_t)M * 2 * dw))) return rc;
     if (M > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->boxes, lohi, sizeof(double) * (size_t)M * 2 * dw, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->M = M; ctx->dw = dw; ctx->have_boxes = true; ctx->cc_kind = 0;
@@ -558,9 +516,9 @@ int32_t mpfmt_graph_import(mpfmt_ctx* ctx, double r, const int64_t* colptr, cons
     for (int64_t e = 0; e < nnz; ++e) rv0[e] = (int32_t)(rowval[e] - 1);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->colptr, sizeof(int64_t) * (size_t)(N + 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->rowval, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->nzval, sizeof(double) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
+    if ((rc = ctx->colptr.ensure(ctx, sizeof(int64_t) * (size_t)(N + 1)))) return rc;
+    if ((rc = ctx->rowval.ensure(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
+    if ((rc = ctx->nzval.ensure(ctx, sizeof(double) * (size_t)std::max<int64_t>(nnz, 1)))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ctx->colptr, cp0.data(), sizeof(int64_t) * (size_t)(N + 1), hipMemcpyHostToDevice, ctx->stream));
     if (nnz > 0) {
         HIPCHK(ctx, hipMemcpyAsync(ctx->rowval, rv0.data(), sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
@@ -593,7 +551,7 @@ int32_t mpfmt_rdisc_query(mpfmt_ctx* ctx, int64_t v, double r, int64_t* inds, do
 
 // ---- validity sweeps ---------------------------------------------------------------------------------
 
-static int32_t up_i64(mpfmt_ctx* ctx, DevTmp& tmp, const int64_t* h, int64_t n, int64_t** d)
+static int32_t up_i64(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const int64_t* h, int64_t n, int64_t** d)
 {
     *d = nullptr;
     HIPCHK(ctx, tmp.get(d, sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1)));
@@ -621,7 +579,7 @@ int32_t mpfmt_points_free(mpfmt_ctx* ctx, const int64_t* idx, int64_t n, uint64_
     int32_t rc;
     if (idx && (rc = check_idx(ctx, idx, n, "idx"))) return rc;
     const int64_t words = (n + 63) / 64;
-    DevTmp tmp;
+    mpfmt_tmp tmp;
     int64_t* d_idx = nullptr; uint64_t* d_mask = nullptr;
     if (idx && (rc = up_i64(ctx, tmp, idx, n, &d_idx))) return rc;
     HIPCHK(ctx, tmp.get(&d_mask, sizeof(uint64_t) * words));
@@ -645,7 +603,7 @@ int32_t mpfmt_edges_free(mpfmt_ctx* ctx, const int64_t* src, const int64_t* dst,
     int32_t rc;
     if ((rc = check_idx(ctx, src, E, "src")) || (rc = check_idx(ctx, dst, E, "dst"))) return rc;
     const int64_t words = (E + 63) / 64;
-    DevTmp tmp;
+    mpfmt_tmp tmp;
     int64_t *d_s = nullptr, *d_t = nullptr; uint64_t* d_mask = nullptr;
     if ((rc = up_i64(ctx, tmp, src, E, &d_s))) return rc;
     if ((rc = up_i64(ctx, tmp, dst, E, &d_t))) return rc;
@@ -672,7 +630,7 @@ int32_t mpfmt_mc_edges_collision(mpfmt_ctx* ctx, const int64_t* src, const int64
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
     if ((rc = check_idx(ctx, src, E, "src")) || (rc = check_idx(ctx, dst, E, "dst"))) return rc;
-    DevTmp tmp;
+    mpfmt_tmp tmp;
     int64_t *d_s = nullptr, *d_t = nullptr; unsigned long long* d_h = nullptr;
     if ((rc = up_i64(ctx, tmp, src, E, &d_s))) return rc;
     if ((rc = up_i64(ctx, tmp, dst, E, &d_t))) return rc;
@@ -697,7 +655,7 @@ int32_t mpfmt_mc_edges_collision_is(mpfmt_ctx* ctx, const int64_t* src, const in
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
     if ((rc = check_idx(ctx, src, E, "src")) || (rc = check_idx(ctx, dst, E, "dst"))) return rc;
-    DevTmp tmp;
+    mpfmt_tmp tmp;
     int64_t *d_s = nullptr, *d_t = nullptr; unsigned long long* d_h = nullptr;
     if ((rc = up_i64(ctx, tmp, src, E, &d_s))) return rc;
     if ((rc = up_i64(ctx, tmp, dst, E, &d_t))) return rc;
@@ -723,7 +681,7 @@ int32_t mpfmt_mc_edges_collision_ais(mpfmt_ctx* ctx, const int64_t* src, const i
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
     if ((rc = check_idx(ctx, src, E, "src")) || (rc = check_idx(ctx, dst, E, "dst"))) return rc;
-    DevTmp tmp;
+    mpfmt_tmp tmp;
     int64_t *d_s = nullptr, *d_t = nullptr; unsigned long long* d_h = nullptr; double* d_mu = nullptr;
     if ((rc = up_i64(ctx, tmp, src, E, &d_s))) return rc;
     if ((rc = up_i64(ctx, tmp, dst, E, &d_t))) return rc;
@@ -750,7 +708,7 @@ static int32_t explicit_sweep(mpfmt_ctx* ctx, const double* P, const double* Q, 
     const int d = ctx->dw;
     const int64_t words = (n + 63) / 64;
     const size_t pb = sizeof(double) * (size_t)n * d;
-    DevTmp tmp;
+    mpfmt_tmp tmp;
     double *dP = nullptr, *dQ = nullptr; uint64_t* d_mask = nullptr;
     HIPCHK(ctx, tmp.get(&dP, pb));
     HIPCHK(ctx, hipMemcpyAsync(dP, P, pb, hipMemcpyHostToDevice, ctx->stream));
@@ -928,13 +886,11 @@ int32_t mpfmt_export_arena(mpfmt_ctx* ctx, int64_t bytes, void** out)
     if (!ctx) return MPFMT_ERR_ARG;
     if (!out || bytes < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "mpfmt_export_arena: bad arguments");
     *out = nullptr;
-    if ((size_t)bytes > ctx->export_arena_bytes) {
+    if ((size_t)bytes > ctx->export_arena.bytes()) {
         HIPCHK(ctx, hipSetDevice(ctx->device));
-        if (ctx->export_arena) { HIPCHK(ctx, hipHostFree(ctx->export_arena)); ctx->export_arena = nullptr; ctx->export_arena_bytes = 0; }
         // (an eighth of slack: the next graph of the same problem -- new samples, new obstacles -- finds its room in place)
-        const size_t want = (size_t)bytes + (size_t)bytes / 8 + 4096;
-        HIPCHK(ctx, hipHostMalloc(&ctx->export_arena, want, hipHostMallocDefault));
-        ctx->export_arena_bytes = want;
+        int32_t rc;
+        if ((rc = ctx->export_arena.ensure(ctx, (size_t)bytes + (size_t)bytes / 8 + 4096))) return rc;
     }
     *out = ctx->export_arena;
     return MPFMT_OK;
@@ -998,7 +954,7 @@ int32_t mpfmt_euclid_steer(mpfmt_ctx* ctx, const int64_t* src, const int64_t* ds
     int32_t rc;
     if ((rc = check_idx(ctx, src, E, "src")) || (rc = check_idx(ctx, dst, E, "dst"))) return rc;
     const int d = ctx->d;
-    DevTmp tmp;
+    mpfmt_tmp tmp;
     int64_t *d_s = nullptr, *d_t = nullptr; double *dt = nullptr, *du = nullptr;
     if ((rc = up_i64(ctx, tmp, src, E, &d_s))) return rc;
     if ((rc = up_i64(ctx, tmp, dst, E, &d_t))) return rc;
@@ -1022,7 +978,7 @@ int32_t mpfmt_euclid_propagate(mpfmt_ctx* ctx, const int64_t* src, int64_t E, co
     int32_t rc;
     if ((rc = check_idx(ctx, src, E, "src"))) return rc;
     const int d = ctx->d;
-    DevTmp tmp;
+    mpfmt_tmp tmp;
     int64_t* d_s = nullptr; double *dt = nullptr, *du = nullptr, *ds = nullptr, *dout = nullptr;
     if ((rc = up_i64(ctx, tmp, src, E, &d_s))) return rc;
     HIPCHK(ctx, tmp.get(&dt, sizeof(double) * (size_t)E));
@@ -1059,7 +1015,7 @@ int32_t mpfmt_expand(mpfmt_ctx* ctx, const uint64_t* W, const uint64_t* H, const
     int32_t rc;
     if ((rc = check_idx(ctx, zs, nz, "zs"))) return rc;
     const int64_t N = ctx->N, words = (N + 63) / 64;
-    DevTmp tmp;
+    mpfmt_tmp tmp;
     uint64_t *dW = nullptr, *dH = nullptr, *dF = nullptr; double* dC = nullptr; int64_t* dz = nullptr;
     int64_t *dxs = nullptr, *dym = nullptr; double* dcm = nullptr; uint8_t* dfr = nullptr;
     const int64_t capd = std::max<int64_t>(cap, 1);
@@ -1318,7 +1274,7 @@ static int32_t sssp_ready(mpfmt_ctx* ctx)
 static int32_t sssp_point_bitmap(mpfmt_ctx* ctx)
 {
     int32_t rc;
-    if ((rc = mpfmt_ensure(ctx, (void**)&ctx->sssp_F, sizeof(uint64_t) * (size_t)((ctx->N + 63) / 64)))) return rc;
+    if ((rc = ctx->sssp_F.ensure(ctx, sizeof(uint64_t) * (size_t)((ctx->N + 63) / 64)))) return rc;
     return mpfmt_launch_points_free(ctx, nullptr, ctx->N, ctx->sssp_F);
 }
 
@@ -1724,8 +1680,8 @@ int32_t mpfmt_di_graph_device_ptrs(mpfmt_ctx* ctx, void** colptr, void** rowval,
     if (rowval) *rowval = ctx->rowval;
     if (nzval) *nzval = ctx->nzval;
     if (tval) *tval = ctx->tval;
-    if (free_mask) *free_mask = ctx->steer_swept ? (void*)ctx->graph_free : nullptr;
-    if (nseg) *nseg = ctx->steer_swept ? (void*)ctx->steer_nseg : nullptr;
+    if (free_mask) *free_mask = ctx->steer_swept ? (void*)ctx->graph_free.get() : nullptr;
+    if (nseg) *nseg = ctx->steer_swept ? (void*)ctx->steer_nseg.get() : nullptr;
     return MPFMT_OK;
 }
 
@@ -1740,7 +1696,7 @@ int32_t mpfmt_di_steer(mpfmt_ctx* ctx, const double* X0, const double* X1, int64
     if (!(rho > 0.0) || !(r > 0.0)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "rho and r must be > 0");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t pb = sizeof(double) * (size_t)n * 2 * m;
-    DevTmp tmp;
+    mpfmt_tmp tmp;
     double *d0 = nullptr, *d1 = nullptr, *dc = nullptr, *dt = nullptr;
     HIPCHK(ctx, tmp.get(&d0, pb)); HIPCHK(ctx, tmp.get(&d1, pb));
     HIPCHK(ctx, tmp.get(&dc, 8 * n)); HIPCHK(ctx, tmp.get(&dt, 8 * n));
@@ -1779,7 +1735,7 @@ static int32_t car_steer_pairs(mpfmt_ctx* ctx, mpfmt_steer kind, const double* X
     if (!X0 || !X1 || !cost) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL array");
     if (!(turn_radius > 0.0) || !(speed > 0.0)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "turning radius and speed must be > 0");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevTmp tmp;
+    mpfmt_tmp tmp;
     double *d0, *d1, *dc, *du; int32_t* dn;
     int32_t rc;
     HIPCHK(ctx, tmp.get(&d0, sizeof(double) * 3 * n));

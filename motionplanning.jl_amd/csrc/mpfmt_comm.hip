@@ -94,28 +94,25 @@ struct mpfmt_comm {
     hipEvent_t ev_compute = nullptr;         // compute stream -> communication stream
     hipEvent_t ev_done = nullptr;            // communication stream -> host / compute stream
     // free-mask gather: [world][2 + cap] words; slot g = (mask words of rank g, nnz of rank g, mask...)
-    uint64_t* gbuf = nullptr;
-    int64_t gbuf_words = 0;
+    mpfmt_dbuf<uint64_t> gbuf;
     int64_t cap = -1;                        // mask words per rank agreed for the NEXT exchange (-1: not agreed yet)
     int64_t slot_last = 0;                   // words per rank slot (2 header words + capacity) of the last exchange
-    int64_t* hdr_host = nullptr;             // pinned [world][2]
-    int64_t* hdr_dev = nullptr;              // [world][2] staging of the first (lengths only) exchange
+    mpfmt_hbuf<int64_t> hdr_host;            // pinned [world][2]
+    mpfmt_dbuf<int64_t> hdr_dev;             // [world][2] staging of the first (lengths only) exchange
     bool pending = false;
     bool grouped = false;                    // the gather in flight was launched inside mpfmt_group_begin / _end (one thread, several ctxs)
     bool post_due = false;                   // its header copy + completion event are still to be enqueued (by mpfmt_group_end)
     int64_t my_words = 0, my_nnz = 0;
-    uint64_t* snap = nullptr;                // this rank's mask as it was at _launch: a repeat at a larger capacity re-sends THAT step
-    int64_t snap_words = 0;
+    mpfmt_dbuf<uint64_t> snap;               // this rank's mask as it was at _launch: a repeat at a larger capacity re-sends THAT step
     // generic all-gather staging (wavefront triples): [world][slot]
-    void* abuf = nullptr;
-    size_t abuf_bytes = 0;
+    mpfmt_dbuf<void> abuf;
 };
 
 static int32_t comm_of(mpfmt_ctx* ctx, mpfmt_comm** out)
 {
     if (!ctx) return MPFMT_ERR_ARG;
     if (!ctx->comm) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no communicator (mpfmt_comm_create)");
-    *out = (mpfmt_comm*)ctx->comm;
+    *out = ctx->comm;
     return MPFMT_OK;
 }
 
@@ -139,7 +136,7 @@ int32_t mpfmt_comm_allgather_inplace(mpfmt_ctx* ctx, void* buf, size_t bytes_per
 
 int32_t mpfmt_comm_world(const mpfmt_ctx* ctx, int* rank, int* world)
 {
-    if (ctx->comm) { const mpfmt_comm* c = (const mpfmt_comm*)ctx->comm; *rank = c->rank; *world = c->world; return 1; }
+    if (ctx->comm) { const mpfmt_comm* c = ctx->comm; *rank = c->rank; *world = c->world; return 1; }
     *rank = ctx->rank; *world = ctx->world;
     return 0;
 }
@@ -165,10 +162,11 @@ static int32_t gather_post(mpfmt_ctx* ctx, mpfmt_comm* c)
 static int32_t gather_issue(mpfmt_ctx* ctx, mpfmt_comm* c)
 {
     const int64_t slot = c->cap + 2;
-    if (c->gbuf_words < slot * c->world) {
-        if (c->gbuf) { HIPCHK(ctx, hipStreamSynchronize(c->stream)); HIPCHK(ctx, hipFree(c->gbuf)); c->gbuf = nullptr; }
-        HIPCHK(ctx, hipMalloc((void**)&c->gbuf, sizeof(uint64_t) * (size_t)(slot * c->world)));
-        c->gbuf_words = slot * c->world;
+    const size_t gbytes = sizeof(uint64_t) * (size_t)(slot * c->world);
+    if (c->gbuf.bytes() < gbytes) {
+        int32_t rc;
+        if (c->gbuf) HIPCHK(ctx, hipStreamSynchronize(c->stream));
+        if ((rc = c->gbuf.ensure(ctx, gbytes))) return rc;
     }
     // pack on the compute stream (after the sweep and the snapshot), exchange on the communication stream
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, c->ev_done, 0));        // the previous gather has left the buffer
@@ -228,12 +226,12 @@ int32_t mpfmt_group_end(void)
     due.swap(g_group_post);
     if (gr != ncclSuccess) {
         g_group_depth = 0;
-        for (mpfmt_ctx* ctx : due) { mpfmt_comm* c = (mpfmt_comm*)ctx->comm; if (c) { c->post_due = false; c->pending = false; } }
+        for (mpfmt_ctx* ctx : due) { mpfmt_comm* c = ctx->comm; if (c) { c->post_due = false; c->pending = false; } }
         return mpfmt_fail(nullptr, MPFMT_ERR_HIP, "ncclGroupEnd failed: %s", g_rccl.GetErrorString(gr));
     }
     int32_t first = MPFMT_OK;
     for (mpfmt_ctx* ctx : due) {
-        rc = gather_post(ctx, (mpfmt_comm*)ctx->comm);
+        rc = gather_post(ctx, ctx->comm);
         if (rc && !first) first = rc;
     }
     return first;
@@ -260,21 +258,22 @@ int32_t mpfmt_comm_create(mpfmt_ctx* ctx, int32_t rank, int32_t world, const uin
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_compute, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->hdr_host, sizeof(int64_t) * 2 * (size_t)world);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->hdr_dev, sizeof(int64_t) * 2 * (size_t)world);
+    ctx->comm = c;
     if (e != hipSuccess) {
-        ctx->comm = c;
         mpfmt_comm_destroy(ctx);
         return mpfmt_fail(ctx, MPFMT_ERR_HIP, "communicator resources: %s", hipGetErrorString(e));
     }
-    ctx->comm = c;
+    if ((rc = c->hdr_host.ensure(ctx, sizeof(int64_t) * 2 * (size_t)world)) || (rc = c->hdr_dev.ensure(ctx, sizeof(int64_t) * 2 * (size_t)world))) {
+        mpfmt_comm_destroy(ctx);                              // (keeps the message of the failed allocation)
+        return rc;
+    }
     return mpfmt_set_shard(ctx, rank, world);
 }
 
 int32_t mpfmt_comm_destroy(mpfmt_ctx* ctx)
 {
     if (!ctx || !ctx->comm) return MPFMT_OK;
-    mpfmt_comm* c = (mpfmt_comm*)ctx->comm;
+    mpfmt_comm* c = ctx->comm;
     // a ctx destroyed inside an open group must not be posted at group_end: the opener's list is thread-local, so only the opening
     // thread can take the ctx out of it -- from any other thread the destroy is refused while the group's post is due
     const size_t before = g_group_post.size();
@@ -284,15 +283,11 @@ int32_t mpfmt_comm_destroy(mpfmt_ctx* ctx)
     hipSetDevice(ctx->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
-    if (c->gbuf) hipFree(c->gbuf);
-    if (c->snap) hipFree(c->snap);
-    if (c->abuf) hipFree(c->abuf);
-    if (c->hdr_dev) hipFree(c->hdr_dev);
-    if (c->hdr_host) hipHostFree(c->hdr_host);
     if (c->ev_compute) hipEventDestroy(c->ev_compute);
     if (c->ev_done) hipEventDestroy(c->ev_done);
-    if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    const hipStream_t st = c->stream;
+    delete c;                                                 // (its buffers go before the stream they were used on)
+    if (st) hipStreamDestroy(st);
     ctx->comm = nullptr;
     return MPFMT_OK;
 }
@@ -329,11 +324,9 @@ int32_t mpfmt_allgather_free_mask_launch(mpfmt_ctx* ctx, int64_t cap_hint)
     // snapshot of this rank's mask and lengths: the overlap protocol runs the NEXT step's kernels before _finish, so a repeat at a
     // larger capacity must not read the ctx's live mask (it would gather step k+1 under step k's name)
     c->my_words = words; c->my_nnz = ctx->nnz;
-    if (c->snap_words < std::max<int64_t>(words, 1)) {
-        if (c->snap) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(c->snap)); c->snap = nullptr; }
-        const int64_t want = std::max<int64_t>(words + words / 8, 64);
-        HIPCHK(ctx, hipMalloc((void**)&c->snap, sizeof(uint64_t) * (size_t)want));
-        c->snap_words = want;
+    if (c->snap.bytes() < sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1)) {
+        if (c->snap) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if ((rc = c->snap.ensure(ctx, sizeof(uint64_t) * (size_t)std::max<int64_t>(words + words / 8, 64)))) return rc;
     }
     if (words > 0) HIPCHK(ctx, hipMemcpyAsync(c->snap, ctx->graph_free, sizeof(uint64_t) * (size_t)words, hipMemcpyDeviceToDevice, ctx->stream));
     return gather_issue(ctx, c);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include <map>
+#include <utility>
 #include <vector>
 #include "../../include/mpfmt.h"
 #include "mpfmt_host.h"
@@ -78,6 +79,68 @@ struct mpfmt_shape2d {
 };
 struct mpfmt_aabb2d { double xr[2], yr[2]; };
 
+struct mpfmt_ctx;
+struct mpfmt_wf;                         // kernels_wavefront.hip
+struct mpfmt_comm;                       // mpfmt_comm.hip
+struct mpfmt_timer_state;                    // mpfmt_capi.hip
+int32_t mpfmt_fail(mpfmt_ctx* ctx, int32_t code, const char* fmt, ...);
+
+// An owning buffer: one pointer, its capacity in bytes, and a destructor.  PINNED = false: device memory; true: page-locked host
+// memory.  Whoever holds one of these owns the allocation; a raw pointer member is a view into somebody else's.
+template <class T, bool PINNED> struct mpfmt_buf {
+    mpfmt_buf() = default;
+    mpfmt_buf(const mpfmt_buf&) = delete;
+    mpfmt_buf& operator=(const mpfmt_buf&) = delete;
+    mpfmt_buf(mpfmt_buf&& o) noexcept { swap(o); }
+    mpfmt_buf& operator=(mpfmt_buf&& o) noexcept { swap(o); return *this; }
+    ~mpfmt_buf() { reset(); }
+    void swap(mpfmt_buf& o) noexcept { std::swap(p_, o.p_); std::swap(bytes_, o.bytes_); }
+    void reset()
+    {
+        if (p_) { if (PINNED) hipHostFree(p_); else hipFree(p_); }
+        p_ = nullptr; bytes_ = 0;
+    }
+    // grow-only, exact size (no slack), contents NOT kept across a reallocation; 0 bytes asks for 16.  A failed allocation leaves
+    // the buffer empty.
+    int32_t ensure(mpfmt_ctx* ctx, size_t bytes)
+    {
+        if (bytes == 0) bytes = 16;
+        if (p_ && bytes_ >= bytes) return MPFMT_OK;
+        reset();
+        void* q = nullptr;
+        const hipError_t e = PINNED ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
+        if (e != hipSuccess)
+            return mpfmt_fail(ctx, MPFMT_ERR_HIP, "%s of %zu bytes failed: %s", PINNED ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
+        p_ = (T*)q; bytes_ = bytes;
+        return MPFMT_OK;
+    }
+    operator T*() const { return p_; }
+    T* operator->() const { return p_; }
+    T* get() const { return p_; }
+    size_t bytes() const { return bytes_; }
+private:
+    T* p_ = nullptr;
+    size_t bytes_ = 0;
+};
+template <class T> using mpfmt_dbuf = mpfmt_buf<T, false>;      // device
+template <class T> using mpfmt_hbuf = mpfmt_buf<T, true>;       // page-locked host
+
+// temporaries of one ABI call: device buffers freed on every exit path
+struct mpfmt_tmp {
+    std::vector<void*> p;
+    mpfmt_tmp() = default;
+    mpfmt_tmp(const mpfmt_tmp&) = delete;
+    mpfmt_tmp& operator=(const mpfmt_tmp&) = delete;
+    ~mpfmt_tmp() { for (void* q : p) hipFree(q); }
+    template <class T> hipError_t get(T** out, size_t bytes)
+    {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
+        if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
+        return e;
+    }
+};
+
 // the steering graph resident in a ctx (kernels_di.hip, kernels_car.hip)
 enum mpfmt_steer : int32_t { MPFMT_STEER_DI = 1, MPFMT_STEER_DUBINS = 2, MPFMT_STEER_REEDSSHEPP = 3 };
 
@@ -97,125 +160,118 @@ struct mpfmt_ctx {
     int32_t overlap = 1;                 // option: 1 = the side stream from 65536 samples on, 2 = always, 0 = every kernel of the step on ctx->stream
     hipStream_t copy_stream[2] = {nullptr, nullptr};      // mpfmt_graph_export: two device-to-host streams and their hand-over events
     hipEvent_t ev_conv[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
-    void* export_arena = nullptr;        // page-locked host memory of mpfmt_graph_export_pinned (grow-only, lives as long as the ctx)
-    size_t export_arena_bytes = 0;
+    mpfmt_hbuf<void> export_arena;        // page-locked host memory of mpfmt_graph_export_pinned (grow-only, lives as long as the ctx)
     std::string err;
     int rank = 0, world = 1;
 
     // ---- samples -------------------------------------------------------------------------------
     int64_t N = 0;
     int32_t d = 0;
-    double* Xo = nullptr;                // [N][d] original order (AoS = the caller's layout)
-    double* Xo_next = nullptr;           // where an upload lands: changes places with Xo once the set has been accepted (a refused set leaves the ctx as it was)
+    mpfmt_dbuf<double> Xo;                // [N][d] original order (AoS = the caller's layout)
+    mpfmt_dbuf<double> Xo_next;           // where an upload lands: changes places with Xo once the set has been accepted (a refused set leaves the ctx as it was)
     double bb_lo[MPFMT_MAX_DIM], bb_hi[MPFMT_MAX_DIM];
-    void* bb_dev = nullptr;              // mpfmt_upload_samples_device: per-block partial boxes, and their pinned host mirror
-    void* bb_host = nullptr;
+    mpfmt_dbuf<void> bb_dev;              // mpfmt_upload_samples_device: per-block partial boxes, and their pinned host mirror
+    mpfmt_hbuf<void> bb_host;
 
     // ---- cell grid for radius grid_r --------------------------------------------------------------
     double grid_r = -1.0;
     mpfmt_grid grid;
     int64_t ntiles = 0;                  // ceil(N/64)
-    int32_t* perm = nullptr;             // [ntiles*64] sorted position -> original index (pad = -1)
-    int32_t* iperm = nullptr;            // [N] original index -> sorted position
-    uint32_t* cellkey = nullptr;         // [N] cell id of each sorted position
+    mpfmt_dbuf<int32_t> perm;             // [ntiles*64] sorted position -> original index (pad = -1)
+    mpfmt_dbuf<int32_t> iperm;            // [N] original index -> sorted position
+    mpfmt_dbuf<uint32_t> cellkey;         // [N] cell id of each sorted position
     // one arena, one fill per index build: cellstart [ncells + 1] (the cells' counters, scanned in place) | list_max (longest chunk list,
     // k_chunk_lists) | tileneed [ntiles] bytes
-    void* idx_arena = nullptr;
-    int32_t* cellstart = nullptr;        // [ncells+1] (inside idx_arena)
-    int32_t* list_max = nullptr;         // (inside idx_arena)
-    int32_t* cellcnt_pad = nullptr;      // block-major ids (sharded ctx): the cell counters of the count pass, one per 64-byte line (kernels_rdisc.hip)
+    mpfmt_dbuf<void> idx_arena;
+    int32_t* cellstart = nullptr;        // view: [ncells+1] (inside idx_arena)
+    int32_t* list_max = nullptr;         // view: (inside idx_arena)
+    mpfmt_dbuf<int32_t> cellcnt_pad;      // block-major ids (sharded ctx): the cell counters of the count pass, one per 64-byte line (kernels_rdisc.hip)
     bool list_max_clean = false;         // zeroed by the index build's fill and not written since
     // sharded ctx on the matrix-core path: only the tiles this rank reads are built -- its own and the halo (the tiles of the cells next
     // to its own cells); tileneed [ntiles] marks them (nullptr: the index is whole)
-    uint8_t* tileneed = nullptr;
-    uint8_t* tileneed_buf = nullptr;     // (inside idx_arena)
+    uint8_t* tileneed = nullptr;         // view: tileneed_buf or nullptr
+    uint8_t* tileneed_buf = nullptr;     // view: (inside idx_arena)
     int32_t index_halo = 1;              // option: allow the shard + halo index
     int32_t shard_blocks = 1;            // option: block-major cell ids on a sharded ctx (0: row-major -- shards are slabs; measurements)
     int index_rank = 0, index_world = 1; // the shard the index was built for
     std::vector<double> cut_frac;        // shard boundaries as fractions of the cell-sorted order (cut_key: the geometry they belong to)
     std::vector<int64_t> cut_key;
-    double* Xt = nullptr;                // [ntiles][d][64] tiled SoA, cell-sorted, NaN padded
-    double* tile_lo = nullptr;           // [ntiles][d] tight bounding box of each tile
-    double* tile_hi = nullptr;
-    double* tile_sub = nullptr;          // [ntiles][4][d] two sub-boxes per tile (k_tile_bbox)
-    float* tile_sub32 = nullptr;         // the same boxes in fp32, rounded outward: the candidate side of the chunk-list test (half the bytes)
+    mpfmt_dbuf<double> Xt;                // [ntiles][d][64] tiled SoA, cell-sorted, NaN padded
+    mpfmt_dbuf<double> tile_lo;           // [ntiles][d] tight bounding box of each tile
+    mpfmt_dbuf<double> tile_hi;
+    mpfmt_dbuf<double> tile_sub;          // [ntiles][4][d] two sub-boxes per tile (k_tile_bbox)
+    mpfmt_dbuf<float> tile_sub32;         // the same boxes in fp32, rounded outward: the candidate side of the chunk-list test (half the bytes)
 
     // ---- r-disc graph (device resident) ------------------------------------------------------------
     double graph_r = -1.0;
     bool graph_counted = false, graph_filled = false;
     int32_t S = 1;                       // candidate slices per tile
     int64_t tile_begin = 0, tile_end = 0;  // shard tile range
-    int32_t* slice_cnt = nullptr;        // [S][ntiles*64] hits per (slice, sorted query)
-    int64_t* deg = nullptr;              // [N+1] degree by original index
-    int64_t* degs = nullptr;             // [npad+1] degree by sorted position
-    int64_t* tptr = nullptr;             // [npad+1] offsets of the sorted-order staging CSC (rowtmp/valtmp)
+    mpfmt_dbuf<int32_t> slice_cnt;        // [S][ntiles*64] hits per (slice, sorted query)
+    mpfmt_dbuf<int64_t> deg;              // [N+1] degree by original index
+    mpfmt_dbuf<int64_t> degs;             // [npad+1] degree by sorted position
+    mpfmt_dbuf<int64_t> tptr;             // [npad+1] offsets of the sorted-order staging CSC (rowtmp/valtmp)
     bool tptr_valid = false;             // tptr holds the scan of the counted graph's degs (the single-pass build leaves it undone)
     // MFMA filter path (kernels_rdisc_mfma.hip)
-    double* Xs = nullptr;                // [npad][d] cell-sorted AoS fp64 (NaN padded): exact refine gathers
-    void* ops = nullptr;                 // [npad] 16 fp16 slots (32 B) per sorted sample: MFMA operands
+    mpfmt_dbuf<double> Xs;                // [npad][d] cell-sorted AoS fp64 (NaN padded): exact refine gathers
+    mpfmt_dbuf<void> ops;                 // [npad] 16 fp16 slots (32 B) per sorted sample: MFMA operands
     double mf_scale = 1.0;
     double ops_r = -1.0;                 // grid radius the operands were built for
     int32_t rdisc_path = 0;              // 0 auto, 1 exact fp64 VALU kernel, 2 MFMA filter + exact refine
     int32_t rdisc_path_used = 0;
     bool filter_valu = false;            // the counted graph's pair kernel ran the exact fp64 filter on the vector ALUs (k_rdisc_vf_w4) instead of the fp16 matrix-core one
-    int32_t lists_wide = -1;             // (fixed; was an option until the A/B was settled) chunk lists built by four wavefronts per tile on small shards, one elsewhere
     int32_t cell_fb_max = 8;             // position bits inside a cell that the sort key carries (k_cellkey)
     int64_t mf_tail_min_items = 32768;   // ... in launches of at least this many items (smaller ones do not fill the chip: nothing to even out)
-    int32_t* ord_ctr = nullptr;          // [8] inside the counter arena: the ordering kernel's per-XCD quarter counters (zeroed with the arena)
     int32_t ord_draw = 1;                // option: 1 = the ordering kernel's workgroups draw their quarters when those are long (>= 1536 records on average), 2 = always, 0 = every nb-th quarter each
     int32_t mf_tail_permille = 80, mf_tail_slices = 9;      // options: the last tiles of a single-pass pair-kernel launch are cut into this many slices (0: off)
     int32_t mf_xcd_mode = -1;            // work items go to the XCDs in interleaved groups of this many; -1: 256 for launches of >= 32768 items, else 64
                                          // (north star: groups of 64 2.02 ms / 5.6 GB of counter traffic, 256 2.04 / 4.6, 512 2.05 / 4.4; one range per XCD 2.41 ms)
     int32_t num_cus = 256;               // compute units of the device (persistent-grid sizing)
     int ord_per_cu = 0;          // k_order_logs: resident workgroups per CU on THIS ctx's device
-    int* sweep_ctr = nullptr;            // graph sweep: one task counter per obstacle chunk
+    mpfmt_dbuf<int> sweep_ctr;            // graph sweep: one task counter per obstacle chunk
     int32_t sweep_rounds = 1;            // option: round-table sweep (k_graph_sweep_rt) where it applies (d <= 8, M <= 256)
-    int64_t* rt_cnt = nullptr;           // [columns visited + 1] rounds per column, then (scan) first round of each column
-    int64_t* rt_off = nullptr;
-    void* rt_tmp = nullptr;              // scan temporary
-    void* rt_table = nullptr;            // [rounds] (column, entries | first << 31, first entry) in visiting order
-    int64_t* rt_total = nullptr;         // device: number of rounds
-    double* rt_ss = nullptr;             // device copy of the state-space bounds (lo[MAX_DIM], hi[MAX_DIM]) for scalar loads
+    mpfmt_dbuf<int64_t> rt_cnt;           // [columns visited + 1] rounds per column, then (scan) first round of each column
+    mpfmt_dbuf<int64_t> rt_off;
+    mpfmt_dbuf<void> rt_tmp;              // scan temporary
+    mpfmt_dbuf<void> rt_table;            // [rounds] (column, entries | first << 31, first entry) in visiting order
+    mpfmt_dbuf<int64_t> rt_total;         // device: number of rounds
+    mpfmt_dbuf<double> rt_ss;             // device copy of the state-space bounds (lo[MAX_DIM], hi[MAX_DIM]) for scalar loads
     mpfmt_ss rt_ss_host;                 // what rt_ss holds
     bool rt_ss_valid = false;
     // "every sample lies in the state space" for (samples_epoch, ss): the sweep then skips the per-row in_state_space test
     int64_t samples_epoch = 0, ssflag_epoch = -1;
     mpfmt_ss ssflag_ss;
     bool ssflag_all_in = false;
-    int32_t* ssflag_dev = nullptr;
+    mpfmt_dbuf<int32_t> ssflag_dev;
     int64_t mf_target_items = 40000;     // work items (tile x slice) the MFMA path aims for (tools/run_shard_sweep_items.py: flat from 40k up at 1 shard, best at 2 and 4)
     float mf_negT = 0.f;
-    void* lists = nullptr;               // [shard tiles][list_cap] candidate chunk ids per tile
-    int32_t* list_len = nullptr;         // [shard tiles + 1] lengths, last = max
-    void* lists_stage = nullptr;         // small shards with long lists: [tiles][4][list_cap] staging of the 4-wavefront list kernel
+    mpfmt_dbuf<void> lists;               // [shard tiles][list_cap] candidate chunk ids per tile
+    mpfmt_dbuf<int32_t> list_len;         // [shard tiles + 1] lengths, last = max
+    mpfmt_dbuf<void> lists_stage;         // small shards with long lists: [tiles][4][list_cap] staging of the 4-wavefront list kernel
     int64_t list_cap = 0;
     double lists_r = -1.0; int64_t lists_begin = -1, lists_end = -1;
     // single-pass hit pool (MFMA path): hits found by the count pass are kept, so the fill pass is a scatter
     int32_t use_pool = 1;                // option "rdisc_pool"
-    int32_t* pool_flag = nullptr;        // overflow flag
     int64_t qcap = 0;                    // capacity of one quarter log, in records (a multiple of 16)
-    uint32_t* qkey = nullptr;            // [quarter tiles of the shard][qcap] record keys: row sample index | column within the quarter << 26 | flags
-    double* qd2 = nullptr;               // [quarter tiles of the shard][qcap] squared distances
-    int32_t* qlen = nullptr;             // [quarter tiles of the shard] the logs' cursors
+    mpfmt_dbuf<uint32_t> qkey;            // [quarter tiles of the shard][qcap] record keys: row sample index | column within the quarter << 26 | flags
+    mpfmt_dbuf<double> qd2;               // [quarter tiles of the shard][qcap] squared distances
     const double* st_C = nullptr; const uint64_t* st_H = nullptr; int st_free = 0;      // streaming mode (mpfmt_rdisc_stream): inputs of the launch in flight
-    void* st_best = nullptr; int32_t* st_besti = nullptr; int32_t* st_nfree = nullptr;  //   and its per-slice partials [S][npad]
-    void* smask = nullptr;               // [npad] per-sample obstacle masks (k_sample_masks): the drain's broad phase walks the boxes in (mask_q & mask_c) only
+    mpfmt_dbuf<void> st_best; mpfmt_dbuf<int32_t> st_besti, st_nfree;                    //   and its per-slice partials [S][npad]
+    mpfmt_dbuf<void> smask;               // [npad] per-sample obstacle masks (k_sample_masks): the drain's broad phase walks the boxes in (mask_q & mask_c) only
     int64_t pool_hint_qmax = 0;          // records in the fullest quarter (16 consecutive cell-sorted columns) of the last build: sizes the next one's logs
     // half build of the single-pass r-disc graph (kernels_rdisc_mfma.hip: every pair found once, the other column's record goes
     // to a foreign log of that column's tile)
     int use_half = 1;                    // option rdisc_half
     int fuse_broad = 2;                  // option: broad phase of the edge tests in the half build's drain (step APIs only)
-    void* pend_items = nullptr;          // [segments][pend_wcap] (entry, column sample, row position) of the entries that need an exact test
+    mpfmt_dbuf<void> pend_items;          // [segments][pend_wcap] (entry, column sample, row position) of the entries that need an exact test
     int64_t pend_wcap = 0;
-    int32_t* pend_cnt = nullptr;         // [segments] items per segment, then the overflow flag
-    int32_t* pend_over = nullptr;
+    mpfmt_dbuf<int32_t> pend_cnt;         // [segments] items per segment, then the overflow flag
+    int32_t* pend_over = nullptr;        // view: behind pend_cnt's segments
     int pend_nseg = 0;
     bool sweep_pending_used = false;     // the last graph sweep visited the pending list only
     bool pend_overflowed = false;        // read back behind the speculative step's synchronisation
     bool pend_valid = false;             // the resident graph has its pending list (made by this step's ordering pass)
-    void* pair_items = nullptr;          // fuse_broad = 2: [items][pair_icap] 32-byte pending-pair items (k_exact_pairs)
-    int32_t* pair_cnt = nullptr;         // [items], then the overflow flag
-    int32_t* pair_over = nullptr;
+    mpfmt_dbuf<void> pair_items;          // fuse_broad = 2: [items][pair_icap] 32-byte pending-pair items (k_exact_pairs)
     int64_t pair_icap = 0;
     int pair_slack = 1;                  // doubled (to 8) by a step whose pending-pair list overflowed
     bool sweep_in_order = false;         // the mask of the resident graph was written by the ordering pass (form 2)
@@ -236,79 +292,83 @@ struct mpfmt_ctx {
     bool spec_ready = false;             // the previous build of the same (N, r, shard) went through the single-pass pool path
     bool spec_lists = false;             // chunk lists of the pending count were built without reading back their maximum
     bool cnt_pool = false, cnt_mf = false;   // the pending count used the pool / the MFMA pair kernel
-    int32_t* spec_fail = nullptr;        // device flag: pool overflow, truncated chunk list or nnz beyond the trusted capacity
+    mpfmt_dbuf<int32_t> spec_fail;        // device flag: pool overflow, truncated chunk list or nnz beyond the trusted capacity
     int64_t nnz_cap = 0;                 // entries rowval / nzval / the mask are sized for
-    void* rb_dev = nullptr;              // count read-back block (device) and its pinned host mirror
-    void* rb_host = nullptr;
+    mpfmt_dbuf<void> rb_dev;              // count read-back block (device) and its pinned host mirror
+    mpfmt_hbuf<void> rb_host;
     int64_t lists_cap_trusted = -1;      // list capacity that a verified build found sufficient
     int64_t pool_hint_N = -1; double pool_hint_r = -1.0; int64_t pool_hint_nnz = 0; int64_t pool_hint_maxdeg = 0; int pool_hint_rank = -1, pool_hint_world = -1;   // capacity hint from the last build
     int64_t survivors = 0;
-    int64_t* colptr = nullptr;           // [N+1] 0-based offsets by original index
+    mpfmt_dbuf<int64_t> colptr;           // [N+1] 0-based offsets by original index
     int64_t nnz = 0;
-    int32_t* rowtmp = nullptr;           // [nnz] unsorted fill
-    double* valtmp = nullptr;
-    int32_t* rowval = nullptr;           // [nnz] 0-based, ascending per column
-    double* nzval = nullptr;
-    int32_t* rowpos = nullptr;           // [nnz] cell-sorted position of each entry's row (single-pass build): the sweep gathers rows from Xs
+    mpfmt_dbuf<int32_t> rowtmp;           // [nnz] unsorted fill
+    mpfmt_dbuf<double> valtmp;
+    mpfmt_dbuf<int32_t> rowval;           // [nnz] 0-based, ascending per column
+    mpfmt_dbuf<double> nzval;
+    mpfmt_dbuf<int32_t> rowpos;           // [nnz] cell-sorted position of each entry's row (single-pass build): the sweep gathers rows from Xs
     bool rowpos_valid = false;
-    int32_t sweep_sorted = 1;            // (fixed; was an option until the A/B was settled) gather the sweep's rows from Xs in cell-sorted order with per-XCD task ranges (6x less HBM traffic,
-                                         // 74 % L2 hits): with the round-table sweep, whose instruction count no longer hides under the
-                                         // caller-order gather (2.29 ms floor), this is the faster mode (2.2 vs 2.65 ms); on by default
-    uint64_t* graph_free = nullptr;      // [ceil(nnz/64)]
+    mpfmt_dbuf<uint64_t> graph_free;      // [ceil(nnz/64)]
     bool graph_swept = false;
-    size_t zarena_bytes = 0;
     bool deg_zero_valid = false;         // sharded ctx: deg[] is all zeros (the ordering pass cleared what the last step wrote)
-    void* zarena = nullptr;              // one arena for d_pairs, pool_flag, pair_cnt (one fill per build); they point into it when it exists
-    unsigned long long* d_pairs = nullptr;   // device counter: candidate pairs tested
+    // The small per-build counters.  Each is a VIEW: into zarena (one arena, one fill per build) when the ctx has one, else into the
+    // _own buffer beside it (a ctx whose counters were first allocated one by one -- by the steering spaces' builds -- keeps them
+    // and their separate fills).  Views are never freed; zarena and the _own buffers always are.
+    mpfmt_dbuf<void> zarena;
+    mpfmt_dbuf<unsigned long long> d_pairs_own;
+    mpfmt_dbuf<int32_t> pool_flag_own, pair_cnt_own, qlen_own;
+    unsigned long long* d_pairs = nullptr;   // view: [514] candidate pairs tested (512 sharded counters), longest column, fullest quarter
+    int32_t* pool_flag = nullptr;        // view: the logs' overflow flag
+    int32_t* pair_cnt = nullptr;         // view: [items] pending pairs per item, then the overflow flag
+    int32_t* pair_over = nullptr;        // view: pair_cnt + 1024
+    int32_t* qlen = nullptr;             // view: [quarter tiles of the shard] the logs' cursors
+    int32_t* ord_ctr = nullptr;          // view: [8] the ordering kernel's per-XCD quarter counters (arena only)
     int64_t pairs_tested = 0;
 
     // ---- k-nearest graph (kernels_knn.hip): installed in colptr / rowval / nzval like an r-disc graph, graph_r = its longest entry ----
     int64_t knn_k = 0;                   // > 0 with graph_filled: the resident graph is the k-nearest one of this k (never "a filled graph of radius graph_r")
-    uint64_t* knn_mutual = nullptr;      // [ceil(nnz/64)] mutual bit per entry (row y in column x: x in knn(y))
-    double* knn_st = nullptr;            // [2][supertiles][d] boxes of 64 consecutive tiles
-    void* knn_bitmap = nullptr;          // [workgroups][ceil(N/64)] selection bitmaps
-    void* knn_lists = nullptr;           // the rounds' short-column lists and counters
+    mpfmt_dbuf<uint64_t> knn_mutual;      // [ceil(nnz/64)] mutual bit per entry (row y in column x: x in knn(y))
+    mpfmt_dbuf<double> knn_st;            // [2][supertiles][d] boxes of 64 consecutive tiles
+    mpfmt_dbuf<void> knn_bitmap;          // [workgroups][ceil(N/64)] selection bitmaps
+    mpfmt_dbuf<void> knn_lists;           // the rounds' short-column lists and counters
     int64_t knn_pairs = 0, knn_rounds = 0, knn_short = 0, knn_scan = 0;      // stats of the last build
 
     // ---- steering graphs (double integrator, Dubins, Reeds-Shepp): share colptr / rowval / nzval / graph_free ---------------
     mpfmt_steer steer_kind = MPFMT_STEER_DI;     // which steering graph the steer_* state describes
     double steer_r = 0.0;                // cost radius of the built graph
     bool steer_counted = false, steer_filled = false, steer_swept = false;
-    uint8_t* steer_nseg = nullptr;       // [nnz] workspace segment tests the reference would have made per edge
+    mpfmt_dbuf<uint8_t> steer_nseg;       // [nnz] workspace segment tests the reference would have made per edge
     int32_t di_S = 1;
     double di_rho = 1.0;
-    int32_t* di_pool_i = nullptr; double* di_pool_c = nullptr; double* di_pool_t = nullptr;   // DI single-pass slot lists
+    mpfmt_dbuf<int32_t> di_pool_i; mpfmt_dbuf<double> di_pool_c, di_pool_t;                   // DI single-pass slot lists
     int64_t di_pool_cap = 0; bool di_pool_valid = false;
-    void* di_ops = nullptr;              // matrix-core prefilter of the double-integrator build (kernels_di_mfma.hip): target- and source-role operands
+    mpfmt_dbuf<void> di_ops;              // matrix-core prefilter of the double-integrator build (kernels_di_mfma.hip): target- and source-role operands
     bool di_mf = false; float di_negT = 0.f;     // the counted DI graph went through it; its threshold
     int32_t di_path = 0;                 // option: 0 auto, 1 vector-ALU candidate test, 2 matrix-core prefilter
     double car_rt = 1.0, car_sp = 1.0;   // Dubins turning radius / speed of the built graph
-    uint64_t* car_keep = nullptr;        // keep bits over the candidate (positions) graph
+    mpfmt_dbuf<uint64_t> car_keep;        // keep bits over the candidate (positions) graph
     mpfmt_ctx* aux = nullptr;            // helper ctx: Euclidean r-disc graph of the positions (Dubins build)
-    double* tvaltmp = nullptr;           // [nnz] optimal times, unsorted staging
-    double* tval = nullptr;              // [nnz] optimal times t* per entry
+    mpfmt_dbuf<double> tvaltmp;           // [nnz] optimal times, unsorted staging
+    mpfmt_dbuf<double> tval;              // [nnz] optimal times t* per entry
 
     // ---- obstacles -----------------------------------------------------------------------------
-    double* boxes = nullptr;             // [M][2][dw]
+    mpfmt_dbuf<double> boxes;             // [M][2][dw]
     std::vector<double> boxes_host;      // the same on the host
     int32_t M = 0, dw = 0;
     bool have_boxes = false;
     int32_t cc_kind = 0;                 // collision checker: 0 = PointRobotNDBoxes, 1 = PointRobot2D (SAT)
-    mpfmt_shape2d* shapes2d = nullptr;   // [M] when cc_kind == 1
+    mpfmt_dbuf<mpfmt_shape2d> shapes2d;   // [M] when cc_kind == 1
     mpfmt_aabb2d aabb2d;                 // Compound2D bounding box
     mpfmt_ss ss;
 
     // ---- scratch -------------------------------------------------------------------------------
-    void* scratch = nullptr;
-    size_t scratch_bytes = 0;
-    std::map<void*, size_t> caps;       // capacity (bytes) of each grow-only device buffer, keyed by member address
+    mpfmt_dbuf<void> scratch;
     std::map<std::string, mpfmt_timer> timers;
-    void* timer_state = nullptr;         // HIP-event timing records of this ctx (mpfmt_capi.hip)
+    mpfmt_timer_state* timer_state = nullptr;      // HIP-event timing records of this ctx (mpfmt_capi.hip)
     bool timing_enabled = true;
     bool rebuild_index = false;          // option "rebuild_index": graph_build_device rebuilds the cell grid every call
 
     // ---- multi-GPU exchange (mpfmt_comm.hip) and the device-resident wavefront FMT* driver (kernels_wavefront.hip) ----
-    void* comm = nullptr;                // mpfmt_comm: RCCL communicator + communication stream of this ctx
+    mpfmt_comm* comm = nullptr;          // RCCL communicator + communication stream of this ctx
     int32_t step_state = 0; double step_r = 0.0;   // graph_step_launch / _finish: 0 none, 1 speculative kernels in flight, 2 complete
     int32_t wf_graphs = 0;               // option (off: measured, no gain -- the solve is bound by k_wf_connect, 3.2 of 5.4 ms, not by launches): replay a captured
                                          // hipGraph of a group of 8 steps instead of launching its ~48 kernels
@@ -317,15 +377,15 @@ struct mpfmt_ctx {
     int64_t wf_seen_epoch = -1; double wf_seen_r = -1.0; int64_t wf_seen_nnz = -1;      // the graph the last device solve ran on
     int32_t wf_pos_used = 0;             // stat: the last device solve gathered by position
     int32_t wf_force_sharded = 0;        // option: run the sharded form of the wavefront step (own-column marking, triples, exchange) at world = 1
-    void* wf = nullptr;                  // mpfmt_wf: W / H / C / A and the batch lists of a running wavefront solve
+    mpfmt_wf* wf = nullptr;              // W / H / C / A and the batch lists of a running wavefront solve
 
     // ---- PRM* shortest-path field (kernels_sssp.hip): labels, parents, the three changed-sample bitmaps, round state, point bitmap ----
-    double* sssp_C = nullptr;            // [N]
-    int64_t* sssp_A = nullptr;           // [N] 1-based parents
-    uint64_t* sssp_bm = nullptr;         // [3][ceil(N/64)]
-    void* sssp_state = nullptr;          // sssp_state (device) and its pinned host mirror
-    void* sssp_state_host = nullptr;
-    uint64_t* sssp_F = nullptr;          // [ceil(N/64)] checkpts bitmap of the call
+    mpfmt_dbuf<double> sssp_C;            // [N]
+    mpfmt_dbuf<int64_t> sssp_A;           // [N] 1-based parents
+    mpfmt_dbuf<uint64_t> sssp_bm;         // [3][ceil(N/64)]
+    mpfmt_dbuf<void> sssp_state;          // sssp_state (device) and its pinned host mirror
+    mpfmt_hbuf<void> sssp_state_host;
+    mpfmt_dbuf<uint64_t> sssp_F;          // [ceil(N/64)] checkpts bitmap of the call
     hipEvent_t sssp_ev[2] = {nullptr, nullptr};
     int64_t sssp_rounds = 0, sssp_relax = 0, sssp_reached = 0;      // stats of the last source
 
@@ -334,7 +394,6 @@ struct mpfmt_ctx {
 };
 
 // error helpers ---------------------------------------------------------------------------------
-int32_t mpfmt_fail(mpfmt_ctx* ctx, int32_t code, const char* fmt, ...);
 #define HIPCHK(ctx, call)                                                                          \
     do {                                                                                           \
         hipError_t e_ = (call);                                                                    \
@@ -344,10 +403,23 @@ int32_t mpfmt_fail(mpfmt_ctx* ctx, int32_t code, const char* fmt, ...);
     } while (0)
 
 int32_t mpfmt_scratch(mpfmt_ctx* ctx, size_t bytes, void** out);
+// a ctx without the counter arena: the pair counters / the logs' overflow flag as allocations of their own, made once
+inline int32_t mpfmt_own_pairs(mpfmt_ctx* ctx)
+{
+    if (ctx->d_pairs) return MPFMT_OK;
+    const int32_t rc = ctx->d_pairs_own.ensure(ctx, 514 * sizeof(unsigned long long));      // (512 pair counters + the Euclidean build's longest-column word + the fullest quarter: one size everywhere)
+    ctx->d_pairs = ctx->d_pairs_own;
+    return rc;
+}
+inline int32_t mpfmt_own_pool_flag(mpfmt_ctx* ctx)
+{
+    if (ctx->pool_flag) return MPFMT_OK;
+    const int32_t rc = ctx->pool_flag_own.ensure(ctx, sizeof(int32_t));
+    ctx->pool_flag = ctx->pool_flag_own;
+    return rc;
+}
 // the samples on the host (X: [N][d]) and their first k coordinates (P: [N][k], the workspace points of steering-space states)
 int32_t mpfmt_states_host(mpfmt_ctx* ctx, int k, std::vector<double>& X, std::vector<double>& P);
-// grow-only device buffer: (re)allocates *p when it is smaller than bytes
-int32_t mpfmt_ensure(mpfmt_ctx* ctx, void** p, size_t bytes);
 void mpfmt_time_begin(mpfmt_ctx* ctx);
 void mpfmt_time_end(mpfmt_ctx* ctx, const char* name);
 void mpfmt_time_abandon(mpfmt_ctx* ctx);
