@@ -93,6 +93,21 @@ MPFMT_API int32_t mpfmt_upload_samples_device(mpfmt_ctx* ctx, const double* dX, 
  *      dw = workspace dimension (Identity s2w: dw == d). ------------------------------------------- */
 MPFMT_API int32_t mpfmt_upload_boxes(mpfmt_ctx* ctx, const double* lohi, int32_t M, int32_t dw,
                            const double* ss_lo, const double* ss_hi, int32_t d_state);
+/* addobstacle / addblocker (boxesND.jl, robots2D.jl:23-24) on the ctx's PointRobotNDBoxes set, in place.  After either call the
+ * ctx is what mpfmt_upload_boxes with the resulting list (same dw, same state-space bounds) leaves, except that the free-edge
+ * mask of a swept, unsharded resident graph (r-disc, imported or k-nearest) is brought up to date on the ctx's stream instead
+ * of being thrown away: adding boxes only clears bits (new = old AND free against the added boxes), removing one only sets
+ * bits of blocked entries whose segment box meets it (tested again against what remains).  The mask is the one a whole sweep
+ * of the resulting list writes, bit for bit.  In every other state (no swept mask, a sharded ctx, a steering graph) the list
+ * is edited and the mask invalidated, as mpfmt_upload_boxes does.  The steering spaces' masks are always re-swept.
+ *   mpfmt_boxes_add:    lohi [M_add][2][dw] (the ctx's dw), appended behind the current boxes.
+ *   mpfmt_boxes_remove: ids 1-based, distinct; the remaining boxes keep their order.
+ * Refused, leaving the ctx as it was: NULL with a positive count, an id out of range or repeated (MPFMT_ERR_ARG); no box set
+ * uploaded, or the 2-D SAT world (MPFMT_ERR_STATE).  A count of 0 succeeds and does nothing.
+ * mpfmt_get_stat: "boxes_delta_path" (1 in place, 0 invalidated), "boxes_delta_columns" (columns whose entries were read),
+ * "boxes_delta_entries" (entries that reached an exact test); timing key "boxes_delta". */
+MPFMT_API int32_t mpfmt_boxes_add(mpfmt_ctx* ctx, const double* lohi, int32_t M_add);
+MPFMT_API int32_t mpfmt_boxes_remove(mpfmt_ctx* ctx, const int64_t* ids, int32_t n_ids);
 
 /* ---- r-disc neighbour graph = ImmutableNNC(D::SparseMatrixCSC, r) (src/nearneighbors.jl:23-27):
  *      column v = inball(V, dist, DS, v, r) (src/nearneighbors.jl:179-183) for every v.

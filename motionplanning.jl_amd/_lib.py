@@ -65,6 +65,8 @@ SYMBOLS = [
     ("mpfmt_upload_samples", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, C.c_int32]),
     ("mpfmt_upload_samples_device", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     ("mpfmt_upload_boxes", C.c_int32, [C.c_void_p, c_d_p, C.c_int32, C.c_int32, c_d_p, c_d_p, C.c_int32]),
+    ("mpfmt_boxes_add", C.c_int32, [C.c_void_p, c_d_p, C.c_int32]),
+    ("mpfmt_boxes_remove", C.c_int32, [C.c_void_p, c_i64_p, C.c_int32]),
     ("mpfmt_rdisc_count", C.c_int32, [C.c_void_p, C.c_double, c_i64_p, c_i64_p]),
     ("mpfmt_rdisc_fill", C.c_int32, [C.c_void_p, c_i64_p, c_d_p]),
     ("mpfmt_rdisc_query", C.c_int32, [C.c_void_p, C.c_int64, C.c_double, c_i64_p, c_d_p, C.c_int64, c_i64_p]),
@@ -342,6 +344,7 @@ class Context:
         self.d = 0
         self.dw = 0
         self.nnz = None
+        self._cc_epoch = 0                                   # counts the changes of the collision checker (what a bound checker compares)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -371,6 +374,7 @@ class Context:
     def set_state_bounds(self, ss_lo, ss_hi):
         """BoundedStateSpace lo / hi of any state dimension (after upload_shapes2d: the bounds of a steering space over the 2-D world)."""
         lo = np.ascontiguousarray(ss_lo, dtype=np.float64); hi = np.ascontiguousarray(ss_hi, dtype=np.float64)
+        self._cc_epoch += 1
         self._chk(self._L.mpfmt_set_state_bounds(self._h, _dp(lo), _dp(hi), len(lo)))
 
     def set_shard(self, rank, world):
@@ -404,8 +408,30 @@ class Context:
         lo = None if ss_lo is None else np.ascontiguousarray(ss_lo, dtype=np.float64)
         hi = None if ss_hi is None else np.ascontiguousarray(ss_hi, dtype=np.float64)
         ds = 0 if lo is None else lo.size
+        self._cc_epoch += 1
         self._chk(self._L.mpfmt_upload_boxes(self._h, _dp(lohi), M, dw, _dp(lo), _dp(hi), ds))
         self.dw = dw
+
+    def boxes_add(self, lohi):
+        """Append boxes lohi (M_add, 2, dw) to the uploaded PointRobotNDBoxes set in place (mpfmt_boxes_add): the free-edge mask of a
+        swept resident graph is brought up to date instead of being thrown away (stat("boxes_delta_path") == 1)."""
+        lohi = np.ascontiguousarray(lohi, dtype=np.float64)
+        if lohi.size == 0:
+            lohi = np.zeros((0, 2, self.dw))
+        if lohi.ndim == 2:
+            lohi = lohi[None]
+        if lohi.ndim != 3 or lohi.shape[1] != 2:
+            raise ValueError("lohi must be (M_add, 2, dw)")
+        if lohi.shape[0] > 0 and lohi.shape[2] != self.dw:
+            raise ValueError("boxes of dimension %d added to a set of dimension %d" % (lohi.shape[2], self.dw))
+        self._chk(self._L.mpfmt_boxes_add(self._h, _dp(lohi), lohi.shape[0]))
+        self._cc_epoch += 1
+
+    def boxes_remove(self, ids):
+        """Remove the boxes `ids` (1-based, distinct) from the uploaded set in place (mpfmt_boxes_remove); the others keep their order."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int64)
+        self._chk(self._L.mpfmt_boxes_remove(self._h, _ip(ids), ids.size))
+        self._cc_epoch += 1
 
     def upload_shapes2d(self, shapes, ss_lo=None, ss_hi=None):
         """2-D SAT world: shapes = [("circle", (cx, cy), r) | ("polygon", [(x, y), ...]), ...] (a flat Compound2D)."""
@@ -417,6 +443,7 @@ class Context:
         lo = None if ss_lo is None else np.ascontiguousarray(ss_lo, dtype=np.float64)
         hi = None if ss_hi is None else np.ascontiguousarray(ss_hi, dtype=np.float64)
         i32 = C.POINTER(C.c_int32)
+        self._cc_epoch += 1
         self._chk(self._L.mpfmt_upload_shapes2d(self._h, len(shapes), kinds.ctypes.data_as(i32), nv.ctypes.data_as(i32), _dp(data),
                                                 None if lo is None else _dp(lo), None if hi is None else _dp(hi)))
         self.dw = 2

@@ -389,6 +389,88 @@ int32_t mpfmt_upload_boxes(mpfmt_ctx* ctx, const double* lohi, int32_t M, int32_
     return MPFMT_OK;
 }
 
+// ---- in-place edits of the box list (kernels_boxdelta.hip) ----------------------------------------------------------------------
+// the resident mask can be brought up to date instead of being thrown away
+static bool boxes_delta_in_place(const mpfmt_ctx* ctx)
+{
+    return ctx->world == 1 && ctx->cc_kind == 0 && ctx->dw == ctx->d && ctx->graph_filled && ctx->graph_swept && ctx->nnz > 0 &&
+           ctx->graph_free && ctx->step_state != 1;
+}
+
+// the list has been edited: the mask follows in place (delta = the boxes added or a copy of those removed) or goes stale
+static int32_t boxes_delta_finish(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove)
+{
+    ctx->bd_columns = ctx->bd_entries = 0;
+    ctx->pend_valid = false;                                 // (a pending list belongs to the obstacle set it was made against)
+    ctx->steer_swept = false;
+    ctx->bd_path = boxes_delta_in_place(ctx) ? 1 : 0;
+    if (!ctx->bd_path) { ctx->graph_swept = false; return MPFMT_OK; }
+    const int32_t rc = mpfmt_boxdelta_apply(ctx, d_delta, nd, remove);
+    if (rc) { ctx->graph_swept = false; ctx->bd_path = 0; }   // (the list stands, the mask is swept again)
+    return rc;
+}
+
+int32_t mpfmt_boxes_add(mpfmt_ctx* ctx, const double* lohi, int32_t M_add)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (M_add < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "M_add = %d < 0", M_add);
+    if (M_add > 0 && !lohi) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "lohi is NULL");
+    if (!ctx->have_boxes || ctx->cc_kind != 0)
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, "boxes are added to a PointRobotNDBoxes set (mpfmt_upload_boxes), not to the 2-D SAT world");
+    if (M_add == 0) return MPFMT_OK;
+    if ((int64_t)ctx->M + M_add > INT32_MAX) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "more than 2^31 - 1 boxes");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t per = (size_t)2 * ctx->dw, old_n = (size_t)ctx->M * per, add_n = (size_t)M_add * per;
+    int32_t rc;
+    mpfmt_dbuf<double> nb;                                   // the new list beside the old one: a failure leaves the ctx as it was
+    if ((rc = nb.ensure(ctx, sizeof(double) * (old_n + add_n)))) return rc;
+    if (old_n) HIPCHK(ctx, hipMemcpyAsync(nb, ctx->boxes, sizeof(double) * old_n, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(nb.get() + old_n, lohi, sizeof(double) * add_n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->boxes_host.reserve(old_n + add_n);
+    ctx->boxes_host.insert(ctx->boxes_host.end(), lohi, lohi + add_n);
+    ctx->boxes.swap(nb);
+    ctx->M += M_add;
+    return boxes_delta_finish(ctx, ctx->boxes.get() + old_n, M_add, false);
+}
+
+int32_t mpfmt_boxes_remove(mpfmt_ctx* ctx, const int64_t* ids, int32_t n_ids)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (n_ids < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "n_ids = %d < 0", n_ids);
+    if (n_ids > 0 && !ids) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "ids is NULL");
+    if (!ctx->have_boxes || ctx->cc_kind != 0)
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, "boxes are removed from a PointRobotNDBoxes set (mpfmt_upload_boxes), not from the 2-D SAT world");
+    const int32_t M = ctx->M;
+    std::vector<char> out((size_t)std::max(M, 1), 0);
+    for (int32_t j = 0; j < n_ids; ++j) {
+        if (ids[j] < 1 || ids[j] > M) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "box id %lld out of range 1..%d", (long long)ids[j], M);
+        if (out[(size_t)(ids[j] - 1)]) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "box id %lld given twice", (long long)ids[j]);
+        out[(size_t)(ids[j] - 1)] = 1;
+    }
+    if (n_ids == 0) return MPFMT_OK;
+    if ((int64_t)ctx->boxes_host.size() != (int64_t)M * 2 * ctx->dw) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the host copy of the box list is not whole");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t per = (size_t)2 * ctx->dw;
+    std::vector<double> keep, gone;
+    keep.reserve((size_t)(M - n_ids) * per); gone.reserve((size_t)n_ids * per);
+    for (int32_t k = 0; k < M; ++k) {
+        std::vector<double>& to = out[(size_t)k] ? gone : keep;
+        to.insert(to.end(), ctx->boxes_host.begin() + (size_t)k * per, ctx->boxes_host.begin() + (size_t)(k + 1) * per);
+    }
+    int32_t rc;
+    mpfmt_dbuf<double> nb, removed;                          // the remaining list beside the old one; a copy of what leaves, for the kernel
+    if ((rc = nb.ensure(ctx, sizeof(double) * keep.size()))) return rc;
+    if ((rc = removed.ensure(ctx, sizeof(double) * gone.size()))) return rc;
+    if (!keep.empty()) HIPCHK(ctx, hipMemcpyAsync(nb, keep.data(), sizeof(double) * keep.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(removed, gone.data(), sizeof(double) * gone.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->boxes_host.swap(keep);
+    ctx->boxes.swap(nb);
+    ctx->M = M - n_ids;
+    return boxes_delta_finish(ctx, removed, n_ids, true);    // (synchronises before `removed` goes)
+}
+
 // ---- r-disc graph ------------------------------------------------------------------------------------
 
 int32_t mpfmt_graph_build_device(mpfmt_ctx* ctx, double r, int64_t* nnz)
@@ -1920,6 +2002,11 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "sssp_reached") == 0) { *value = ctx->sssp_reached; return MPFMT_OK; }
     if (strcmp(name, "shortcut_tests_evaluated") == 0) { *value = ctx->shortcut_tests; return MPFMT_OK; }
     if (strcmp(name, "shortcut_checks") == 0) { *value = ctx->shortcut_checks; return MPFMT_OK; }
+    if (strcmp(name, "boxes_delta_path") == 0) { *value = ctx->bd_path; return MPFMT_OK; }
+    if (strcmp(name, "boxes_delta_columns") == 0) { *value = ctx->bd_columns; return MPFMT_OK; }
+    if (strcmp(name, "boxes_delta_entries") == 0) { *value = ctx->bd_entries; return MPFMT_OK; }
+    if (strcmp(name, "boxes") == 0) { *value = ctx->have_boxes ? ctx->M : 0; return MPFMT_OK; }
+    if (strcmp(name, "graph_swept") == 0) { *value = ctx->graph_swept ? 1 : 0; return MPFMT_OK; }
     if (strcmp(name, "survivors") == 0) { *value = ctx->survivors; return MPFMT_OK; }
     if (strcmp(name, "pairs_tested") == 0) { *value = ctx->pairs_tested; return MPFMT_OK; }
     if (strcmp(name, "nnz") == 0) { *value = ctx->nnz; return MPFMT_OK; }

@@ -359,6 +359,12 @@ struct mpfmt_ctx {
     mpfmt_dbuf<mpfmt_shape2d> shapes2d;   // [M] when cc_kind == 1
     mpfmt_aabb2d aabb2d;                 // Compound2D bounding box
     mpfmt_ss ss;
+    // in-place edits of the box list (mpfmt_boxes_add / _remove, kernels_boxdelta.hip): the flagged columns, their count and the
+    // entries tested (device), and the stats of the last call
+    mpfmt_dbuf<int32_t> bd_cols;          // [N]
+    mpfmt_dbuf<unsigned long long> bd_ctr; // [2] flagged columns, entries that reached an exact test
+    int32_t bd_path = 0;                 // 1: the resident mask was updated in place, 0: invalidated
+    int64_t bd_columns = 0, bd_entries = 0;
 
     // ---- scratch -------------------------------------------------------------------------------
     mpfmt_dbuf<void> scratch;
@@ -487,6 +493,9 @@ int32_t mpfmt_launch_mc_is_edges(mpfmt_ctx* ctx, const int64_t* d_src1, const in
 int32_t mpfmt_launch_mc_ais_edges(mpfmt_ctx* ctx, const int64_t* d_src1, const int64_t* d_dst1, int64_t E, double sigma, int64_t rollouts,
                                   uint64_t seed, unsigned long long* d_wsum, double* d_mu);
 int32_t mpfmt_launch_graph_sweep(mpfmt_ctx* ctx, const int32_t* spec_fail = nullptr, int64_t mask_entries = -1);
+
+// kernels_boxdelta.hip --------------------------------------------------------------------------
+int32_t mpfmt_boxdelta_apply(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove);
 
 // kernels_di.hip ----------------------------------------------------------------------------------
 #include <functional>

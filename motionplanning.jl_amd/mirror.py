@@ -123,6 +123,7 @@ class PointRobotNDBoxes:
         self.count = 0
         self._ctx = None
         self._ss = None
+        self._bound = None                   # (list and bounds as bytes, the context's checker epoch) of the last _bind
 
     def lohi(self):
         if not self.boxes:
@@ -131,13 +132,27 @@ class PointRobotNDBoxes:
 
     def _bind(self, ctx, SS):
         dw = SS.workspace_dim
-        lohi = self.lohi() if self.boxes else np.zeros((0, 2, dw))
+        lohi = np.ascontiguousarray(self.lohi() if self.boxes else np.zeros((0, 2, dw)), dtype=np.float64)
+        key = (lohi.tobytes(), lohi.shape, np.asarray(SS.lo, dtype=np.float64).tobytes(), np.asarray(SS.hi, dtype=np.float64).tobytes())
+        # a list the context already holds is not uploaded again (an upload throws the resident free-edge mask away); anything else
+        # that changed the context's checker since -- another checker, a workspace binding, new bounds -- moved its epoch on
+        if self._ctx is ctx and self._bound == (key, ctx._cc_epoch):
+            self._ss = SS
+            return
         ctx.upload_boxes(lohi, SS.lo, SS.hi, dw=dw)
         self._ctx, self._ss = ctx, SS
+        self._bound = (key, ctx._cc_epoch)
 
     def _bind_workspace(self, ctx, SS):
         ctx.upload_boxes(self.lohi() if self.boxes else np.zeros((0, 2, SS.workspace_dim)), None, None, dw=SS.workspace_dim)
         self._ctx = None
+
+    def _edited(self, ctx):
+        """The list was edited in place on the bound context: what was bound is the new list."""
+        SS = self._ss
+        lohi = np.ascontiguousarray(self.lohi() if self.boxes else np.zeros((0, 2, SS.workspace_dim)), dtype=np.float64)
+        self._bound = ((lohi.tobytes(), lohi.shape, np.asarray(SS.lo, dtype=np.float64).tobytes(),
+                        np.asarray(SS.hi, dtype=np.float64).tobytes()), ctx._cc_epoch)
 
     def inflate(self, eps):
         return PointRobotNDBoxes([BoxBounds(b.lo - eps, b.hi + eps) for b in self.boxes]) if eps > 0 else self
@@ -213,6 +228,52 @@ class PointRobot2D:
 
     def addblocker(self, p, r):                                               # robots2D.jl:24
         return self.addobstacle(Circle(p, r))
+
+
+def _cc_bound_to(P):
+    """P.CC is a box checker whose list P.ctx holds right now (bound by _bind and untouched since)."""
+    CC = P.CC
+    return (isinstance(CC, PointRobotNDBoxes) and CC._ctx is P.ctx and CC._ss is P.SS and CC._bound is not None
+            and CC._bound[1] == P.ctx._cc_epoch)
+
+
+def addobstacle_(P, o):
+    """In-place addobstacle (boxesND.jl): appends the box to P.CC.boxes; when P.CC is bound to P.ctx the context's list and the
+    resident free-edge mask follow in place (Context.boxes_add), so the next solve on the same samples sweeps nothing again."""
+    CC = P.CC
+    if not isinstance(CC, PointRobotNDBoxes):
+        raise TypeError("in-place obstacle edits are for PointRobotNDBoxes (the 2-D shape world is rebuilt: CC.addobstacle)")
+    o = o if isinstance(o, BoxBounds) else BoxBounds(o)
+    bound = _cc_bound_to(P)
+    if bound:
+        P.ctx.boxes_add(np.stack([o.lo, o.hi])[None])
+    CC.boxes.append(o)
+    if bound:
+        CC._edited(P.ctx)
+    return P
+
+
+def addblocker_(P, v, r):
+    """In-place addblocker: the box [v - r, v + r] (boxesND.jl)."""
+    v = np.asarray(v, dtype=np.float64)
+    return addobstacle_(P, BoxBounds(v - r, v + r))
+
+
+def removeobstacle_(P, i):
+    """Remove box i (1-based, as the reference indexes CC.boxes) in place; see addobstacle_."""
+    CC = P.CC
+    if not isinstance(CC, PointRobotNDBoxes):
+        raise TypeError("in-place obstacle edits are for PointRobotNDBoxes")
+    i = int(i)
+    if not 1 <= i <= len(CC.boxes):
+        raise IndexError("box %d out of range 1..%d" % (i, len(CC.boxes)))
+    bound = _cc_bound_to(P)
+    if bound:
+        P.ctx.boxes_remove([i])
+    del CC.boxes[i - 1]
+    if bound:
+        CC._edited(P.ctx)
+    return P
 
 
 def is_free_state(v, CC, SS, ctx):
