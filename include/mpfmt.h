@@ -274,6 +274,68 @@ MPFMT_API int32_t mpfmt_prmstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int3
 MPFMT_API int32_t mpfmt_knn_prmstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
                           int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
 
+/* ---- roadmap queries for external states: start and goal states that are NOT samples (the robot's present pose, a batch of candidate
+ *      goals) are attached to the resident roadmap instead of being appended to the sample set (which would rebuild graph and mask).
+ *      The ctx holds an unsharded, swept r-disc graph of radius r = its graph radius (built or imported); the checker is the N-D AABB
+ *      checker in the state space's own coordinates (identity workspace).  For an external state q (d finite doubles):
+ *        near(q) = the samples y with d2(q, y) <= r * r, d2 = the left-to-right unfused fp64 fold of squared differences (the membership
+ *                  test of mpfmt_rdisc_query, same arithmetic), distance = sqrt(d2) (the graph costs' canon); indices ascend.  A q that is
+ *                  bit-equal to sample v gets column v of the resident graph plus v itself at distance 0.
+ *        tail direction (q -> y): the free bit is what mpfmt_motions_free returns for (P = q, Q = V[y]), first-point bounds test included;
+ *        head direction (y -> q): the free bit is what mpfmt_motions_free returns for (P = V[y], Q = q).
+ *      A pair query (s, g) is the PRM* field of the section above on the graph augmented by two nodes:
+ *        edges s -> y, y in near(s), usable iff free and, with checkpts != 0, F[y] set; edges y -> g, y in near(g), usable iff free;
+ *        the direct edge s -> g exists iff d2(s, g) <= r * r and free(s, g);
+ *        C = the least fixed point of C[x] = min(seed[x], min_y fl(C[y] + w_yx)), seed[y] = fl(0 + d(s, y)) on usable seeds, +Inf elsewhere
+ *        (seeds are further upper bounds only: the uniqueness argument above carries over, host and device results are bit-identical and
+ *        independent of scheduling; DESIGN.md "Roadmap queries for external states");
+ *        cost = min(d(s, g) if direct, min_y fl(C[y] + d(y, g)) over usable y), +Inf when there is none.
+ *      Path: s counts as index 0 with C = 0 in the parent rule above (lowest (C[y], y) with fl(C[y] + w) == C[x]): a sample whose seed
+ *        equals its label has parent s; the last hop to g follows the same rule, the direct edge wins when d(s, g) == cost.  The result
+ *        is the list of 1-based sample indices between s and g (empty when the edge is direct).
+ *      Per-query status is a field, not an error: 0 solved, 1 no usable path, 2 s is not a free state, 3 g is not a free state
+ *        (mpfmt_states_free semantics; s is looked at first).  Statuses 1-3 give cost = +Inf and an empty path.  near_s / usable_s /
+ *        near_g / usable_g (sizes of the near sets and their usable parts) are filled for every status.
+ * mpfmt_roadmap_near : the list form for nq states Q (d x nq column-major); direction 0 = tail, 1 = head.  CSR: ptr[nq + 1] 0-based
+ *      offsets (always written), idx 1-based ascending, dist, free_mask bit e = free bit of entry e (ceil(cap / 64) words), *total = ptr[nq].
+ *      *total > cap: MPFMT_ERR_CAPACITY with *total and ptr written, like mpfmt_closeR.  cap == 0 is the size query: only the count pass runs.
+ *      The lists are put in index order by a counting rank, quadratic in a list's length: meant for roadmap radii (lists up to about a
+ *      thousand entries), not for an r that spans a sizeable part of the sample cloud.
+ * mpfmt_roadmap_attach : the reduce form over a host field C[N] (e.g. a row of mpfmt_graph_sssp): per state the head-direction minimum
+ *      cost[q] = min over free y in near(q) with C[y] < +Inf of fl(C[y] + d(y, q)), parent[q] = that y of lowest (C[y], y), 1-based; none:
+ *      parent 0, cost +Inf.  No list is stored: one field, many goals.
+ * mpfmt_roadmap_query : nq pairs S / G (d x nq).  cost[nq]; path_ptr[nq + 1] 0-based offsets into path (1-based samples, room for
+ *      path_cap; beyond it: MPFMT_ERR_CAPACITY with cost, info and path_ptr written); info[nq] (may be NULL).  All 2 nq attachments run in one
+ *      launch each way, the seeded fields one after another.  info.rounds and ms_device depend on scheduling, nothing else does.
+ * mpfmt_host_roadmap_query : one pair on the host over the device-native arrays (as mpfmt_host_graph_sssp; X d x N, lohi (2 d) x M,
+ *      ss_lo / ss_hi or both NULL, F NULL: checkpts = false): all samples scanned for the near sets, the free-motion test of
+ *      mpfmt_host_adaptive_shortcut, a binary-heap Dijkstra with seeds.  No ctx, no device.  path has room for cap indices
+ *      (MPFMT_ERR_CAPACITY with info written otherwise).
+ * Refusals leave the ctx as it was.  MPFMT_ERR_STATE: no resident r-disc graph, a k-nearest graph in the slot, a stale or missing mask, a
+ *      sharded ctx, the 2-D SAT world, a non-identity workspace; MPFMT_ERR_ARG: NULL arrays, a non-finite query coordinate.  nq == 0
+ *      succeeds and does nothing.  Timers "roadmap_near", "roadmap_attach"; stats "roadmap_candidates" (distances evaluated by the last
+ *      call), "roadmap_near_total" (near-set entries it found).
+ * Out of scope: k-nearest graphs (an external state has no radius there), steering spaces, the SAT world, sharded contexts, and repairing
+ *      a field after mpfmt_boxes_add / _remove (the mask stays current: ask again). */
+typedef struct {
+    int32_t status;            /* 0 solved, 1 no usable path, 2 s not a free state, 3 g not a free state */
+    int32_t pad_;
+    int64_t near_s, usable_s;
+    int64_t near_g, usable_g;
+    int64_t rounds;            /* relaxation rounds of the seeded field (0 on the host) */
+    int64_t path_len;          /* samples between s and g */
+    double  ms_device;
+} mpfmt_roadmap_info;
+MPFMT_API int32_t mpfmt_roadmap_near(mpfmt_ctx* ctx, const double* Q, int64_t nq, int32_t direction, int64_t* ptr, int64_t cap, int64_t* idx,
+                           double* dist, uint64_t* free_mask, int64_t* total);
+MPFMT_API int32_t mpfmt_roadmap_attach(mpfmt_ctx* ctx, const double* Q, int64_t nq, const double* C, int64_t* parent, double* cost);
+MPFMT_API int32_t mpfmt_roadmap_query(mpfmt_ctx* ctx, const double* S, const double* G, int64_t nq, int32_t checkpts, double* cost,
+                            int64_t* path_ptr, int64_t* path, int64_t path_cap, mpfmt_roadmap_info* info);
+MPFMT_API int32_t mpfmt_host_roadmap_query(int64_t N, int32_t d, const double* X, const int64_t* colptr, const int32_t* rowval, const double* nzval,
+                                 const uint64_t* efree, const uint64_t* F, const double* lohi, int32_t M, const double* ss_lo,
+                                 const double* ss_hi, double r, const double* s, const double* g, double* cost, int64_t* path, int64_t cap,
+                                 mpfmt_roadmap_info* info);
+
 /* ---- adaptive shortcutting of solution paths (Hsu 2000): shortcut / cut_corner / adaptive_shortcut(!) of src/postprocessors.jl:6-50,
  *      statement for statement, for ONE path on the host and for a BATCH of paths on the device (one wavefront per path; the tree paths
  *      that mpfmt_prmstar / mpfmt_graph_sssp leave to every reached sample are the batch).

@@ -209,6 +209,33 @@ function hip_graph_sssp(DS::HIPDistanceDS, N::Int, sources::Vector{Int}; checkpt
     C, A, info
 end
 
+# states that are NOT samples (the robot's present pose, candidate goals) against the resident roadmap: nothing is rebuilt.
+# S, G: d x n matrices (one state per column).  hip_roadmap_query -> (cost[n], path_ptr[n + 1] 0-based, path (1-based samples), info[n]);
+# hip_roadmap_attach -> the goal half for many goals over ONE field C (a column of hip_graph_sssp): (cost[n], parent[n], 0 = none)
+const sym_roadmap_query = :mpfmt_roadmap_query
+const sym_roadmap_attach = :mpfmt_roadmap_attach
+immutable RoadmapInfo
+    status::Int32; pad::Int32; near_s::Int64; usable_s::Int64; near_g::Int64; usable_g::Int64; rounds::Int64; path_len::Int64
+    ms_device::Float64
+end
+function hip_roadmap_query(DS::HIPDistanceDS, S::Matrix{Float64}, G::Matrix{Float64}; checkpts = true, path_cap = 64 * size(S, 2))
+    n = size(S, 2)
+    cost = Vector{Float64}(n); pptr = Vector{Int}(n + 1); path = Vector{Int}(max(path_cap, 1)); info = Vector{RoadmapInfo}(n)
+    rc = ccall((sym_roadmap_query, libmpfmt), Int32,
+               (Ptr{Void}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{RoadmapInfo}),
+               DS.ctx, S, G, n, checkpts, cost, pptr, path, path_cap, info)
+    rc == -5 && return hip_roadmap_query(DS, S, G; checkpts = checkpts, path_cap = pptr[n + 1])
+    chk(DS.ctx, rc)
+    cost, pptr, path[1:pptr[n + 1]], info
+end
+function hip_roadmap_attach(DS::HIPDistanceDS, Q::Matrix{Float64}, C::Vector{Float64})
+    n = size(Q, 2)
+    cost = Vector{Float64}(n); parent = Vector{Int}(n)
+    chk(DS.ctx, ccall((sym_roadmap_attach, libmpfmt), Int32, (Ptr{Void}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
+                      DS.ctx, Q, n, C, parent, cost))
+    cost, parent
+end
+
 # ---- post-processing: adaptive_shortcut!(P, iterations) (src/postprocessors.jl:41-50) on the device; the checker of P.V.DS.ctx is the
 #      one the last upload bound (hip_bind! / the planner calls).  max_states bounds the working path (include/mpfmt.h).
 const sym_adaptive_shortcut = :mpfmt_adaptive_shortcut

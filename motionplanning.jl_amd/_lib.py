@@ -50,7 +50,13 @@ class ShortcutInfo(C.Structure):
                 ("max_halvings", C.c_int64), ("collision_checks", C.c_int64), ("tests_evaluated", C.c_int64)]
 
 
+class RoadmapInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("pad_", C.c_int32), ("near_s", C.c_int64), ("usable_s", C.c_int64), ("near_g", C.c_int64),
+                ("usable_g", C.c_int64), ("rounds", C.c_int64), ("path_len", C.c_int64), ("ms_device", C.c_double)]
+
+
 SHORTCUT_DONE, SHORTCUT_TRUNCATED, SHORTCUT_STUCK = 0, 1, 2
+ROADMAP_SOLVED, ROADMAP_NO_PATH, ROADMAP_START_BLOCKED, ROADMAP_GOAL_BLOCKED = 0, 1, 2, 3
 WF_SINGLE, WF_EAGER, WF_LAZY = 1, 2, 4
 COMM_ID_BYTES = 128
 
@@ -94,6 +100,11 @@ SYMBOLS = [
                                   C.POINTER(FmtResult)]),
     ("mpfmt_knn_prmstar", C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_d_p, c_i64_p, c_d_p, c_i64_p,
                                       C.POINTER(FmtResult)]),
+    ("mpfmt_roadmap_near", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, C.c_int32, c_i64_p, C.c_int64, c_i64_p, c_d_p, c_u64_p, c_i64_p]),
+    ("mpfmt_roadmap_attach", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, c_d_p, c_i64_p, c_d_p]),
+    ("mpfmt_roadmap_query", C.c_int32, [C.c_void_p, c_d_p, c_d_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, c_i64_p, C.c_int64, C.POINTER(RoadmapInfo)]),
+    ("mpfmt_host_roadmap_query", C.c_int32, [C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p, c_d_p, C.c_int32,
+                                             c_d_p, c_d_p, C.c_double, c_d_p, c_d_p, c_d_p, c_i64_p, C.c_int64, C.POINTER(RoadmapInfo)]),
     ("mpfmt_host_adaptive_shortcut", C.c_int32, [c_d_p, C.c_int64, C.c_int32, c_d_p, C.c_int32, c_d_p, c_d_p, C.c_int32, C.c_int64, c_d_p, C.c_int64,
                                                  c_d_p, C.POINTER(ShortcutInfo)]),
     ("mpfmt_adaptive_shortcut_batch", C.c_int32, [C.c_void_p, c_d_p, c_i64_p, C.c_int64, C.c_int32, C.c_int64, c_d_p, c_i64_p, C.c_int64, c_d_p,
@@ -302,6 +313,38 @@ def host_graph_sssp(colptr0, rowval0, nzval, efree, F=None, source=1, want_paren
     if rc != 0:
         raise MPFMTError(rc, "mpfmt_host_graph_sssp rejected its arguments")
     return Cc[:N], (None if A is None else A[:N])
+
+
+def _roadmap_info(i):
+    return dict(status=int(i.status), near_s=int(i.near_s), usable_s=int(i.usable_s), near_g=int(i.near_g), usable_g=int(i.usable_g),
+                rounds=int(i.rounds), path_len=int(i.path_len), ms_device=float(i.ms_device))
+
+
+def host_roadmap_query(X, colptr0, rowval0, nzval, efree, F, lohi, ss_lo, ss_hi, r, s, g):
+    """One pair query (s, g) for states that are not samples, on the host (include/mpfmt.h, "roadmap queries for external states"): no
+    GPU needed; the checker of Context.roadmap_query.  X (N, d); colptr0 / rowval0 0-based (rowval0 int32), efree / F packed uint64 bit
+    masks (F None: checkpts=false); lohi (M, 2, d); ss_lo / ss_hi or None.  Returns (cost, path (1-based samples between s and g), info)."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    N, d = X.shape
+    colptr0 = np.ascontiguousarray(colptr0, dtype=np.int64)
+    rowval0 = np.ascontiguousarray(rowval0, dtype=np.int32)
+    nzval = np.ascontiguousarray(nzval, dtype=np.float64)
+    efree = np.ascontiguousarray(efree, dtype=np.uint64)
+    Fp = None if F is None else np.ascontiguousarray(F, dtype=np.uint64)
+    lohi = np.ascontiguousarray(lohi, dtype=np.float64).reshape(-1, 2, d)
+    lo = None if ss_lo is None else np.ascontiguousarray(ss_lo, dtype=np.float64)
+    hi = None if ss_hi is None else np.ascontiguousarray(ss_hi, dtype=np.float64)
+    s = np.ascontiguousarray(s, dtype=np.float64).reshape(d)
+    g = np.ascontiguousarray(g, dtype=np.float64).reshape(d)
+    cost = C.c_double(0.0)
+    path = np.empty(N + 1, dtype=np.int64)
+    info = RoadmapInfo()
+    rc = lib().mpfmt_host_roadmap_query(N, d, _dp(X), _ip(colptr0), rowval0.ctypes.data_as(C.POINTER(C.c_int32)), _dp(nzval), _up(efree), _up(Fp),
+                                        _dp(lohi), lohi.shape[0], _dp(lo), _dp(hi), float(r), _dp(s), _dp(g), C.byref(cost), _ip(path), N + 1,
+                                        C.byref(info))
+    if rc != 0:
+        raise MPFMTError(rc, "mpfmt_host_roadmap_query rejected its arguments")
+    return float(cost.value), path[:info.path_len].copy(), _roadmap_info(info)
 
 
 def _shortcut_info(i):
@@ -599,6 +642,73 @@ class Context:
         self._chk(self._L.mpfmt_graph_sssp(self._h, _ip(src), n, int(bool(checkpts)), _dp(Cc), _ip(A), info))
         return dict(C=Cc[:n, :self.N], A=None if A is None else A[:n, :self.N],
                     info=[{k: getattr(info[i], k) for k, _ in SsspInfo._fields_} for i in range(n)])
+
+    # ---- roadmap queries for states that are not samples (include/mpfmt.h, "roadmap queries for external states") ----------
+    def _states(self, Q):
+        Q = np.asarray(Q, dtype=np.float64)
+        Q = np.ascontiguousarray(Q.reshape(0, self.d) if Q.size == 0 else np.atleast_2d(Q))
+        if Q.ndim != 2 or (Q.shape[0] and Q.shape[1] != self.d):
+            raise ValueError("states must be (n, %d)" % self.d)
+        return Q
+
+    def roadmap_near(self, Q, direction=0, cap=None):
+        """Near lists of the external states Q (n, d) over the resident r-disc graph's radius: (ptr (n + 1,) 0-based, idx 1-based
+        ascending, dist, free bits (bool)); direction 0 = tail (q -> sample), 1 = head (sample -> q).  cap: capacity in entries (None:
+        ask, then fetch); too small raises MPFMTError(ERR_CAPACITY) whose .total holds the size needed."""
+        Q = self._states(Q)
+        n = Q.shape[0]
+        ptr = np.zeros(n + 1, dtype=np.int64)
+        total = C.c_int64(0)
+        ask = cap is None
+        cap = 0 if ask else int(cap)
+        while True:
+            idx = np.empty(max(cap, 1), dtype=np.int64); dist = np.empty(max(cap, 1), dtype=np.float64)
+            mask = np.zeros(max(nwords(cap), 1), dtype=np.uint64)
+            rc = self._L.mpfmt_roadmap_near(self._h, _dp(Q), n, int(direction), _ip(ptr), cap, _ip(idx), _dp(dist), _up(mask), C.byref(total))
+            if rc == ERR_CAPACITY and ask:
+                cap, ask = int(total.value), False
+                continue
+            if rc == ERR_CAPACITY:
+                e = MPFMTError(rc, self._L.mpfmt_last_error(self._h).decode())
+                e.total, e.ptr = int(total.value), ptr
+                raise e
+            self._chk(rc)
+            t = int(total.value)
+            return ptr, idx[:t].copy(), dist[:t].copy(), unpack_bits(mask, t)
+
+    def roadmap_attach(self, Q, Cfield):
+        """The goal half for many goals over ONE field (a row of graph_sssp): per state of Q (n, d) the head-direction minimum
+        fl(C[y] + d(y, q)) over the free near samples -> (cost (n,), +Inf = none; parent (n,) 1-based, 0 = none)."""
+        Q = self._states(Q)
+        n = Q.shape[0]
+        Cf = np.ascontiguousarray(Cfield, dtype=np.float64)
+        if Cf.shape != (self.N,):
+            raise ValueError("C must have N entries")
+        cost = np.empty(max(n, 1), dtype=np.float64); par = np.empty(max(n, 1), dtype=np.int64)
+        self._chk(self._L.mpfmt_roadmap_attach(self._h, _dp(Q), n, _dp(Cf), _ip(par), _dp(cost)))
+        return cost[:n], par[:n]
+
+    def roadmap_query(self, S, G, checkpts=True):
+        """Pair queries between external states S[i] -> G[i] ((n, d) each) over the resident roadmap: (cost (n,), paths = list of 1-based
+        sample index arrays between s and g, info = list of dicts: status 0 solved / 1 no path / 2 start blocked / 3 goal blocked,
+        near_s, usable_s, near_g, usable_g, rounds, path_len, ms_device)."""
+        S = self._states(S); G = self._states(G)
+        if S.shape != G.shape:
+            raise ValueError("S and G must have the same shape")
+        n = S.shape[0]
+        cost = np.empty(max(n, 1), dtype=np.float64)
+        pptr = np.zeros(n + 1, dtype=np.int64)
+        info = (RoadmapInfo * max(n, 1))()
+        cap = max(64 * n, 1)
+        while True:
+            path = np.empty(cap, dtype=np.int64)
+            rc = self._L.mpfmt_roadmap_query(self._h, _dp(S), _dp(G), n, int(bool(checkpts)), _dp(cost), _ip(pptr), _ip(path), cap, info)
+            if rc == ERR_CAPACITY and int(pptr[n]) > cap:
+                cap = int(pptr[n])
+                continue
+            self._chk(rc)
+            break
+        return (cost[:n], [path[pptr[i]:pptr[i + 1]].copy() for i in range(n)], [_roadmap_info(info[i]) for i in range(n)])
 
     def prmstar(self, r, goal_kind, goal_params, init_idx=1, checkpts=True):
         """PRM*: graph_step_device(r) (reused when resident), then the exact cost-to-come field of init_idx over the free-edge graph and

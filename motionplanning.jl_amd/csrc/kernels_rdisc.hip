@@ -33,14 +33,7 @@
 // ------------------------------------------------------------------------------------------------
 // grid build
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int cell_of(double x, double lo, double inv_w, int g)
-{
-    double f = floor((x - lo) * inv_w);
-    int c = (int)f;
-    if (!(f >= 0.0)) c = 0;
-    if (f >= (double)g) c = g - 1;
-    return c;
-}
+__device__ __forceinline__ int cell_of(double x, double lo, double inv_w, int g) { return mpfmt_cell_of(x, lo, inv_w, g); }
 
 // ------------------------------------------------------------------------------------------------
 // The cell sort (hand-written: a counting sort by cell id, then an ordering pass inside each cell).

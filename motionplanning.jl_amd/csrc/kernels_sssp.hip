@@ -148,11 +148,85 @@ void mpfmt_sssp_free(mpfmt_ctx* ctx)
     ctx->sssp_ev[0] = ctx->sssp_ev[1] = nullptr;
 }
 
-int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, double* C_host, int64_t* A_host, mpfmt_sssp_info* info)
+// ---- the seeded field: an external start (include/mpfmt.h, "roadmap queries for external states") ----------------------------------------
+// The start s is not a sample: it enters the relaxation as upper bounds on the labels of its usable neighbours, seed[y] = fl(0 + d(s, y)).
+// C starts from min(+Inf, seed) instead of (+Inf, C[src] = 0), the round-0 bitmap holds the seeds, slot[0].changed their number and
+// slot[0].minbits = 0 -- every label written later is fl(C[y] + w) >= 0 = mlow(0), so the band skip of k_sssp_relax is valid from round 0 and
+// k_sssp_relax runs unchanged.  An empty seed set leaves slot[0].changed = 0: every round returns at once.
+__global__ __launch_bounds__(256) void k_sssp_seed_clear(int64_t N, int64_t words, double* __restrict__ C, double* __restrict__ seed,
+                                                         uint64_t* __restrict__ bm, sssp_state* __restrict__ st)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < N) { C[i] = INFINITY; seed[i] = INFINITY; }
+    if (i < 3 * words) bm[i] = 0ull;
+    if (i == 0) {
+        st->slot[0].changed = 0; st->slot[0].minbits = 0ull;
+        st->slot[1].changed = 0; st->slot[1].minbits = SSSP_INF_BITS;
+        st->slot[2].changed = 0; st->slot[2].minbits = SSSP_INF_BITS;
+        st->relax = 0; st->rounds = 0; st->reached = 0; st->pad = 0;
+    }
+}
+
+// scatter of the usable entries of the start's near list (distinct samples: no two threads write one label)
+__global__ __launch_bounds__(256) void k_sssp_seed(int64_t n, const int64_t* __restrict__ idx1, const double* __restrict__ dist,
+                                                   const uint8_t* __restrict__ bits, double* __restrict__ C, double* __restrict__ seed,
+                                                   uint64_t* bm, sssp_state* st)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool us = e < n && (bits[e] & 2);
+    if (us) {
+        const int64_t y = idx1[e] - 1;
+        const double sd = 0.0 + dist[e];
+        C[y] = sd; seed[y] = sd;
+        atomicOr((unsigned long long*)&bm[y >> 6], 1ull << (y & 63));
+    }
+    const unsigned long long m = __ballot(us);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&st->slot[0].changed, (unsigned long long)__popcll(m));
+}
+
+// k_sssp_parents with the start as index 0 of label 0: seed[x] == C[x] makes s the parent of lowest (C, index), A[x] = -1
+__global__ __launch_bounds__(256) void k_sssp_parents_seeded(int64_t N, const int64_t* __restrict__ colptr, const int32_t* __restrict__ rowval,
+                                                             const double* __restrict__ nzval, const uint64_t* __restrict__ efree,
+                                                             const double* __restrict__ C, const double* __restrict__ seed,
+                                                             int64_t* __restrict__ A, sssp_state* st)
+{
+    const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    unsigned long long nreach = 0;
+    for (int64_t x = gtid >> 6; x < N; x += nwaves) {
+        const double cx = C[x];
+        if (!(cx < INFINITY)) { if (lane == 0) A[x] = 0; continue; }
+        ++nreach;
+        if (seed[x] == cx) { if (lane == 0) A[x] = -1; continue; }
+        double cb = INFINITY; int32_t yb = 0x7fffffff;
+        for (int64_t b = colptr[x] + lane; b < colptr[x + 1]; b += 64) {
+            if (!((efree[b >> 6] >> (b & 63)) & 1ull)) continue;
+            const int32_t y = rowval[b];
+            const double cy = C[y];
+            if (!(cy + nzval[b] == cx)) continue;
+            if (cy < cb || (cy == cb && y < yb)) { cb = cy; yb = y; }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const double oc = __shfl_xor(cb, off);
+            const int32_t oy = __shfl_xor(yb, off);
+            if (oc < cb || (oc == cb && oy < yb)) { cb = oc; yb = oy; }
+        }
+        if (lane == 0) A[x] = yb == 0x7fffffff ? 0 : (int64_t)yb + 1;
+    }
+    if (lane == 0 && nreach) atomicAdd(&st->reached, nreach);
+}
+
+// One field over the resident graph and mask: from a sample (source0 >= 0: k_sssp_init, k_sssp_parents) or from the usable entries of an
+// external start's near list (source0 < 0: k_sssp_seed_clear + k_sssp_seed, k_sssp_parents_seeded); the rounds are the same.
+struct sssp_seeds { const int64_t* idx1; const double* dist; const uint8_t* bits; int64_t n; };
+
+static int32_t sssp_run(mpfmt_ctx* ctx, int64_t source0, const sssp_seeds* sd, const uint64_t* d_F, double* C_host, int64_t* A_host, mpfmt_sssp_info* info)
 {
     const int64_t N = ctx->N, words = (N + 63) / 64;
     int32_t rc;
     if ((rc = ctx->sssp_C.ensure(ctx, sizeof(double) * (size_t)N))) return rc;
+    if (sd && (rc = ctx->sssp_seed.ensure(ctx, sizeof(double) * (size_t)N))) return rc;
     if ((rc = ctx->sssp_A.ensure(ctx, sizeof(int64_t) * (size_t)N))) return rc;
     if ((rc = ctx->sssp_bm.ensure(ctx, sizeof(uint64_t) * 3 * (size_t)words))) return rc;
     if ((rc = ctx->sssp_state.ensure(ctx, sizeof(sssp_state)))) return rc;
@@ -167,7 +241,14 @@ int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, 
     HIPCHK(ctx, hipEventRecord(ctx->sssp_ev[0], ctx->stream));
     {
         mpfmt_timed tm(ctx);
-        hipLaunchKernelGGL(k_sssp_init, dim3(nb_init), dim3(256), 0, ctx->stream, N, words, source0, ctx->sssp_C, ctx->sssp_bm, st);
+        if (!sd) {
+            hipLaunchKernelGGL(k_sssp_init, dim3(nb_init), dim3(256), 0, ctx->stream, N, words, source0, ctx->sssp_C, ctx->sssp_bm, st);
+        } else {
+            hipLaunchKernelGGL(k_sssp_seed_clear, dim3(nb_init), dim3(256), 0, ctx->stream, N, words, ctx->sssp_C, ctx->sssp_seed, ctx->sssp_bm, st);
+            if (sd->n > 0)
+                hipLaunchKernelGGL(k_sssp_seed, dim3((unsigned)((sd->n + 255) / 256)), dim3(256), 0, ctx->stream, sd->n, sd->idx1, sd->dist, sd->bits,
+                                   ctx->sssp_C, ctx->sssp_seed, ctx->sssp_bm, st);
+        }
         // every non-final round lowers at least one label for good, and a label is the fold of a simple path: N rounds bound the loop
         int64_t round = 0;
         bool done = false;
@@ -184,8 +265,12 @@ int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, 
     }
     {
         mpfmt_timed tm(ctx);
-        hipLaunchKernelGGL(k_sssp_parents, dim3(nb), dim3(256), 0, ctx->stream, N, source0, ctx->colptr, ctx->rowval, ctx->nzval, ctx->graph_free,
-                           ctx->sssp_C, ctx->sssp_A, st);
+        if (!sd)
+            hipLaunchKernelGGL(k_sssp_parents, dim3(nb), dim3(256), 0, ctx->stream, N, source0, ctx->colptr, ctx->rowval, ctx->nzval, ctx->graph_free,
+                               ctx->sssp_C, ctx->sssp_A, st);
+        else
+            hipLaunchKernelGGL(k_sssp_parents_seeded, dim3(nb), dim3(256), 0, ctx->stream, N, ctx->colptr, ctx->rowval, ctx->nzval, ctx->graph_free,
+                               ctx->sssp_C, ctx->sssp_seed, ctx->sssp_A, st);
         tm.end("sssp_parents");
     }
     HIPCHK(ctx, hipEventRecord(ctx->sssp_ev[1], ctx->stream));
@@ -199,4 +284,16 @@ int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, 
     ctx->sssp_rounds = (int64_t)sh->rounds; ctx->sssp_relax = (int64_t)sh->relax; ctx->sssp_reached = (int64_t)sh->reached;
     if (info) { info->reached = ctx->sssp_reached; info->rounds = ctx->sssp_rounds; info->relaxations = ctx->sssp_relax; info->ms_device = ms; }
     return MPFMT_OK;
+}
+
+int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, double* C_host, int64_t* A_host, mpfmt_sssp_info* info)
+{
+    return sssp_run(ctx, source0, nullptr, d_F, C_host, A_host, info);
+}
+
+int32_t mpfmt_sssp_seeded_device(mpfmt_ctx* ctx, const int64_t* d_idx1, const double* d_dist, const uint8_t* d_bits, int64_t n, const uint64_t* d_F,
+                                 mpfmt_sssp_info* info)
+{
+    const sssp_seeds sd{d_idx1, d_dist, d_bits, n};
+    return sssp_run(ctx, -1, &sd, d_F, nullptr, nullptr, info);
 }

@@ -1378,6 +1378,179 @@ int32_t mpfmt_graph_sssp(mpfmt_ctx* ctx, const int64_t* sources, int64_t nsrc, i
     return MPFMT_OK;
 }
 
+// ---- roadmap queries for external states (kernels_roadmap.hip, the seeded field of kernels_sssp.hip) ---------------------------------------
+
+// what every call on external states asks of the ctx; nothing has been touched when it refuses
+static int32_t roadmap_ready(mpfmt_ctx* ctx)
+{
+    // (what the ctx IS comes before what it has ready: a wrong checker or workspace is named as such, not as the stale mask its upload left)
+    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "roadmap queries run on an unsharded ctx");
+    if (ctx->knn_k > 0 && ctx->graph_filled) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "external states attach to an r-disc graph: the resident graph is a k-nearest one");
+    if (ctx->cc_kind != 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "external states need the N-D box checker (the 2-D SAT world is resident)");
+    if (ctx->have_boxes && ctx->Xo && ctx->dw != ctx->d)
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, "external states need an identity workspace (dw = %d, d = %d)", ctx->dw, ctx->d);
+    int32_t rc;
+    if ((rc = sssp_ready(ctx))) return rc;
+    if (!(ctx->graph_r >= 0.0)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no resident r-disc graph");
+    if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
+    return MPFMT_OK;
+}
+
+static int32_t roadmap_finite(mpfmt_ctx* ctx, const double* Q, int64_t nq, const char* what)
+{
+    for (int64_t i = 0; i < nq * ctx->d; ++i)
+        if (!std::isfinite(Q[i])) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%s: non-finite coordinate in state %lld", what, (long long)(i / ctx->d + 1));
+    return MPFMT_OK;
+}
+
+static int32_t up_d(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* h, size_t n, double** d)
+{
+    HIPCHK(ctx, tmp.get(d, sizeof(double) * n));
+    HIPCHK(ctx, hipMemcpyAsync(*d, h, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_roadmap_near(mpfmt_ctx* ctx, const double* Q, int64_t nq, int32_t direction, int64_t* ptr, int64_t cap, int64_t* idx, double* dist,
+                           uint64_t* free_mask, int64_t* total)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (nq < 0 || cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_near: nq / cap < 0");
+    if (direction != 0 && direction != 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_near: direction must be 0 (tail) or 1 (head)");
+    if (nq > 0 && (!Q || !ptr || !total)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_near: Q / ptr / total is NULL");
+    if (nq > 0 && cap > 0 && (!idx || !dist || !free_mask)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_near: idx / dist / free_mask is NULL");
+    int32_t rc;
+    if ((rc = roadmap_ready(ctx))) return rc;
+    if (nq == 0) return MPFMT_OK;
+    if ((rc = roadmap_finite(ctx, Q, nq, "roadmap_near"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    mpfmt_tmp tmp;
+    double* dQ = nullptr;
+    if ((rc = up_d(ctx, tmp, Q, (size_t)nq * ctx->d, &dQ))) return rc;
+    mpfmt_rm_list L;
+    if ((rc = mpfmt_roadmap_lists(ctx, tmp, dQ, nq, direction, nullptr, &L, cap == 0))) return rc;      // (cap == 0 asks for the sizes: the count pass alone)
+    memcpy(ptr, L.ptr_host.data(), sizeof(int64_t) * (size_t)(nq + 1));
+    *total = L.total;
+    if (L.total > cap) return mpfmt_fail(ctx, MPFMT_ERR_CAPACITY, "roadmap_near: %lld entries exceed capacity %lld", (long long)L.total, (long long)cap);
+    if (L.total == 0) return MPFMT_OK;
+    std::vector<uint8_t> bits((size_t)L.total);
+    HIPCHK(ctx, hipMemcpyAsync(idx, L.idx1, sizeof(int64_t) * (size_t)L.total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(dist, L.dist, sizeof(double) * (size_t)L.total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(bits.data(), L.bits, (size_t)L.total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t w = 0; w < (L.total + 63) / 64; ++w) free_mask[w] = 0;
+    for (int64_t e = 0; e < L.total; ++e) if (bits[(size_t)e] & 1) free_mask[e >> 6] |= 1ull << (e & 63);
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_roadmap_attach(mpfmt_ctx* ctx, const double* Q, int64_t nq, const double* C, int64_t* parent, double* cost)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (nq < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_attach: nq < 0");
+    if (nq > 0 && (!Q || !C || !parent || !cost)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_attach: Q / C / parent / cost is NULL");
+    int32_t rc;
+    if ((rc = roadmap_ready(ctx))) return rc;
+    if (nq == 0) return MPFMT_OK;
+    if ((rc = roadmap_finite(ctx, Q, nq, "roadmap_attach"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    mpfmt_tmp tmp;
+    double *dQ = nullptr, *dC = nullptr, *d_cost = nullptr; int64_t* d_par = nullptr;
+    if ((rc = up_d(ctx, tmp, Q, (size_t)nq * ctx->d, &dQ))) return rc;
+    if ((rc = up_d(ctx, tmp, C, (size_t)ctx->N, &dC))) return rc;
+    HIPCHK(ctx, tmp.get(&d_cost, sizeof(double) * (size_t)nq));
+    HIPCHK(ctx, tmp.get(&d_par, sizeof(int64_t) * (size_t)nq));
+    if ((rc = mpfmt_roadmap_reduce(ctx, tmp, dQ, nq, dC, d_cost, d_par))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(parent, d_par, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_roadmap_query(mpfmt_ctx* ctx, const double* S, const double* G, int64_t nq, int32_t checkpts, double* cost, int64_t* path_ptr,
+                            int64_t* path, int64_t path_cap, mpfmt_roadmap_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (nq < 0 || path_cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_query: nq / path_cap < 0");
+    if (nq > 0 && (!S || !G || !cost || !path_ptr || (path_cap > 0 && !path))) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_query: S / G / cost / path_ptr / path is NULL");
+    int32_t rc;
+    if ((rc = roadmap_ready(ctx))) return rc;
+    if (nq == 0) return MPFMT_OK;
+    if ((rc = roadmap_finite(ctx, S, nq, "roadmap_query (S)"))) return rc;
+    if ((rc = roadmap_finite(ctx, G, nq, "roadmap_query (G)"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int d = ctx->d;
+    const int64_t N = ctx->N, words = (nq + 63) / 64;
+    mpfmt_tmp tmp;
+    double *dS = nullptr, *dG = nullptr;
+    if ((rc = up_d(ctx, tmp, S, (size_t)nq * d, &dS))) return rc;
+    if ((rc = up_d(ctx, tmp, G, (size_t)nq * d, &dG))) return rc;
+    // the two states of every pair and the direct edge
+    uint64_t* d_m = nullptr;
+    HIPCHK(ctx, tmp.get(&d_m, sizeof(uint64_t) * 3 * (size_t)words));
+    if ((rc = mpfmt_launch_states_free(ctx, dS, nq, d_m))) return rc;
+    if ((rc = mpfmt_launch_states_free(ctx, dG, nq, d_m + words))) return rc;
+    if ((rc = mpfmt_launch_motions_free(ctx, dS, dG, nq, d_m + 2 * words))) return rc;
+    std::vector<uint64_t> m((size_t)(3 * words));
+    HIPCHK(ctx, hipMemcpyAsync(m.data(), d_m, sizeof(uint64_t) * 3 * (size_t)words, hipMemcpyDeviceToHost, ctx->stream));
+    if (checkpts && (rc = sssp_point_bitmap(ctx))) return rc;
+    const uint64_t* d_F = checkpts ? ctx->sssp_F.get() : nullptr;
+    // all attachments, one launch each way
+    mpfmt_rm_list Ls, Lg;
+    if ((rc = mpfmt_roadmap_lists(ctx, tmp, dS, nq, 0, d_F, &Ls))) return rc;
+    const int64_t cand_s = ctx->roadmap_candidates, tot_s = ctx->roadmap_near_total;
+    if ((rc = mpfmt_roadmap_lists(ctx, tmp, dG, nq, 1, nullptr, &Lg))) return rc;
+    ctx->roadmap_candidates += cand_s; ctx->roadmap_near_total += tot_s;
+    int64_t* d_res = nullptr;
+    HIPCHK(ctx, tmp.get(&d_res, sizeof(int64_t) * (size_t)(N + 8)));
+    int64_t res[3];
+    std::vector<int64_t> hops;
+    const double r2 = ctx->graph_r * ctx->graph_r;
+    int64_t used = 0;
+    bool over = false;
+    path_ptr[0] = 0;
+    for (int64_t q = 0; q < nq; ++q) {
+        mpfmt_roadmap_info inf;
+        memset(&inf, 0, sizeof inf);
+        inf.near_s = Ls.ptr_host[(size_t)q + 1] - Ls.ptr_host[(size_t)q]; inf.usable_s = Ls.usable_host[(size_t)q];
+        inf.near_g = Lg.ptr_host[(size_t)q + 1] - Lg.ptr_host[(size_t)q]; inf.usable_g = Lg.usable_host[(size_t)q];
+        cost[q] = INFINITY;
+        int64_t len = 0;
+        if (!((m[(size_t)(q >> 6)] >> (q & 63)) & 1ull)) inf.status = 2;
+        else if (!((m[(size_t)(words + (q >> 6))] >> (q & 63)) & 1ull)) inf.status = 3;
+        else {
+            const int64_t s0 = Ls.ptr_host[(size_t)q];
+            mpfmt_sssp_info fi;
+            if ((rc = mpfmt_sssp_seeded_device(ctx, Ls.idx1 + s0, Ls.dist + s0, Ls.bits + s0, inf.near_s, d_F, &fi))) return rc;
+            inf.rounds = fi.rounds; inf.ms_device = fi.ms_device;
+            if ((rc = mpfmt_roadmap_goal(ctx, Lg, q, ctx->sssp_C, ctx->sssp_A, d_res))) return rc;
+            HIPCHK(ctx, hipMemcpyAsync(res, d_res, sizeof(int64_t) * 3, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            double best; memcpy(&best, &res[0], sizeof best);
+            const int64_t last = res[1];
+            double dsg2 = 0.0;
+            for (int i = 0; i < d; ++i) { const double t = S[q * d + i] - G[q * d + i]; const double tt = t * t; dsg2 = (i == 0) ? tt : dsg2 + tt; }
+            const bool direct = dsg2 <= r2 && ((m[(size_t)(2 * words + (q >> 6))] >> (q & 63)) & 1ull);
+            const double dsg = std::sqrt(dsg2);
+            if (direct && (last == 0 || dsg <= best)) { cost[q] = dsg; inf.status = 0; }
+            else if (last == 0) inf.status = 1;
+            else {
+                cost[q] = best; inf.status = 0; len = res[2];
+                if (used + len <= path_cap) {
+                    hops.resize((size_t)len);
+                    HIPCHK(ctx, hipMemcpyAsync(hops.data(), d_res + 3, sizeof(int64_t) * (size_t)len, hipMemcpyDeviceToHost, ctx->stream));
+                    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+                    for (int64_t i = 0; i < len; ++i) path[used + i] = hops[(size_t)(len - 1 - i)];
+                } else over = true;
+            }
+        }
+        inf.path_len = len;
+        used += len;
+        path_ptr[q + 1] = used;
+        if (info) info[q] = inf;
+    }
+    if (over) return mpfmt_fail(ctx, MPFMT_ERR_CAPACITY, "roadmap_query: %lld path samples exceed capacity %lld", (long long)used, (long long)path_cap);
+    return MPFMT_OK;
+}
+
 // ---- adaptive shortcutting of solution paths (kernels_shortcut.hip; host reference: mpfmt_host_adaptive_shortcut) ------------------------
 
 int32_t mpfmt_adaptive_shortcut_batch(mpfmt_ctx* ctx, const double* P, const int64_t* offsets, int64_t B, int32_t iterations, int64_t max_states,
@@ -2000,6 +2173,8 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "sssp_rounds") == 0) { *value = ctx->sssp_rounds; return MPFMT_OK; }
     if (strcmp(name, "sssp_relaxations") == 0) { *value = ctx->sssp_relax; return MPFMT_OK; }
     if (strcmp(name, "sssp_reached") == 0) { *value = ctx->sssp_reached; return MPFMT_OK; }
+    if (strcmp(name, "roadmap_candidates") == 0) { *value = ctx->roadmap_candidates; return MPFMT_OK; }
+    if (strcmp(name, "roadmap_near_total") == 0) { *value = ctx->roadmap_near_total; return MPFMT_OK; }
     if (strcmp(name, "shortcut_tests_evaluated") == 0) { *value = ctx->shortcut_tests; return MPFMT_OK; }
     if (strcmp(name, "shortcut_checks") == 0) { *value = ctx->shortcut_checks; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_path") == 0) { *value = ctx->bd_path; return MPFMT_OK; }

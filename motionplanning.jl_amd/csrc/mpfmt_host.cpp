@@ -498,3 +498,126 @@ int32_t mpfmt_host_adaptive_shortcut(const double* P, int64_t n, int32_t d, cons
     }
     return MPFMT_OK;
 }
+
+// ---- roadmap query for one external pair (s, g) on the host (include/mpfmt.h, "roadmap queries for external states"): the checker of
+// mpfmt_roadmap_query (kernels_roadmap.hip, kernels_sssp.hip), bit-equal to it.  Near sets by a scan of all samples, the free-motion test
+// above, a binary-heap Dijkstra from the usable seeds, then the parent rule with s as index 0 of label 0.
+int32_t mpfmt_host_roadmap_query(int64_t N, int32_t d, const double* X, const int64_t* colptr, const int32_t* rowval, const double* nzval,
+                                 const uint64_t* efree, const uint64_t* F, const double* lohi, int32_t M, const double* ss_lo,
+                                 const double* ss_hi, double r, const double* s, const double* g, double* cost, int64_t* path, int64_t cap,
+                                 mpfmt_roadmap_info* info)
+{
+    if (!X || !colptr || !efree || !s || !g || !cost || !info || N < 1 || d < 1 || d > MPFMT_MAX_DIM || M < 0 || cap < 0) return MPFMT_ERR_ARG;
+    if ((M > 0 && !lohi) || (cap > 0 && !path) || (ss_lo == nullptr) != (ss_hi == nullptr) || !(r >= 0.0) || !std::isfinite(r)) return MPFMT_ERR_ARG;
+    if (colptr[0] != 0) return MPFMT_ERR_ARG;
+    for (int64_t j = 0; j < N; ++j) if (colptr[j + 1] < colptr[j]) return MPFMT_ERR_ARG;
+    const int64_t nnz = colptr[N];
+    if (nnz > 0 && (!rowval || !nzval)) return MPFMT_ERR_ARG;
+    for (int64_t e = 0; e < nnz; ++e) if (rowval[e] < 0 || rowval[e] >= N || !(nzval[e] >= 0.0)) return MPFMT_ERR_ARG;
+    for (int i = 0; i < d; ++i) if (!std::isfinite(s[i]) || !std::isfinite(g[i])) return MPFMT_ERR_ARG;
+    auto bitp = [](const uint64_t* m, int64_t i) { return (m[i >> 6] >> (i & 63)) & 1ull; };
+    ShortcutWorld W{d, lohi, M, ss_lo, ss_hi};
+    auto state_free = [&](const double* v) {                                     // is_free_state (statespaces.jl:151-152, boxesND.jl:42-43)
+        if (ss_lo) for (int i = 0; i < d; ++i) if (!((ss_lo[i] <= v[i]) && (v[i] <= ss_hi[i]))) return false;
+        for (int k = 0; k < M; ++k) {
+            const double* lo = lohi + (size_t)k * 2 * d;
+            const double* hi = lo + d;
+            bool out = false;
+            for (int i = 0; i < d; ++i) out = out || !((lo[i] <= v[i]) && (v[i] <= hi[i]));
+            if (!out) return false;
+        }
+        return true;
+    };
+    auto dist2 = [&](const double* a, const double* b) {
+        double s2 = 0.0;
+        for (int i = 0; i < d; ++i) { const double t = a[i] - b[i]; const double tt = t * t; s2 = (i == 0) ? tt : s2 + tt; }
+        return s2;
+    };
+    memset(info, 0, sizeof *info);
+    *cost = INFINITY;
+    const double r2 = r * r;
+    // near sets: seeds (tail direction, s -> y) and the goal's entries (head direction, y -> g)
+    std::vector<double> seed((size_t)N, INFINITY);
+    std::vector<int64_t> gy; std::vector<double> gd;
+    for (int64_t y = 0; y < N; ++y) {
+        const double* v = X + (size_t)y * d;
+        const double ds2 = dist2(s, v);
+        if (ds2 <= r2) {
+            ++info->near_s;
+            if (W.free(s, v) && (!F || bitp(F, y))) { ++info->usable_s; seed[(size_t)y] = 0.0 + std::sqrt(ds2); }
+        }
+        const double dg2 = dist2(g, v);
+        if (dg2 <= r2) {
+            ++info->near_g;
+            if (W.free(v, g)) { ++info->usable_g; gy.push_back(y); gd.push_back(std::sqrt(dg2)); }
+        }
+    }
+    if (!state_free(s)) { info->status = 2; return MPFMT_OK; }
+    if (!state_free(g)) { info->status = 3; return MPFMT_OK; }
+    const double dsg2 = dist2(s, g);
+    const bool direct = dsg2 <= r2 && W.free(s, g);
+    // out-edges of every sample: the usable entries only (free bit set, target allowed by F)
+    std::vector<int64_t> rowptr((size_t)N + 1, 0);
+    for (int64_t x = 0; x < N; ++x) {
+        if (F && !bitp(F, x)) continue;
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b) if (bitp(efree, b)) rowptr[rowval[b] + 1]++;
+    }
+    for (int64_t i = 0; i < N; ++i) rowptr[i + 1] += rowptr[i];
+    std::vector<int64_t> cur(rowptr.begin(), rowptr.end() - 1);
+    std::vector<int32_t> tgt((size_t)std::max<int64_t>(rowptr[N], 1));
+    std::vector<double> wgt((size_t)std::max<int64_t>(rowptr[N], 1));
+    for (int64_t x = 0; x < N; ++x) {
+        if (F && !bitp(F, x)) continue;
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b)
+            if (bitp(efree, b)) { const int64_t a = cur[rowval[b]]++; tgt[a] = (int32_t)x; wgt[a] = nzval[b]; }
+    }
+    std::vector<double> C(seed);
+    Heap heap;
+    for (int64_t y = 0; y < N; ++y) if (C[(size_t)y] < INFINITY) heap.push(y, C[(size_t)y]);
+    while (!heap.empty()) {
+        const double cy = heap.pri[0];
+        const int64_t y = heap.pop();
+        if (cy > C[(size_t)y]) continue;
+        for (int64_t a = rowptr[y]; a < rowptr[y + 1]; ++a) {
+            const int64_t x = tgt[a];
+            const double c = cy + wgt[a];
+            if (c < C[(size_t)x]) { C[(size_t)x] = c; heap.push(x, c); }
+        }
+    }
+    // the last hop: lowest (fl(C[y] + d(y, g)), C[y], y); the direct edge is (d(s, g), 0, index 0)
+    double best = INFINITY, bcy = INFINITY; int64_t by = -1;
+    for (size_t k = 0; k < gy.size(); ++k) {
+        const int64_t y = gy[k];
+        const double cy = C[(size_t)y];
+        if (!(cy < INFINITY)) continue;
+        const double c = cy + gd[k];
+        if (c < best || (c == best && (cy < bcy || (cy == bcy && y < by)))) { best = c; bcy = cy; by = y; }
+    }
+    if (direct) {
+        const double dsg = std::sqrt(dsg2);
+        if (by < 0 || dsg <= best) { *cost = dsg; info->status = 0; info->path_len = 0; return MPFMT_OK; }
+    }
+    if (by < 0) { info->status = 1; return MPFMT_OK; }
+    *cost = best;
+    std::vector<int64_t> rev;
+    int64_t x = by;
+    for (;;) {
+        rev.push_back(x + 1);
+        if ((int64_t)rev.size() > N) break;
+        if (seed[(size_t)x] == C[(size_t)x]) break;                              // parent s
+        int64_t yb = -1; double cb = 0.0;
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b) {
+            if (!bitp(efree, b)) continue;
+            const int64_t y = rowval[b];
+            const double cy = C[(size_t)y];
+            if (!(cy + nzval[b] == C[(size_t)x])) continue;
+            if (yb < 0 || cy < cb || (cy == cb && y < yb)) { yb = y; cb = cy; }
+        }
+        if (yb < 0) break;
+        x = yb;
+    }
+    info->path_len = (int64_t)rev.size();
+    if ((int64_t)rev.size() > cap) return MPFMT_ERR_CAPACITY;
+    for (size_t i = 0; i < rev.size(); ++i) path[i] = rev[rev.size() - 1 - i];
+    return MPFMT_OK;
+}

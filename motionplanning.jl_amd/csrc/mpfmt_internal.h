@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include <string>
 #include <map>
 #include <utility>
@@ -41,6 +42,16 @@ struct mpfmt_grid {
     int64_t inner;                       // ids per half-block
     int64_t ncells;                      // id range = inner << nsplit
 };
+// cell coordinate of x along one axis, clamped to [0, g - 1]: THE binning rule -- the cell sort and every kernel that looks for a sample's
+// cell (pair kernels, single queries, external states) share this one definition
+__host__ __device__ __forceinline__ int mpfmt_cell_of(double x, double lo, double inv_w, int g)
+{
+    double f = floor((x - lo) * inv_w);
+    int c = (int)f;
+    if (!(f >= 0.0)) c = 0;
+    if (f >= (double)g) c = g - 1;
+    return c;
+}
 // contribution of cell coordinate c of axis i to the cell id
 __host__ __device__ __forceinline__ int64_t mpfmt_cell_term(const mpfmt_grid& G, int i, int c)
 {
@@ -397,6 +408,10 @@ struct mpfmt_ctx {
 
     // ---- adaptive shortcutting (kernels_shortcut.hip): stats of the last batch ----
     int64_t shortcut_tests = 0, shortcut_checks = 0;
+
+    // ---- roadmap queries for external states (kernels_roadmap.hip, the seeded field of kernels_sssp.hip) ----
+    mpfmt_dbuf<double> sssp_seed;         // [N] seed labels of the running pair query (+Inf: no usable edge from the start)
+    int64_t roadmap_candidates = 0, roadmap_near_total = 0;      // stats of the last call
 };
 
 // error helpers ---------------------------------------------------------------------------------
@@ -537,6 +552,23 @@ void mpfmt_wf_info_now(mpfmt_ctx* ctx, mpfmt_wf_info* info);
 // nullptr) receive the field; the labels and parents also stay in ctx->sssp_C / sssp_A
 int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, double* C_host, int64_t* A_host, mpfmt_sssp_info* info);
 void mpfmt_sssp_free(mpfmt_ctx* ctx);
+// the field of the usable seeds of one external start: entries [n] of a near list (1-based samples, distances, bits: 2 = usable) become
+// C[y] = seed[y] = fl(0 + dist); labels stay in ctx->sssp_C, parents in ctx->sssp_A (1-based, -1 = the start, 0 = none)
+int32_t mpfmt_sssp_seeded_device(mpfmt_ctx* ctx, const int64_t* d_idx1, const double* d_dist, const uint8_t* d_bits, int64_t n, const uint64_t* d_F,
+                                 mpfmt_sssp_info* info);
+
+// kernels_roadmap.hip --------------------------------------------------------------------------------
+struct mpfmt_rm_list {                   // near lists of a batch of external states, CSR, on the device (owned by the call's mpfmt_tmp)
+    int64_t* ptr = nullptr; int64_t* idx1 = nullptr; double* dist = nullptr; uint8_t* bits = nullptr;      // bits: 1 free, 2 usable
+    std::vector<int64_t> ptr_host, usable_host;
+    int64_t total = 0;
+};
+int32_t mpfmt_roadmap_grid(mpfmt_ctx* ctx);
+// count_only: ptr_host / total alone (no list is filled)
+int32_t mpfmt_roadmap_lists(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, int dir, const uint64_t* d_F, mpfmt_rm_list* out,
+                            bool count_only = false);
+int32_t mpfmt_roadmap_reduce(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, const double* d_C, double* d_cost, int64_t* d_parent);
+int32_t mpfmt_roadmap_goal(mpfmt_ctx* ctx, const mpfmt_rm_list& L, int64_t q, const double* d_C, const int64_t* d_A, int64_t* d_res);
 
 // kernels_shortcut.hip -----------------------------------------------------------------------------
 // the batch on the device; arguments already validated (mpfmt_adaptive_shortcut_batch, mpfmt_capi.hip)
