@@ -274,6 +274,66 @@ MPFMT_API int32_t mpfmt_prmstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int3
 MPFMT_API int32_t mpfmt_knn_prmstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
                           int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
 
+/* ---- a cost-to-come field kept valid across box edits: repair, not recompute (DESIGN.md "a tracked field").
+ *      Notation of the roadmap queries above: entry b of column x with row y is the edge y -> x; it is usable iff mask bit b is set
+ *      and, with checkpts, F[x] is set; the source is exempt from F; C* is the least fixed point of C[x] = min_y fl(C[y] + w_yx)
+ *      with C[s] = 0.
+ *      A TRACKED FIELD is (s, checkpts, C, A, Ab), held in buffers of its own that no other call writes: C and A are exactly what
+ *      mpfmt_graph_sssp returns for s; Ab[x] is the entry index b of the parent edge A[x] -> x (undefined for the source and for
+ *      unreached samples).
+ *      The REPAIR runs after any sequence of in-place box edits (mpfmt_boxes_add / _remove, mixed):
+ *        1. F is recomputed when checkpts is set.
+ *        2. Invalidate.  I0 = the x != s with C[x] < Inf for which mask bit Ab[x] is now clear, or checkpts is set and F[x] is clear.
+ *           I = I0 plus every descendant of I0 in the parent forest A; C[x] = +Inf on I.  I is exactly this closure.
+ *        3. Relax to a fixed point with C[x] <- min(C[x], fl(C[y] + w)) over usable entries.  Round 0 lets every column of I u D look
+ *           at all its usable rows with finite labels (D = the dirty columns: those the delta kernels flagged since the field was
+ *           last valid); later rounds are driven by which labels changed.
+ *        4. Parents by the rule of the roadmap queries (lowest (C[y], y) among achievers), a function of the final C alone; Ab is
+ *           refreshed.
+ *      The result is bit-identical to a fresh field over the edited mask (DESIGN.md has the argument).
+ * mpfmt_field_begin  : computes the field of `source` (1-based) over the resident swept graph into the tracked buffers.  The refusals of
+ *      mpfmt_graph_sssp; a refused call leaves an earlier tracked field as it was.
+ * mpfmt_field_update : the repair.  A field that lost its delta history while a swept mask exists (a box edit took the fall-back of
+ *      mpfmt_boxes_add and the mask was swept whole since) is recomputed in full: info->path = 0.  No swept mask for the current graph
+ *      and box set: MPFMT_ERR_STATE.  With nothing dirty it returns at once with zero rounds.
+ * mpfmt_field_read   : host copies of C[N] and A[N]; either pointer may be NULL.
+ * mpfmt_field_goal   : the goal extraction and walk-back of mpfmt_prmstar on the tracked field: the same res fields (status, cost, z,
+ *      path_len, nnz), collision_checks = 0; path has capacity N.  While box edits are pending (no mpfmt_field_update since) the
+ *      field is that of the previous box set: MPFMT_ERR_STATE (mpfmt_field_read hands out the field as it was last valid).
+ * mpfmt_field_drop   : forgets the field (always succeeds).
+ * The field is dropped by new samples, a new graph (another r or k, an import), mpfmt_upload_boxes, mpfmt_upload_shapes2d,
+ * mpfmt_set_state_bounds, mpfmt_set_shard and by destroying the ctx; mpfmt_field_update / _read / _goal then return MPFMT_ERR_STATE
+ * until mpfmt_field_begin.  mpfmt_graph_sssp, mpfmt_prmstar and the roadmap queries keep scratch buffers of their own and leave it alone.
+ * Unsharded ctx, Euclidean samples; the in-place edits are those of the AABB checker.
+ * mpfmt_get_stat: "field_tracked", "field_update_path" (1 repaired, 0 recomputed), "field_invalidated" (|I|), "field_dirty_columns"
+ * (|D|), "field_columns_read" (distinct columns whose entries the relaxation read, over all rounds), "field_column_visits" (the same
+ * counted once per round), "field_entries_read", "field_rounds", "field_relaxations", "field_reached".
+ * Timers: "field_invalidate", "field_relax", "field_parents".
+ * mpfmt_host_field_repair : steps 2-4 on the host over the device-native arrays (as mpfmt_host_graph_sssp), no ctx and no device:
+ *      C / A hold the old field on entry and the repaired one on return; efree / F are the NEW mask and point bitmap (F NULL:
+ *      checkpts = false), dirty the bitmap of D over samples; *invalidated receives |I| (may be NULL).  It returns what
+ *      mpfmt_host_graph_sssp returns on the new mask. */
+typedef struct {
+    int64_t reached;           /* samples with C < +Inf, the source included */
+    int64_t invalidated;       /* |I| */
+    int64_t dirty_columns;     /* |D| */
+    int64_t columns_read;      /* distinct columns whose entries the relaxation read */
+    int64_t column_visits;     /* columns read, counted once per round */
+    int64_t entries_read;      /* entries of the columns read, counted once per round (rowval + nzval: 12 bytes each) */
+    int64_t rounds;            /* relaxation rounds that ran */
+    int64_t relaxations;       /* fl(C[y] + w) evaluated; scheduling-dependent */
+    double  ms_device;         /* device time of the call */
+    int32_t path;              /* 1 repaired, 0 computed in full */
+    int32_t pad_;
+} mpfmt_field_info;
+MPFMT_API int32_t mpfmt_field_begin(mpfmt_ctx* ctx, int64_t source, int32_t checkpts, mpfmt_field_info* info);
+MPFMT_API int32_t mpfmt_field_update(mpfmt_ctx* ctx, mpfmt_field_info* info);
+MPFMT_API int32_t mpfmt_field_read(mpfmt_ctx* ctx, double* C, int64_t* A);
+MPFMT_API int32_t mpfmt_field_goal(mpfmt_ctx* ctx, int32_t goal_kind, const double* goal_params, int64_t* path, mpfmt_fmt_result* res);
+MPFMT_API int32_t mpfmt_field_drop(mpfmt_ctx* ctx);
+MPFMT_API int32_t mpfmt_host_field_repair(int64_t N, const int64_t* colptr, const int32_t* rowval, const double* nzval, const uint64_t* efree,
+                                const uint64_t* F, const uint64_t* dirty, int64_t source, double* C, int64_t* A, int64_t* invalidated);
+
 /* ---- roadmap queries for external states: start and goal states that are NOT samples (the robot's present pose, a batch of candidate
  *      goals) are attached to the resident roadmap instead of being appended to the sample set (which would rebuild graph and mask).
  *      The ctx holds an unsharded, swept r-disc graph of radius r = its graph radius (built or imported); the checker is the N-D AABB

@@ -236,6 +236,41 @@ function hip_roadmap_attach(DS::HIPDistanceDS, Q::Matrix{Float64}, C::Vector{Flo
     cost, parent
 end
 
+# ---- a cost-to-come field kept valid across box edits (include/mpfmt.h): hip_prmstar!(P, r) computes a field and throws it away;
+#      hip_field_begin! keeps the field of init_idx in the ctx, and after mpfmt_boxes_add / _remove (INTEGRATION.md, "obstacles that
+#      change") hip_replan! repairs it -- work that follows the edit -- and extracts goal and path again.  The C caller that executes
+#      these calls with the same widths is tests/abi_c/abi_caller7.c. ----
+const sym_field_begin = :mpfmt_field_begin
+const sym_field_update = :mpfmt_field_update
+const sym_field_read = :mpfmt_field_read
+const sym_field_goal = :mpfmt_field_goal
+const sym_field_drop = :mpfmt_field_drop
+immutable FieldInfo
+    reached::Int64; invalidated::Int64; dirty_columns::Int64; columns_read::Int64; column_visits::Int64; entries_read::Int64
+    rounds::Int64; relaxations::Int64; ms_device::Float64; path::Int32; pad::Int32
+end
+function hip_field_begin!(DS::HIPDistanceDS; init_idx = 1, checkpts = true)
+    info = Ref{FieldInfo}()
+    chk(DS.ctx, ccall((sym_field_begin, libmpfmt), Int32, (Ptr{Void}, Int64, Int32, Ptr{FieldInfo}), DS.ctx, init_idx, checkpts, info))
+    info[]
+end
+hip_field_drop!(DS::HIPDistanceDS) = chk(DS.ctx, ccall((sym_field_drop, libmpfmt), Int32, (Ptr{Void},), DS.ctx))
+# after the box edits: repair (info.path == 1) or, where an edit could not be applied in place, recompute (0); then goal and path
+function hip_replan!(P::MPProblem)
+    DS = P.V.DS; N = length(P.V)
+    info = Ref{FieldInfo}()
+    chk(DS.ctx, ccall((sym_field_update, libmpfmt), Int32, (Ptr{Void}, Ptr{FieldInfo}), DS.ctx, info))
+    A = Vector{Int}(N); C = Vector{Float64}(N); path = Vector{Int}(N); res = Ref{FmtResult}()
+    g = [P.goal.center; P.goal.radius]           # BallGoal (goals.jl:17-21) = MPFMT_GOAL_BALL
+    chk(DS.ctx, ccall((sym_field_goal, libmpfmt), Int32, (Ptr{Void}, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{FmtResult}), DS.ctx, 1, g, path, res))
+    chk(DS.ctx, ccall((sym_field_read, libmpfmt), Int32, (Ptr{Void}, Ptr{Float64}, Ptr{Int64}), DS.ctx, C, A))
+    P.status = res[].status == 1 ? :solved : :failed
+    P.solution = MPSolution(P.status, res[].cost, (info[].ms_device + res[].ms_host_loop) / 1e3,
+                            Dict("collision_checks" => 0, "tree" => A, "cost" => res[].cost, "path" => path[1:res[].path_len],
+                                 "planner" => "prmstar", "num_samples" => N, "cost_to_come" => C, "field_info" => info[]))
+    P.status, P.solution.cost, P.solution.elapsed
+end
+
 # ---- post-processing: adaptive_shortcut!(P, iterations) (src/postprocessors.jl:41-50) on the device; the checker of P.V.DS.ctx is the
 #      one the last upload bound (hip_bind! / the planner calls).  max_states bounds the working path (include/mpfmt.h).
 const sym_adaptive_shortcut = :mpfmt_adaptive_shortcut

@@ -45,6 +45,12 @@ class SsspInfo(C.Structure):
     _fields_ = [("reached", C.c_int64), ("rounds", C.c_int64), ("relaxations", C.c_int64), ("ms_device", C.c_double)]
 
 
+class FieldInfo(C.Structure):
+    _fields_ = [("reached", C.c_int64), ("invalidated", C.c_int64), ("dirty_columns", C.c_int64), ("columns_read", C.c_int64),
+                ("column_visits", C.c_int64), ("entries_read", C.c_int64), ("rounds", C.c_int64), ("relaxations", C.c_int64),
+                ("ms_device", C.c_double), ("path", C.c_int32), ("pad_", C.c_int32)]
+
+
 class ShortcutInfo(C.Structure):
     _fields_ = [("status", C.c_int32), ("iterations_done", C.c_int32), ("n_out", C.c_int64), ("max_working_len", C.c_int64),
                 ("max_halvings", C.c_int64), ("collision_checks", C.c_int64), ("tests_evaluated", C.c_int64)]
@@ -96,6 +102,13 @@ SYMBOLS = [
                                              C.POINTER(FmtResult)]),
     ("mpfmt_host_graph_sssp", C.c_int32, [C.c_int64, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p, C.c_int64, c_d_p, c_i64_p]),
     ("mpfmt_graph_sssp", C.c_int32, [C.c_void_p, c_i64_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(SsspInfo)]),
+    ("mpfmt_field_begin", C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(FieldInfo)]),
+    ("mpfmt_field_update", C.c_int32, [C.c_void_p, C.POINTER(FieldInfo)]),
+    ("mpfmt_field_read", C.c_int32, [C.c_void_p, c_d_p, c_i64_p]),
+    ("mpfmt_field_goal", C.c_int32, [C.c_void_p, C.c_int32, c_d_p, c_i64_p, C.POINTER(FmtResult)]),
+    ("mpfmt_field_drop", C.c_int32, [C.c_void_p]),
+    ("mpfmt_host_field_repair", C.c_int32, [C.c_int64, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p, c_u64_p, C.c_int64, c_d_p, c_i64_p,
+                                            c_i64_p]),
     ("mpfmt_prmstar", C.c_int32, [C.c_void_p, C.c_double, C.c_int64, C.c_int32, C.c_int32, c_d_p, c_i64_p, c_d_p, c_i64_p,
                                   C.POINTER(FmtResult)]),
     ("mpfmt_knn_prmstar", C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_d_p, c_i64_p, c_d_p, c_i64_p,
@@ -313,6 +326,35 @@ def host_graph_sssp(colptr0, rowval0, nzval, efree, F=None, source=1, want_paren
     if rc != 0:
         raise MPFMTError(rc, "mpfmt_host_graph_sssp rejected its arguments")
     return Cc[:N], (None if A is None else A[:N])
+
+
+def host_field_repair(colptr0, rowval0, nzval, efree, F, dirty, C_old, A_old, source=1):
+    """The repair of a tracked field on the host (include/mpfmt.h, "a cost-to-come field kept valid across box edits"), no GPU needed:
+    the old field (C_old, A_old) of `source` (1-based), the NEW mask efree and point bitmap F (None: checkpts=false), the bitmap
+    `dirty` of the columns the edits flagged (packed uint64 over samples).  Returns (C, A, invalidated)."""
+    colptr0 = np.ascontiguousarray(colptr0, dtype=np.int64)
+    N = colptr0.size - 1
+    rowval0 = np.ascontiguousarray(rowval0, dtype=np.int32)
+    nzval = np.ascontiguousarray(nzval, dtype=np.float64)
+    efree = np.ascontiguousarray(efree, dtype=np.uint64)
+    Fp = None if F is None else np.ascontiguousarray(F, dtype=np.uint64)
+    dirty = np.ascontiguousarray(dirty, dtype=np.uint64)
+    if dirty.size < nwords(N):
+        raise ValueError("dirty must hold one bit per sample")
+    Cc = np.array(C_old, dtype=np.float64).reshape(-1).copy()
+    A = np.array(A_old, dtype=np.int64).reshape(-1).copy()
+    if Cc.size != N or A.size != N:
+        raise ValueError("C_old / A_old must have N entries")
+    inv = np.zeros(1, dtype=np.int64)
+    rc = lib().mpfmt_host_field_repair(N, _ip(colptr0), rowval0.ctypes.data_as(C.POINTER(C.c_int32)), _dp(nzval), _up(efree), _up(Fp), _up(dirty),
+                                       int(source), _dp(Cc), _ip(A), _ip(inv))
+    if rc != 0:
+        raise MPFMTError(rc, "mpfmt_host_field_repair rejected its arguments")
+    return Cc, A, int(inv[0])
+
+
+def _field_info(i):
+    return {k: getattr(i, k) for k, _ in FieldInfo._fields_ if k != "pad_"}
 
 
 def _roadmap_info(i):
@@ -642,6 +684,46 @@ class Context:
         self._chk(self._L.mpfmt_graph_sssp(self._h, _ip(src), n, int(bool(checkpts)), _dp(Cc), _ip(A), info))
         return dict(C=Cc[:n, :self.N], A=None if A is None else A[:n, :self.N],
                     info=[{k: getattr(info[i], k) for k, _ in SsspInfo._fields_} for i in range(n)])
+
+    # ---- a cost-to-come field kept valid across box edits (include/mpfmt.h) ---------------------------------------------------
+    def field_begin(self, source=1, checkpts=True):
+        """Compute the field of `source` (1-based) over the resident swept graph into buffers the context keeps (mpfmt_field_begin);
+        returns the info dict (reached, invalidated, dirty_columns, columns_read, column_visits, entries_read, rounds, relaxations,
+        ms_device, path)."""
+        info = FieldInfo()
+        self._chk(self._L.mpfmt_field_begin(self._h, int(source), int(bool(checkpts)), C.byref(info)))
+        return _field_info(info)
+
+    def field_update(self):
+        """Repair the tracked field after boxes_add / boxes_remove (mpfmt_field_update): info["path"] = 1 repaired, 0 recomputed."""
+        info = FieldInfo()
+        self._chk(self._L.mpfmt_field_update(self._h, C.byref(info)))
+        return _field_info(info)
+
+    def field_read(self, want_parents=True):
+        """Host copies (C, A) of the tracked field: C = +Inf for unreached samples, A 1-based parents (None without want_parents)."""
+        Cc = np.empty(max(self.N, 1), dtype=np.float64)
+        A = np.empty(max(self.N, 1), dtype=np.int64) if want_parents else None
+        self._chk(self._L.mpfmt_field_read(self._h, _dp(Cc), _ip(A)))
+        return Cc[:self.N], (None if A is None else A[:self.N])
+
+    def field_goal(self, goal_kind, goal_params):
+        """The goal extraction and walk-back of prmstar on the tracked field: dict(status, cost, z, collision_checks = 0, nnz,
+        ms_host_loop, path)."""
+        g = np.ascontiguousarray(goal_params, dtype=np.float64)
+        path = np.empty(max(self.N, 1), dtype=np.int64)
+        res = FmtResult()
+        self._chk(self._L.mpfmt_field_goal(self._h, int(goal_kind), _dp(g), _ip(path), C.byref(res)))
+        return dict(status=int(res.status), cost=float(res.cost), z=int(res.z), collision_checks=int(res.collision_checks),
+                    nnz=int(res.nnz), ms_host_loop=res.ms_host_loop, path=path[:res.path_len].copy())
+
+    def field_drop(self):
+        self._chk(self._L.mpfmt_field_drop(self._h))
+
+    @staticmethod
+    def host_field_repair(colptr0, rowval0, nzval, efree, F, dirty, C_old, A_old, source=1):
+        """The module's host_field_repair (no device)."""
+        return host_field_repair(colptr0, rowval0, nzval, efree, F, dirty, C_old, A_old, source=source)
 
     # ---- roadmap queries for states that are not samples (include/mpfmt.h, "roadmap queries for external states") ----------
     def _states(self, Q):

@@ -390,7 +390,7 @@ int32_t mpfmt_knn_build(mpfmt_ctx* ctx, int64_t k)
     ctx->nnz = nnz;
     // the sweep culls the obstacles of a column with the graph's radius: every entry of this graph is at most `longest` long
     ctx->graph_r = longest * (1.0 + 1e-9);
-    ctx->graph_counted = ctx->graph_filled = true;
+    ctx->graph_counted = ctx->graph_filled = true; ctx->graph_epoch += 1; ctx->graph_imported = false;
     ctx->knn_k = k;
     return MPFMT_OK;
 }

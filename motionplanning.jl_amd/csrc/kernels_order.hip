@@ -388,7 +388,7 @@ int32_t mpfmt_order_logs(mpfmt_ctx* ctx, const int32_t* spec_fail, int64_t mask_
             HIPCHK(ctx, hipMemsetAsync(ctx->graph_free, ctx->nnz > 0 ? 0xFF : 0, sizeof(uint64_t) * (size_t)std::max<int64_t>(words, 1), ctx->stream));
     }
     ctx->mask_preset_words = -1;
-    if (ctx->nnz == 0 || nt <= 0) { if ((rc = mpfmt_side_join(ctx))) return rc; if (recbits) { ctx->graph_swept = true; ctx->sweep_in_order = true; } return MPFMT_OK; }
+    if (ctx->nnz == 0 || nt <= 0) { if ((rc = mpfmt_side_join(ctx))) return rc; if (recbits) { ctx->graph_swept = true; ctx->sweep_epoch += 1; ctx->sweep_in_order = true; } return MPFMT_OK; }
     // also keep every row's cell-sorted position, so the whole sweep can gather from Xs (see kernels_sweep.hip)
     const bool want_rowpos = !pend && !recbits;
     if (want_rowpos && (rc = ctx->rowpos.ensure(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(std::max(ctx->nnz, ctx->nnz_cap), 1)))) return rc;
@@ -435,6 +435,6 @@ int32_t mpfmt_order_logs(mpfmt_ctx* ctx, const int32_t* spec_fail, int64_t mask_
     if (pend) ctx->pend_nseg = (int)nb;
     ctx->pend_valid = pend;                                   // the flagged entries have been listed for k_sweep_pending
     ctx->rowpos_valid = want_rowpos;                          // every entry's row is also known by its cell-sorted position (the sweep gathers from Xs)
-    if (recbits) { ctx->graph_swept = true; ctx->sweep_in_order = true; }
+    if (recbits) { ctx->graph_swept = true; ctx->sweep_epoch += 1; ctx->sweep_in_order = true; }
     return MPFMT_OK;
 }

@@ -1352,7 +1352,7 @@ int32_t mpfmt_launch_rdisc_fill(mpfmt_ctx* ctx, double r)
             tm6.end("rdisc_sort");
         }
     }
-    ctx->graph_filled = true;
+    ctx->graph_filled = true; ctx->graph_epoch += 1; ctx->graph_imported = false;
     return MPFMT_OK;
 }
 
@@ -1433,7 +1433,7 @@ int32_t mpfmt_graph_step_launch_impl(mpfmt_ctx* ctx, double r)
             ctx->graph_swept = false;
             if ((rc = mpfmt_order_logs(ctx, ctx->spec_fail, cap))) return rc;
             tm7.end("rdisc_sort");
-            ctx->graph_filled = true;
+            ctx->graph_filled = true; ctx->graph_epoch += 1; ctx->graph_imported = false;
             // (form 2 of the fused edge tests: the ordering pass has written the mask already)
             if (!ctx->graph_swept && (rc = mpfmt_launch_graph_sweep(ctx, ctx->spec_fail, cap))) return rc;
             ctx->step_state = 1;                                    // speculative kernels in flight
@@ -1473,6 +1473,7 @@ static int32_t step_finish_inner(mpfmt_ctx* ctx)
         if ((rc = mpfmt_rdisc_count_finish(ctx, r, &failed))) return rc;
         if (!failed && ctx->nnz < ctx->nnz_cap && ctx->pool_valid) {
             ctx->graph_filled = true; ctx->graph_swept = true;      // (finish resets the flags it owns)
+            ctx->graph_epoch += 1; ctx->sweep_epoch += 1; ctx->graph_imported = false;
             ctx->deg_zero_valid = ctx->world > 1;                   // (the ordering pass ran: the shard's degree entries are zero again)
             if (ctx->pend_overflowed) {                             // the pending-entry / pending-pair list was cut short: sweep the whole graph
                 ctx->redo_reason |= 16; ctx->redo_count += 1;

@@ -1895,7 +1895,7 @@ int32_t mpfmt_launch_graph_sweep(mpfmt_ctx* ctx, const int32_t* spec_fail, int64
         rc = mpfmt_2d_launch_graph(ctx);
         tm6.end("sweep_graph");
         if (rc) return rc;
-        ctx->graph_swept = true;
+        ctx->graph_swept = true; ctx->sweep_epoch += 1;
         return MPFMT_OK;
     }
     mpfmt_timed tm7(ctx);
@@ -1911,7 +1911,7 @@ int32_t mpfmt_launch_graph_sweep(mpfmt_ctx* ctx, const int32_t* spec_fail, int64
         tk.end("sweep_kernel");
         if (rc) return rc;
         tm7.end("sweep_graph");
-        ctx->graph_swept = true;
+        ctx->graph_swept = true; ctx->sweep_epoch += 1;
         ctx->sweep_pending_used = true;
         return MPFMT_OK;
     }
@@ -1946,6 +1946,6 @@ int32_t mpfmt_launch_graph_sweep(mpfmt_ctx* ctx, const int32_t* spec_fail, int64
         HIPCHK(ctx, hipGetLastError());
     }
     tm7.end("sweep_graph");
-    ctx->graph_swept = true;
+    ctx->graph_swept = true; ctx->sweep_epoch += 1;
     return MPFMT_OK;
 }

@@ -230,6 +230,7 @@ int32_t mpfmt_set_shard(mpfmt_ctx* ctx, int32_t rank, int32_t world)
     if (!ctx) return MPFMT_ERR_ARG;
     if (world < 1 || rank < 0 || rank >= world) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "bad shard %d of %d", rank, world);
     ctx->rank = rank; ctx->world = world;
+    mpfmt_field_drop_internal(ctx);
     ctx->deg_zero_valid = false;
     ctx->grid_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0;      // (the cell order and the built part of the index belong to the shard)
     ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
@@ -320,6 +321,7 @@ static int32_t adopt_samples(mpfmt_ctx* ctx, const double* src, bool src_on_host
     // accepted: the new buffer becomes the ctx's sample set (the two members change places, capacities with them)
     ctx->Xo.swap(ctx->Xo_next);
     ctx->samples_epoch += 1;
+    mpfmt_field_drop_internal(ctx);
     ctx->grid_r = -1.0; ctx->graph_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0;
     ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
     ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
@@ -361,6 +363,7 @@ int32_t mpfmt_set_state_bounds(mpfmt_ctx* ctx, const double* ss_lo, const double
     for (int i = 0; i < MPFMT_MAX_DIM; ++i) { ctx->ss.lo[i] = -INFINITY; ctx->ss.hi[i] = INFINITY; }
     if (ss_lo) for (int i = 0; i < d_state; ++i) { ctx->ss.lo[i] = ss_lo[i]; ctx->ss.hi[i] = ss_hi[i]; }
     ctx->graph_swept = false; ctx->steer_swept = false; ctx->pend_valid = false;     // (a pending list belongs to the obstacle set it was made against)
+    mpfmt_field_drop_internal(ctx);
     return MPFMT_OK;
 }
 
@@ -386,6 +389,7 @@ int32_t mpfmt_upload_boxes(mpfmt_ctx* ctx, const double* lohi, int32_t M, int32_
     if (ss_lo) for (int i = 0; i < d_state; ++i) { ctx->ss.lo[i] = ss_lo[i]; ctx->ss.hi[i] = ss_hi[i]; }
     ctx->graph_swept = false; ctx->pend_valid = false;
     ctx->steer_swept = false;
+    mpfmt_field_drop_internal(ctx);
     return MPFMT_OK;
 }
 
@@ -406,8 +410,8 @@ static int32_t boxes_delta_finish(mpfmt_ctx* ctx, const double* d_delta, int32_t
     ctx->bd_path = boxes_delta_in_place(ctx) ? 1 : 0;
     if (!ctx->bd_path) { ctx->graph_swept = false; return MPFMT_OK; }
     const int32_t rc = mpfmt_boxdelta_apply(ctx, d_delta, nd, remove);
-    if (rc) { ctx->graph_swept = false; ctx->bd_path = 0; }   // (the list stands, the mask is swept again)
-    return rc;
+    if (rc) { ctx->graph_swept = false; ctx->bd_path = 0; return rc; }   // (the list stands, the mask is swept again)
+    return mpfmt_field_mark_dirty(ctx);                      // (a tracked field learns which columns the edit read)
 }
 
 int32_t mpfmt_boxes_add(mpfmt_ctx* ctx, const double* lohi, int32_t M_add)
@@ -610,6 +614,8 @@ int32_t mpfmt_graph_import(mpfmt_ctx* ctx, double r, const int64_t* colptr, cons
     ctx->nnz = nnz;
     ctx->graph_r = r;
     ctx->graph_counted = ctx->graph_filled = true; ctx->knn_k = 0;
+    ctx->graph_epoch += 1; ctx->graph_imported = true;
+    mpfmt_field_drop_internal(ctx);
     ctx->graph_swept = false; ctx->pend_valid = false;
     ctx->pool_valid = false;
     ctx->rowpos_valid = false;
@@ -1375,6 +1381,111 @@ int32_t mpfmt_graph_sssp(mpfmt_ctx* ctx, const int64_t* sources, int64_t nsrc, i
     for (int64_t q = 0; q < nsrc; ++q)
         if ((rc = mpfmt_sssp_device(ctx, sources[q] - 1, checkpts ? ctx->sssp_F : nullptr, C + q * N, A ? A + q * N : nullptr, info ? info + q : nullptr)))
             return rc;
+    return MPFMT_OK;
+}
+
+// ---- a tracked field: kept valid across in-place box edits (kernels_field.hip) -----------------------------------------------------------
+
+int32_t mpfmt_field_begin(mpfmt_ctx* ctx, int64_t source, int32_t checkpts, mpfmt_field_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    int32_t rc;
+    if ((rc = sssp_ready(ctx))) return rc;
+    if (checkpts && !ctx->have_boxes && ctx->cc_kind == 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "checkpts needs an obstacle set");
+    if ((rc = check_idx(ctx, &source, 1, "source"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (checkpts && (rc = sssp_point_bitmap(ctx))) return rc;
+    return mpfmt_field_compute(ctx, source - 1, checkpts ? 1 : 0, checkpts ? ctx->sssp_F.get() : nullptr, info);
+}
+
+int32_t mpfmt_field_update(mpfmt_ctx* ctx, mpfmt_field_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!mpfmt_field_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked field (mpfmt_field_begin)");
+    int32_t rc;
+    if ((rc = sssp_ready(ctx))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const bool history = mpfmt_field_history(ctx);                       // no build and no whole sweep since the field was last valid
+    if (history && !ctx->fld_dirty_any) {                                 // nothing was flagged: the field stands
+        ctx->fld_path = 1;
+        ctx->fld_invalidated = ctx->fld_dirty_columns = ctx->fld_columns_read = ctx->fld_column_visits = ctx->fld_entries_read = 0;
+        ctx->fld_rounds = ctx->fld_relax = 0;
+        if (info) {
+            memset(info, 0, sizeof *info);
+            info->reached = ctx->fld_reached; info->path = 1;
+        }
+        return MPFMT_OK;
+    }
+    const int32_t checkpts = ctx->fld_checkpts;
+    if (checkpts && (rc = sssp_point_bitmap(ctx))) return rc;
+    const uint64_t* d_F = checkpts ? ctx->sssp_F.get() : nullptr;
+    if (!history) return mpfmt_field_compute(ctx, ctx->fld_source0, checkpts, d_F, info);
+    if ((rc = mpfmt_field_repair(ctx, d_F, info))) { mpfmt_field_drop_internal(ctx); return rc; }      // (a repair cut short leaves no field)
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_field_read(mpfmt_ctx* ctx, double* C, int64_t* A)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!mpfmt_field_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked field (mpfmt_field_begin)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t N = (size_t)ctx->N;
+    if (C) HIPCHK(ctx, hipMemcpyAsync(C, ctx->fld_C, sizeof(double) * N, hipMemcpyDeviceToHost, ctx->stream));
+    if (A) HIPCHK(ctx, hipMemcpyAsync(A, ctx->fld_A, sizeof(int64_t) * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_field_goal(mpfmt_ctx* ctx, int32_t goal_kind, const double* goal_params, int64_t* path, mpfmt_fmt_result* res)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
+    if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
+    if (!mpfmt_field_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked field (mpfmt_field_begin)");
+    if (ctx->fld_dirty_any || !mpfmt_field_history(ctx) || !ctx->graph_swept)
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the box set was edited since the tracked field was last valid (mpfmt_field_update)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int64_t N = ctx->N, init_idx = ctx->fld_source0 + 1;
+    const int d = ctx->d;
+    memset(res, 0, sizeof *res);
+    const stamp t0 = now();
+    std::vector<double> X((size_t)N * d), C((size_t)N);
+    std::vector<int64_t> A((size_t)N);
+    HIPCHK(ctx, hipMemcpyAsync(X.data(), ctx->Xo, sizeof(double) * (size_t)N * d, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(C.data(), ctx->fld_C, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(A.data(), ctx->fld_A, sizeof(int64_t) * (size_t)N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    // goal node: the reached sample inside the goal region of lowest (C, index) (prmstar_impl)
+    int64_t z = -1;
+    for (int64_t i = 0; i < N; ++i)
+        if (C[i] < INFINITY && (z < 0 || C[i] < C[z]) && mpfmt_is_goal_pt(&X[(size_t)i * d], d, goal_kind, goal_params)) z = i;
+    std::vector<int64_t> rev;
+    if (z >= 0) {
+        int64_t cur = z;
+        rev.push_back(cur + 1);
+        while (cur != init_idx - 1 && (int64_t)rev.size() <= N) {
+            const int64_t p = A[cur];
+            if (p == 0) break;
+            cur = p - 1;
+            rev.push_back(cur + 1);
+        }
+        res->status = 1; res->cost = C[z]; res->z = z + 1;
+    } else {
+        rev.push_back(init_idx);
+        res->status = 0; res->cost = INFINITY; res->z = init_idx;
+    }
+    for (size_t i = 0; i < rev.size() && i < (size_t)N; ++i) path[i] = rev[rev.size() - 1 - i];
+    res->path_len = (int64_t)std::min<size_t>(rev.size(), (size_t)N);
+    res->collision_checks = 0;
+    res->nnz = ctx->nnz;
+    res->ms_host_loop = std::chrono::duration<double, std::milli>(now() - t0).count();
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_field_drop(mpfmt_ctx* ctx)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    mpfmt_field_drop_internal(ctx);
     return MPFMT_OK;
 }
 
@@ -2180,6 +2291,16 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "boxes_delta_path") == 0) { *value = ctx->bd_path; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_columns") == 0) { *value = ctx->bd_columns; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_entries") == 0) { *value = ctx->bd_entries; return MPFMT_OK; }
+    if (strcmp(name, "field_tracked") == 0) { *value = mpfmt_field_live(ctx) ? 1 : 0; return MPFMT_OK; }
+    if (strcmp(name, "field_update_path") == 0) { *value = ctx->fld_path; return MPFMT_OK; }
+    if (strcmp(name, "field_invalidated") == 0) { *value = ctx->fld_invalidated; return MPFMT_OK; }
+    if (strcmp(name, "field_dirty_columns") == 0) { *value = ctx->fld_dirty_columns; return MPFMT_OK; }
+    if (strcmp(name, "field_columns_read") == 0) { *value = ctx->fld_columns_read; return MPFMT_OK; }
+    if (strcmp(name, "field_column_visits") == 0) { *value = ctx->fld_column_visits; return MPFMT_OK; }
+    if (strcmp(name, "field_entries_read") == 0) { *value = ctx->fld_entries_read; return MPFMT_OK; }
+    if (strcmp(name, "field_rounds") == 0) { *value = ctx->fld_rounds; return MPFMT_OK; }
+    if (strcmp(name, "field_relaxations") == 0) { *value = ctx->fld_relax; return MPFMT_OK; }
+    if (strcmp(name, "field_reached") == 0) { *value = ctx->fld_reached; return MPFMT_OK; }
     if (strcmp(name, "boxes") == 0) { *value = ctx->have_boxes ? ctx->M : 0; return MPFMT_OK; }
     if (strcmp(name, "graph_swept") == 0) { *value = ctx->graph_swept ? 1 : 0; return MPFMT_OK; }
     if (strcmp(name, "survivors") == 0) { *value = ctx->survivors; return MPFMT_OK; }

@@ -343,6 +343,110 @@ int32_t mpfmt_host_graph_sssp(int64_t N, const int64_t* colptr, const int32_t* r
     return MPFMT_OK;
 }
 
+// The repair of a tracked field on the host (include/mpfmt.h, "a cost-to-come field kept valid across box edits"): steps 2-4 over the
+// device-native arrays.  C / A hold the old field; efree / F are the new mask and point bitmap; dirty marks the columns the edits
+// flagged.  I0 is tested on the dirty columns through the parent's entry (rows are distinct inside a column: the entry of A[x] is the
+// one whose row is A[x]); the closure walks the children lists of the parent forest; the heap is seeded from the boundary -- every
+// column of I u D looks at all its usable rows with finite labels -- and then corrects labels in key order.  Parents are those of
+// mpfmt_host_graph_sssp, from the final labels alone.
+int32_t mpfmt_host_field_repair(int64_t N, const int64_t* colptr, const int32_t* rowval, const double* nzval, const uint64_t* efree,
+                                const uint64_t* F, const uint64_t* dirty, int64_t source, double* C, int64_t* A, int64_t* invalidated)
+{
+    if (!colptr || !efree || !dirty || !C || !A || N < 1 || source < 1 || source > N) return MPFMT_ERR_ARG;
+    if (colptr[0] != 0) return MPFMT_ERR_ARG;
+    for (int64_t j = 0; j < N; ++j) if (colptr[j + 1] < colptr[j]) return MPFMT_ERR_ARG;
+    const int64_t nnz = colptr[N];
+    if (nnz > 0 && (!rowval || !nzval)) return MPFMT_ERR_ARG;
+    for (int64_t e = 0; e < nnz; ++e) if (rowval[e] < 0 || rowval[e] >= N || !(nzval[e] >= 0.0)) return MPFMT_ERR_ARG;
+    for (int64_t x = 0; x < N; ++x) if (A[x] < 0 || A[x] > N || !(C[x] >= 0.0)) return MPFMT_ERR_ARG;
+    auto bitp = [](const uint64_t* m, int64_t i) { return (m[i >> 6] >> (i & 63)) & 1ull; };
+    const int64_t s = source - 1;
+    // step 2: I0 on the dirty columns, then its descendants
+    std::vector<char> inI((size_t)N, 0);
+    std::vector<int64_t> stack;
+    for (int64_t x = 0; x < N; ++x) {
+        if (!bitp(dirty, x) || x == s || !(C[x] < INFINITY)) continue;
+        bool lost = F && !bitp(F, x);
+        if (!lost) {
+            lost = true;                                                       // (no entry with the parent's row: the edge is gone)
+            for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b)
+                if (rowval[b] == A[x] - 1) { lost = !bitp(efree, b); break; }
+        }
+        if (lost) { inI[x] = 1; stack.push_back(x); }
+    }
+    std::vector<int64_t> cptr((size_t)N + 1, 0);
+    for (int64_t x = 0; x < N; ++x) if (x != s && C[x] < INFINITY && A[x] > 0) cptr[A[x]]++;
+    for (int64_t i = 0; i < N; ++i) cptr[i + 1] += cptr[i];
+    std::vector<int64_t> ccur(cptr.begin(), cptr.end() - 1), child((size_t)std::max<int64_t>(cptr[N], 1));
+    for (int64_t x = 0; x < N; ++x) if (x != s && C[x] < INFINITY && A[x] > 0) child[ccur[A[x] - 1]++] = x;
+    int64_t nI = (int64_t)stack.size();
+    while (!stack.empty()) {
+        const int64_t p = stack.back(); stack.pop_back();
+        for (int64_t a = cptr[p]; a < cptr[p + 1]; ++a) {
+            const int64_t x = child[a];
+            if (!inI[x]) { inI[x] = 1; ++nI; stack.push_back(x); }
+        }
+    }
+    for (int64_t x = 0; x < N; ++x) if (inI[x]) C[x] = INFINITY;
+    if (invalidated) *invalidated = nI;
+    // out-edges of every sample: the usable entries only (free bit set, target allowed by F)
+    std::vector<int64_t> rowptr((size_t)N + 1, 0);
+    for (int64_t x = 0; x < N; ++x) {
+        if (F && !bitp(F, x)) continue;
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b) if (bitp(efree, b)) rowptr[rowval[b] + 1]++;
+    }
+    for (int64_t i = 0; i < N; ++i) rowptr[i + 1] += rowptr[i];
+    std::vector<int64_t> cur(rowptr.begin(), rowptr.end() - 1);
+    std::vector<int32_t> tgt((size_t)std::max<int64_t>(rowptr[N], 1));
+    std::vector<double> wgt((size_t)std::max<int64_t>(rowptr[N], 1));
+    for (int64_t x = 0; x < N; ++x) {
+        if (F && !bitp(F, x)) continue;
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b)
+            if (bitp(efree, b)) { const int64_t a = cur[rowval[b]]++; tgt[a] = (int32_t)x; wgt[a] = nzval[b]; }
+    }
+    // step 3: the boundary seeds the heap, then labels are corrected in key order
+    Heap heap;
+    for (int64_t x = 0; x < N; ++x) {
+        if (!(inI[x] || bitp(dirty, x)) || x == s) continue;
+        if (F && !bitp(F, x)) continue;
+        double best = C[x];
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b) {
+            if (!bitp(efree, b)) continue;
+            const double cy = C[rowval[b]];
+            if (!(cy < INFINITY) || inI[rowval[b]]) continue;
+            const double c = cy + nzval[b];
+            if (c < best) best = c;
+        }
+        if (best < C[x]) { C[x] = best; heap.push(x, best); }
+    }
+    while (!heap.empty()) {
+        const double cy = heap.pri[0];
+        const int64_t y = heap.pop();
+        if (cy > C[y]) continue;
+        for (int64_t a = rowptr[y]; a < rowptr[y + 1]; ++a) {
+            const int64_t x = tgt[a];
+            if (x == s) continue;
+            const double c = cy + wgt[a];
+            if (c < C[x]) { C[x] = c; heap.push(x, c); }
+        }
+    }
+    // step 4
+    for (int64_t x = 0; x < N; ++x) {
+        A[x] = 0;
+        if (x == s || !(C[x] < INFINITY)) continue;
+        int64_t yb = -1; double cb = 0.0;
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b) {
+            if (!bitp(efree, b)) continue;
+            const int64_t y = rowval[b];
+            const double cy = C[y];
+            if (!(cy + nzval[b] == C[x])) continue;
+            if (yb < 0 || cy < cb || (cy == cb && y < yb)) { yb = y; cb = cy; }
+        }
+        A[x] = yb + 1;
+    }
+    return MPFMT_OK;
+}
+
 // ImmutableNNC(D, r) handed in from outside (mpfmt_graph_import; nearneighbors.jl:23-28): 1-based CSC, monotone colptr,
 // rows in range, strictly ascending inside a column, no self loops.  Returns 0, or the 1-based column at fault (negative:
 // -1 colptr[1] != 1, -2 colptr decreases) with a message in err.

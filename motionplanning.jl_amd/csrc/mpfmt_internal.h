@@ -412,6 +412,28 @@ struct mpfmt_ctx {
     // ---- roadmap queries for external states (kernels_roadmap.hip, the seeded field of kernels_sssp.hip) ----
     mpfmt_dbuf<double> sssp_seed;         // [N] seed labels of the running pair query (+Inf: no usable edge from the start)
     int64_t roadmap_candidates = 0, roadmap_near_total = 0;      // stats of the last call
+
+    // ---- tracked cost-to-come field (kernels_field.hip): buffers of its own that no other call writes ----
+    // graph_epoch counts the graph builds (bumped wherever a graph becomes filled), sweep_epoch the whole sweeps of the mask (bumped wherever
+    // graph_swept becomes true).  A tracked field belongs to one sample set and one graph identity (radius or k; an import drops it); it
+    // keeps its delta history -- Ab and the dirty bitmap mean something -- only while neither a build nor a whole sweep intervened
+    int64_t graph_epoch = 0, sweep_epoch = 0;
+    bool graph_imported = false;         // the resident r-disc graph came through mpfmt_graph_import: its symmetry is the caller's word only
+    mpfmt_dbuf<double> fld_C;             // [N] labels
+    mpfmt_dbuf<int64_t> fld_A;            // [N] 1-based parents
+    mpfmt_dbuf<int64_t> fld_Ab;           // [N] entry index of the parent edge (undefined where A == 0)
+    mpfmt_dbuf<uint64_t> fld_bm;          // [4][ceil(N/64)]: dirty columns (the repair's "seen" set while it runs) | the ring of three
+    mpfmt_dbuf<void> fld_state;           // field_state (device) and its pinned host mirror
+    mpfmt_hbuf<void> fld_state_host;
+    bool fld_tracked = false;
+    int64_t fld_source0 = -1; int32_t fld_checkpts = 0;
+    int64_t fld_samples_epoch = -1, fld_graph_epoch = -1, fld_sweep_epoch = -1, fld_N = 0, fld_knn_k = 0;
+    double fld_graph_r = -1.0;
+    bool fld_dirty_any = false;          // a delta call has flagged columns since the field was last valid
+    // stats of the last mpfmt_field_begin / _update
+    int32_t fld_path = 0;
+    int64_t fld_invalidated = 0, fld_dirty_columns = 0, fld_columns_read = 0, fld_column_visits = 0, fld_entries_read = 0, fld_rounds = 0,
+            fld_relax = 0, fld_reached = 0;
 };
 
 // error helpers ---------------------------------------------------------------------------------
@@ -552,6 +574,13 @@ void mpfmt_wf_info_now(mpfmt_ctx* ctx, mpfmt_wf_info* info);
 // nullptr) receive the field; the labels and parents also stay in ctx->sssp_C / sssp_A
 int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, double* C_host, int64_t* A_host, mpfmt_sssp_info* info);
 void mpfmt_sssp_free(mpfmt_ctx* ctx);
+// kernels_field.hip: the tracked field.  d_F: the point bitmap of the current obstacle set or nullptr (checkpts = false)
+int32_t mpfmt_field_compute(mpfmt_ctx* ctx, int64_t source0, int32_t checkpts, const uint64_t* d_F, mpfmt_field_info* info);   // whole field into the tracked buffers
+int32_t mpfmt_field_repair(mpfmt_ctx* ctx, const uint64_t* d_F, mpfmt_field_info* info);                                       // steps 2-4 on the tracked buffers
+int32_t mpfmt_field_mark_dirty(mpfmt_ctx* ctx);          // ORs ctx->bd_cols[0 .. bd_columns) into the dirty bitmap, on ctx->stream
+void mpfmt_field_drop_internal(mpfmt_ctx* ctx);
+bool mpfmt_field_live(mpfmt_ctx* ctx);                   // a tracked field of the resident samples and graph (drops one of another graph)
+bool mpfmt_field_history(const mpfmt_ctx* ctx);          // no graph build and no whole sweep since the field was last valid
 // the field of the usable seeds of one external start: entries [n] of a near list (1-based samples, distances, bits: 2 = usable) become
 // C[y] = seed[y] = fl(0 + dist); labels stay in ctx->sssp_C, parents in ctx->sssp_A (1-based, -1 = the start, 0 = none)
 int32_t mpfmt_sssp_seeded_device(mpfmt_ctx* ctx, const int64_t* d_idx1, const double* d_dist, const uint8_t* d_bits, int64_t n, const uint64_t* d_F,

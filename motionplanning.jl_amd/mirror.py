@@ -597,12 +597,15 @@ def fmtstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_i
     return P.status, P.solution.cost, P.solution.elapsed
 
 
-def prmstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_idx=1, checkpts=True, rng=None, seed=None, k=None):
+def prmstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_idx=1, checkpts=True, rng=None, seed=None, k=None,
+             keep_field=False):
     """The graph planner the reference leaves as a TODO (src/problems.jl:57, "# TODO: graph (PRM)"): PRM* over the same samples, radius
     rule (fmt.jl:38-41) and connection types as fmtstar_.  The whole r-disc (connections = "R") or k-nearest ("K") graph and its
     free-edge mask are built on the device, then the EXACT cost-to-come of every sample from init over the free-edge graph
     (mpfmt_prmstar / mpfmt_knn_prmstar); the answer is the goal sample of lowest cost.  Fills P.solution like fmtstar_, with
-    metadata["planner"] = "prmstar" and metadata["cost_to_come"] = the field (inf = unreachable).  Euclidean state spaces."""
+    metadata["planner"] = "prmstar" and metadata["cost_to_come"] = the field (inf = unreachable).  Euclidean state spaces.
+    keep_field = True: the context keeps the field of init_idx (Context.field_begin), so that after addobstacle_ / addblocker_ /
+    removeobstacle_ a replan_(P) repairs it instead of computing it again."""
     t0 = time.time()
     N = len(P.V) if N is None else int(N)
     P.CC.count = 0
@@ -637,6 +640,35 @@ def prmstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_i
             "ms_host_loop": res["ms_host_loop"]}
     if connections == "K":
         meta["k"] = k
+    if keep_field:
+        ctx.field_begin(init_idx, checkpts=checkpts)
+    P.solution = MPSolution(P.status, res["cost"], time.time() - t0, meta)
+    return P.status, P.solution.cost, P.solution.elapsed
+
+
+def replan_(P):
+    """After addobstacle_ / addblocker_ / removeobstacle_ on a problem solved by prmstar_(..., keep_field=True): repair the field the
+    context kept (Context.field_update: work that follows the edit; a whole recomputation only where the edit could not be applied in
+    place), then extract goal and path from it (Context.field_goal).  Fills P.solution as prmstar_ does, with
+    metadata["field_info"] = the repair's counters.  Raises (MPFMTError, ERR_STATE) without a tracked field."""
+    t0 = time.time()
+    if P.solution is None or P.ctx is None or P.solution.metadata.get("planner") != "prmstar":
+        raise RuntimeError("replan_ needs the solution of a prmstar_(..., keep_field=True) call")
+    ctx = P.ctx
+    if ctx.stat("field_tracked") != 1:
+        raise _lib.MPFMTError(_lib.ERR_STATE, "replan_: the context tracks no field (prmstar_(..., keep_field=True))")
+    P.CC._bind(ctx, P.SS)
+    old = P.solution.metadata
+    if ctx.stat("graph_swept") != 1:                        # (an edit that could not be applied in place: the mask is swept whole)
+        ctx.graph_sweep_device()
+    info = ctx.field_update()
+    res = ctx.field_goal(P.goal.kind, P.goal.params())
+    Cc, A = ctx.field_read()
+    P.status = "solved" if res["status"] == 1 else "failed"
+    path = res["path"]
+    meta = dict(old)
+    meta.update({"collision_checks": 0, "cost": res["cost"], "cumcost": Cc[path - 1], "solved": res["status"] == 1, "tree": A, "path": path,
+                 "cost_to_come": Cc, "ms_host_loop": res["ms_host_loop"], "field_info": info})
     P.solution = MPSolution(P.status, res["cost"], time.time() - t0, meta)
     return P.status, P.solution.cost, P.solution.elapsed
 
