@@ -243,7 +243,8 @@ MPFMT_API int32_t mpfmt_host_fmt_recursion(int64_t N, int32_t d, const double* X
  *      0-based int32, efree one bit per entry, F the point bitmap or NULL for checkpts = false; source 1-based; A may be NULL).
  *      No ctx, no device.  MPFMT_ERR_ARG on malformed arrays (colptr[0] != 0, decreasing colptr, a row out of range, a negative or
  *      NaN weight).
- * mpfmt_graph_sssp : the same field on the device for nsrc sources (1-based), one after another, over the resident graph and mask
+ * mpfmt_graph_sssp : the same field on the device for nsrc sources (1-based), one after another (mpfmt_graph_sssp_multi below runs 64 per
+ *      pass), over the resident graph and mask
  *      WITHOUT copying or transposing them.  C / A are nsrc x N, source-major (A may be NULL); info[nsrc] (may be NULL).
  *      checkpts != 0 sweeps the point bitmap on the device first.  MPFMT_ERR_STATE: no resident r-disc / k-nearest graph, no mask
  *      for the current graph and obstacle set (a mask goes stale with mpfmt_upload_boxes / mpfmt_upload_shapes2d /
@@ -395,6 +396,45 @@ MPFMT_API int32_t mpfmt_host_roadmap_query(int64_t N, int32_t d, const double* X
                                  const uint64_t* efree, const uint64_t* F, const double* lohi, int32_t M, const double* ss_lo,
                                  const double* ss_hi, double r, const double* s, const double* g, double* cost, int64_t* path, int64_t cap,
                                  mpfmt_roadmap_info* info);
+
+/* ---- many-source fields and cost matrices: up to 64 sources per pass over the graph (DESIGN.md "Many sources per pass").
+ *      mpfmt_graph_sssp and mpfmt_roadmap_query compute one field per pass over rowval / nzval / the mask.  The two calls here keep the
+ *      labels as L[sample][source], 64 doubles per sample, one wavefront lane per source: one visit of an entry serves 64 fields with one
+ *      512-byte row read.  The least fixed point is unique and independent of the schedule (the roadmap queries above), so every value is
+ *      BIT-IDENTICAL to what the one-field calls return; only rounds, relaxations and times differ.
+ * mpfmt_graph_sssp_multi : the argument and result contract of mpfmt_graph_sssp -- sources 1-based (duplicates allowed), C / A nsrc x N
+ *      source-major (A may be NULL: no parent pass runs and no parent buffer is held), info[nsrc] (may be NULL), r-disc or k-nearest graph,
+ *      the same refusals and codes, and it never sweeps edges on its own.  Sources run in groups of up to 64, one group per pass; nsrc == 0
+ *      succeeds and does nothing.  C and A equal those of mpfmt_graph_sssp for the same source, bit for bit.  info[q].reached is exact per
+ *      source; info[q].rounds, .relaxations and .ms_device are the GROUP's values, repeated for each of its members, and relaxations counts
+ *      the entry visits whose 512-byte label row was read (one per entry and round, whatever the number of sources), not lane evaluations.
+ * mpfmt_roadmap_matrix : S is d x ns, G is d x ng (column-major: state i at S + i * d).  cost[i * ng + j] and status[i * ng + j] (status may
+ *      be NULL) are exactly the cost and info.status that mpfmt_roadmap_query gives for the pair (S_i, G_j): 0 solved, 1 no usable path,
+ *      2 start not free, 3 goal not free (the start is looked at first); cost = +Inf unless solved.  ns fields are computed, 64 per pass,
+ *      and every goal's head list is reduced over a whole group at once; the ns * ng direct edges go through the motion test of
+ *      mpfmt_motions_free.  No paths are returned: ask mpfmt_roadmap_query for the pair of a chosen cell.  The refusals of
+ *      mpfmt_roadmap_query (no resident r-disc graph, a k-nearest graph in the slot, a stale mask, a sharded ctx, the SAT world, a
+ *      non-identity workspace: MPFMT_ERR_STATE; NULL arrays, a non-finite coordinate: MPFMT_ERR_ARG); a refused call leaves the ctx as it
+ *      was.  ns == 0 or ng == 0 succeeds and does nothing.  info (may be NULL) is per call; the per-start sizes near_s / usable_s are NOT
+ *      reported (an array inside an info struct would make it an in/out argument: mpfmt_roadmap_near with direction 0 gives them).
+ * Both calls keep device buffers of their own in the ctx (grow-only, freed with it): 512 N bytes of labels per group, another 512 N bytes of
+ *      parents once mpfmt_graph_sssp_multi was asked for A, 32 MiB of transposed staging for its copy-out; the matrix needs no parents, no
+ *      seed array and no staging.  Neither touches the tracked field, the scratch of mpfmt_graph_sssp, the graph or the mask.  A failed
+ *      allocation returns MPFMT_ERR_HIP and leaves the ctx usable.
+ *      Stats (last call): "sssp_multi_groups", "sssp_multi_rounds" (summed over groups), "sssp_multi_rows_read" (512-byte label rows read by
+ *      the relaxation, all rounds: times 512 a lower bound of its traffic), "sssp_multi_bytes" (device bytes these buffers hold).
+ *      Timers: "sssp_multi_relax" (all rounds of one group), "sssp_multi_parents", "roadmap_matrix" (seeds, rounds and goal reduction). */
+typedef struct {
+    int64_t groups;            /* passes over the graph: ceil(ns / 64) */
+    int64_t rounds;            /* relaxation rounds, summed over the groups */
+    int64_t near_s, usable_s;  /* near-set entries of all starts (tail direction) and their usable part */
+    int64_t near_g, usable_g;  /* near-set entries of all goals (head direction) and their free part */
+    double  ms_device;         /* device time of the groups: seeds, rounds, goal reduction */
+} mpfmt_roadmap_matrix_info;
+MPFMT_API int32_t mpfmt_graph_sssp_multi(mpfmt_ctx* ctx, const int64_t* sources, int64_t nsrc, int32_t checkpts, double* C, int64_t* A,
+                               mpfmt_sssp_info* info);
+MPFMT_API int32_t mpfmt_roadmap_matrix(mpfmt_ctx* ctx, const double* S, int64_t ns, const double* G, int64_t ng, int32_t checkpts, double* cost,
+                             int32_t* status, mpfmt_roadmap_matrix_info* info);
 
 /* ---- adaptive shortcutting of solution paths (Hsu 2000): shortcut / cut_corner / adaptive_shortcut(!) of src/postprocessors.jl:6-50,
  *      statement for statement, for ONE path on the host and for a BATCH of paths on the device (one wavefront per path; the tree paths

@@ -61,6 +61,11 @@ class RoadmapInfo(C.Structure):
                 ("usable_g", C.c_int64), ("rounds", C.c_int64), ("path_len", C.c_int64), ("ms_device", C.c_double)]
 
 
+class RoadmapMatrixInfo(C.Structure):
+    _fields_ = [("groups", C.c_int64), ("rounds", C.c_int64), ("near_s", C.c_int64), ("usable_s", C.c_int64), ("near_g", C.c_int64),
+                ("usable_g", C.c_int64), ("ms_device", C.c_double)]
+
+
 SHORTCUT_DONE, SHORTCUT_TRUNCATED, SHORTCUT_STUCK = 0, 1, 2
 ROADMAP_SOLVED, ROADMAP_NO_PATH, ROADMAP_START_BLOCKED, ROADMAP_GOAL_BLOCKED = 0, 1, 2, 3
 WF_SINGLE, WF_EAGER, WF_LAZY = 1, 2, 4
@@ -102,6 +107,7 @@ SYMBOLS = [
                                              C.POINTER(FmtResult)]),
     ("mpfmt_host_graph_sssp", C.c_int32, [C.c_int64, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p, C.c_int64, c_d_p, c_i64_p]),
     ("mpfmt_graph_sssp", C.c_int32, [C.c_void_p, c_i64_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(SsspInfo)]),
+    ("mpfmt_graph_sssp_multi", C.c_int32, [C.c_void_p, c_i64_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(SsspInfo)]),
     ("mpfmt_field_begin", C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(FieldInfo)]),
     ("mpfmt_field_update", C.c_int32, [C.c_void_p, C.POINTER(FieldInfo)]),
     ("mpfmt_field_read", C.c_int32, [C.c_void_p, c_d_p, c_i64_p]),
@@ -116,6 +122,8 @@ SYMBOLS = [
     ("mpfmt_roadmap_near", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, C.c_int32, c_i64_p, C.c_int64, c_i64_p, c_d_p, c_u64_p, c_i64_p]),
     ("mpfmt_roadmap_attach", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, c_d_p, c_i64_p, c_d_p]),
     ("mpfmt_roadmap_query", C.c_int32, [C.c_void_p, c_d_p, c_d_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, c_i64_p, C.c_int64, C.POINTER(RoadmapInfo)]),
+    ("mpfmt_roadmap_matrix", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, c_d_p, C.c_int64, C.c_int32, c_d_p, C.POINTER(C.c_int32),
+                                         C.POINTER(RoadmapMatrixInfo)]),
     ("mpfmt_host_roadmap_query", C.c_int32, [C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p, c_d_p, C.c_int32,
                                              c_d_p, c_d_p, C.c_double, c_d_p, c_d_p, c_d_p, c_i64_p, C.c_int64, C.POINTER(RoadmapInfo)]),
     ("mpfmt_host_adaptive_shortcut", C.c_int32, [c_d_p, C.c_int64, C.c_int32, c_d_p, C.c_int32, c_d_p, c_d_p, C.c_int32, C.c_int64, c_d_p, C.c_int64,
@@ -685,6 +693,18 @@ class Context:
         return dict(C=Cc[:n, :self.N], A=None if A is None else A[:n, :self.N],
                     info=[{k: getattr(info[i], k) for k, _ in SsspInfo._fields_} for i in range(n)])
 
+    def graph_sssp_multi(self, sources, checkpts=True, want_parents=True):
+        """graph_sssp with up to 64 sources per pass over the graph (mpfmt_graph_sssp_multi): the same dict, C and A bit-identical;
+        info[q]["rounds"], ["relaxations"] and ["ms_device"] are those of the source's group of 64."""
+        src = np.ascontiguousarray(np.atleast_1d(sources), dtype=np.int64)
+        n = src.size
+        Cc = np.empty((max(n, 1), max(self.N, 1)), dtype=np.float64)
+        A = np.empty((max(n, 1), max(self.N, 1)), dtype=np.int64) if want_parents else None
+        info = (SsspInfo * max(n, 1))()
+        self._chk(self._L.mpfmt_graph_sssp_multi(self._h, _ip(src), n, int(bool(checkpts)), _dp(Cc), _ip(A), info))
+        return dict(C=Cc[:n, :self.N], A=None if A is None else A[:n, :self.N],
+                    info=[{k: getattr(info[i], k) for k, _ in SsspInfo._fields_} for i in range(n)])
+
     # ---- a cost-to-come field kept valid across box edits (include/mpfmt.h) ---------------------------------------------------
     def field_begin(self, source=1, checkpts=True):
         """Compute the field of `source` (1-based) over the resident swept graph into buffers the context keeps (mpfmt_field_begin);
@@ -791,6 +811,20 @@ class Context:
             self._chk(rc)
             break
         return (cost[:n], [path[pptr[i]:pptr[i + 1]].copy() for i in range(n)], [_roadmap_info(info[i]) for i in range(n)])
+
+    def roadmap_matrix(self, S, G, checkpts=True):
+        """The cost matrix between external starts S (ns, d) and goals G (ng, d) at the price of ns fields, 64 per pass over the graph
+        (mpfmt_roadmap_matrix): (cost (ns, ng), status (ns, ng) int32, info dict).  Every cell equals roadmap_query on that pair (cost
+        bits and status 0 solved / 1 no path / 2 start blocked / 3 goal blocked); no paths: ask roadmap_query for a chosen cell."""
+        S = self._states(S); G = self._states(G)
+        ns, ng = S.shape[0], G.shape[0]
+        cost = np.empty(max(ns * ng, 1), dtype=np.float64)
+        status = np.empty(max(ns * ng, 1), dtype=np.int32)
+        info = RoadmapMatrixInfo()
+        self._chk(self._L.mpfmt_roadmap_matrix(self._h, _dp(S), ns, _dp(G), ng, int(bool(checkpts)), _dp(cost),
+                                               status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(info)))
+        return (cost[:ns * ng].reshape(ns, ng), status[:ns * ng].reshape(ns, ng),
+                {k: getattr(info, k) for k, _ in RoadmapMatrixInfo._fields_})
 
     def prmstar(self, r, goal_kind, goal_params, init_idx=1, checkpts=True):
         """PRM*: graph_step_device(r) (reused when resident), then the exact cost-to-come field of init_idx over the free-edge graph and

@@ -204,6 +204,7 @@ int32_t mpfmt_ctx_destroy(mpfmt_ctx* ctx)
     for (int k = 0; k < 2; ++k) { if (ctx->copy_stream[k]) hipStreamDestroy(ctx->copy_stream[k]); if (ctx->ev_conv[k]) hipEventDestroy(ctx->ev_conv[k]); if (ctx->ev_copy[k]) hipEventDestroy(ctx->ev_copy[k]); }
     mpfmt_wf_free(ctx);
     mpfmt_sssp_free(ctx);
+    mpfmt_sssp_multi_free(ctx);
     if (ctx->aux) { mpfmt_ctx_destroy(ctx->aux); ctx->aux = nullptr; }
     timer_resolve(ctx);
     if (ctx->timer_state) {
@@ -1384,6 +1385,22 @@ int32_t mpfmt_graph_sssp(mpfmt_ctx* ctx, const int64_t* sources, int64_t nsrc, i
     return MPFMT_OK;
 }
 
+// the same fields, up to 64 sources per pass over the graph (kernels_sssp_multi.hip)
+int32_t mpfmt_graph_sssp_multi(mpfmt_ctx* ctx, const int64_t* sources, int64_t nsrc, int32_t checkpts, double* C, int64_t* A, mpfmt_sssp_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (nsrc < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "nsrc < 0");
+    if (nsrc > 0 && (!sources || !C)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "sources / C is NULL");
+    int32_t rc;
+    if ((rc = sssp_ready(ctx))) return rc;
+    if (checkpts && !ctx->have_boxes && ctx->cc_kind == 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "checkpts needs an obstacle set");
+    if ((rc = check_idx(ctx, sources, nsrc, "sources"))) return rc;
+    if (nsrc == 0) return MPFMT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (checkpts && (rc = sssp_point_bitmap(ctx))) return rc;
+    return mpfmt_sssp_multi_device(ctx, sources, nsrc, checkpts ? ctx->sssp_F.get() : nullptr, C, A, info);
+}
+
 // ---- a tracked field: kept valid across in-place box edits (kernels_field.hip) -----------------------------------------------------------
 
 int32_t mpfmt_field_begin(mpfmt_ctx* ctx, int64_t source, int32_t checkpts, mpfmt_field_info* info)
@@ -1659,6 +1676,60 @@ int32_t mpfmt_roadmap_query(mpfmt_ctx* ctx, const double* S, const double* G, in
         if (info) info[q] = inf;
     }
     if (over) return mpfmt_fail(ctx, MPFMT_ERR_CAPACITY, "roadmap_query: %lld path samples exceed capacity %lld", (long long)used, (long long)path_cap);
+    return MPFMT_OK;
+}
+
+// the ns x ng cost matrix between external starts and goals at the price of ns fields (kernels_sssp_multi.hip)
+int32_t mpfmt_roadmap_matrix(mpfmt_ctx* ctx, const double* S, int64_t ns, const double* G, int64_t ng, int32_t checkpts, double* cost, int32_t* status,
+                             mpfmt_roadmap_matrix_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (ns < 0 || ng < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_matrix: ns / ng < 0");
+    if (ns > 0 && ng > 0 && (!S || !G || !cost)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_matrix: S / G / cost is NULL");
+    int32_t rc;
+    if ((rc = roadmap_ready(ctx))) return rc;
+    if (info) memset(info, 0, sizeof *info);
+    if (ns == 0 || ng == 0) return MPFMT_OK;
+    if ((rc = roadmap_finite(ctx, S, ns, "roadmap_matrix (S)"))) return rc;
+    if ((rc = roadmap_finite(ctx, G, ng, "roadmap_matrix (G)"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int d = ctx->d;
+    const int64_t np = ns * ng, ws = (ns + 63) / 64, wg = (ng + 63) / 64, wp = (np + 63) / 64;
+    mpfmt_tmp tmp;
+    double *dS = nullptr, *dG = nullptr, *dP = nullptr, *dQ = nullptr, *d_cost = nullptr;
+    int32_t* d_status = nullptr;
+    if ((rc = up_d(ctx, tmp, S, (size_t)ns * d, &dS))) return rc;
+    if ((rc = up_d(ctx, tmp, G, (size_t)ng * d, &dG))) return rc;
+    // the states of both sides and the direct edge of every pair: the tests of the pair query, through the same kernels
+    uint64_t* d_m = nullptr;
+    HIPCHK(ctx, tmp.get(&d_m, sizeof(uint64_t) * (size_t)(ws + wg + wp)));
+    HIPCHK(ctx, tmp.get(&dP, sizeof(double) * (size_t)np * d));
+    HIPCHK(ctx, tmp.get(&dQ, sizeof(double) * (size_t)np * d));
+    HIPCHK(ctx, tmp.get(&d_cost, sizeof(double) * (size_t)np));
+    HIPCHK(ctx, tmp.get(&d_status, sizeof(int32_t) * (size_t)np));
+    if ((rc = mpfmt_launch_states_free(ctx, dS, ns, d_m))) return rc;
+    if ((rc = mpfmt_launch_states_free(ctx, dG, ng, d_m + ws))) return rc;
+    if ((rc = mpfmt_roadmap_pairs(ctx, dS, ns, dG, ng, dP, dQ))) return rc;
+    if ((rc = mpfmt_launch_motions_free(ctx, dP, dQ, np, d_m + ws + wg))) return rc;
+    if (checkpts && (rc = sssp_point_bitmap(ctx))) return rc;
+    const uint64_t* d_F = checkpts ? ctx->sssp_F.get() : nullptr;
+    // all attachments, one launch each way
+    mpfmt_rm_list Ls, Lg;
+    if ((rc = mpfmt_roadmap_lists(ctx, tmp, dS, ns, 0, d_F, &Ls))) return rc;
+    const int64_t cand_s = ctx->roadmap_candidates, tot_s = ctx->roadmap_near_total;
+    if ((rc = mpfmt_roadmap_lists(ctx, tmp, dG, ng, 1, nullptr, &Lg))) return rc;
+    ctx->roadmap_candidates += cand_s; ctx->roadmap_near_total += tot_s;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // (the lists' usable counts have arrived)
+    mpfmt_roadmap_matrix_info inf;
+    memset(&inf, 0, sizeof inf);
+    if ((rc = mpfmt_roadmap_matrix_device(ctx, dS, ns, dG, ng, d_F, d_m, d_m + ws, d_m + ws + wg, Ls, Lg, d_cost, d_status, &inf))) return rc;
+    inf.near_s = Ls.total; inf.near_g = Lg.total;
+    for (int64_t v : Ls.usable_host) inf.usable_s += v;
+    for (int64_t v : Lg.usable_host) inf.usable_g += v;
+    HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIPCHK(ctx, hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (info) *info = inf;
     return MPFMT_OK;
 }
 
@@ -2284,6 +2355,10 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "sssp_rounds") == 0) { *value = ctx->sssp_rounds; return MPFMT_OK; }
     if (strcmp(name, "sssp_relaxations") == 0) { *value = ctx->sssp_relax; return MPFMT_OK; }
     if (strcmp(name, "sssp_reached") == 0) { *value = ctx->sssp_reached; return MPFMT_OK; }
+    if (strcmp(name, "sssp_multi_groups") == 0) { *value = ctx->ms_groups; return MPFMT_OK; }
+    if (strcmp(name, "sssp_multi_rounds") == 0) { *value = ctx->ms_rounds; return MPFMT_OK; }
+    if (strcmp(name, "sssp_multi_rows_read") == 0) { *value = ctx->ms_rows; return MPFMT_OK; }
+    if (strcmp(name, "sssp_multi_bytes") == 0) { *value = ctx->ms_bytes; return MPFMT_OK; }
     if (strcmp(name, "roadmap_candidates") == 0) { *value = ctx->roadmap_candidates; return MPFMT_OK; }
     if (strcmp(name, "roadmap_near_total") == 0) { *value = ctx->roadmap_near_total; return MPFMT_OK; }
     if (strcmp(name, "shortcut_tests_evaluated") == 0) { *value = ctx->shortcut_tests; return MPFMT_OK; }

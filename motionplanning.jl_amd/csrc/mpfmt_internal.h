@@ -413,6 +413,17 @@ struct mpfmt_ctx {
     mpfmt_dbuf<double> sssp_seed;         // [N] seed labels of the running pair query (+Inf: no usable edge from the start)
     int64_t roadmap_candidates = 0, roadmap_near_total = 0;      // stats of the last call
 
+    // ---- many-source fields and cost matrices (kernels_sssp_multi.hip): buffers of their own, grow-only ----
+    mpfmt_dbuf<double> ms_L;              // [N][64] labels, lane = source
+    mpfmt_dbuf<int64_t> ms_A;             // [N][64] 1-based parents (only once parents were asked for)
+    mpfmt_dbuf<uint64_t> ms_bm;           // [3][ceil(N/64)] changed-sample bitmaps
+    mpfmt_dbuf<void> ms_state;            // ms_state (device) and its pinned host mirror
+    mpfmt_hbuf<void> ms_state_host;
+    mpfmt_dbuf<void> ms_stage;            // [64][min(N, 65536)] transposed chunk of the copy-out
+    mpfmt_dbuf<int64_t> ms_src;           // [64] 0-based sources of the running group
+    hipEvent_t ms_ev[2] = {nullptr, nullptr};
+    int64_t ms_groups = 0, ms_rounds = 0, ms_rows = 0, ms_bytes = 0;      // stats of the last call
+
     // ---- tracked cost-to-come field (kernels_field.hip): buffers of its own that no other call writes ----
     // graph_epoch counts the graph builds (bumped wherever a graph becomes filled), sweep_epoch the whole sweeps of the mask (bumped wherever
     // graph_swept becomes true).  A tracked field belongs to one sample set and one graph identity (radius or k; an import drops it); it
@@ -598,6 +609,18 @@ int32_t mpfmt_roadmap_lists(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, i
                             bool count_only = false);
 int32_t mpfmt_roadmap_reduce(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, const double* d_C, double* d_cost, int64_t* d_parent);
 int32_t mpfmt_roadmap_goal(mpfmt_ctx* ctx, const mpfmt_rm_list& L, int64_t q, const double* d_C, const int64_t* d_A, int64_t* d_res);
+
+// kernels_sssp_multi.hip ----------------------------------------------------------------------------
+// nsrc fields (sources 1-based, on the host) in groups of 64 over the resident graph and mask; C_host [nsrc][N], A_host [nsrc][N] or nullptr
+int32_t mpfmt_sssp_multi_device(mpfmt_ctx* ctx, const int64_t* sources1, int64_t nsrc, const uint64_t* d_F, double* C_host, int64_t* A_host,
+                                mpfmt_sssp_info* info);
+// the cost matrix of ns external starts and ng external goals from their near lists (tail lists Ls, head lists Lg) and the three bit arrays
+// (start free, goal free, motion bit of pair i * ng + j); d_cost / d_status [ns][ng] on the device; info: groups, rounds, ms_device
+int32_t mpfmt_roadmap_matrix_device(mpfmt_ctx* ctx, const double* d_S, int64_t ns, const double* d_G, int64_t ng, const uint64_t* d_F,
+                                    const uint64_t* d_sfree, const uint64_t* d_gfree, const uint64_t* d_direct, const mpfmt_rm_list& Ls,
+                                    const mpfmt_rm_list& Lg, double* d_cost, int32_t* d_status, mpfmt_roadmap_matrix_info* info);
+int32_t mpfmt_roadmap_pairs(mpfmt_ctx* ctx, const double* d_S, int64_t ns, const double* d_G, int64_t ng, double* d_P, double* d_Q);      // P / Q [ns * ng][d]
+void mpfmt_sssp_multi_free(mpfmt_ctx* ctx);
 
 // kernels_shortcut.hip -----------------------------------------------------------------------------
 // the batch on the device; arguments already validated (mpfmt_adaptive_shortcut_batch, mpfmt_capi.hip)

@@ -691,6 +691,24 @@ def roadmap_query_(P, starts, goals, checkpts=True):
     return cost, paths
 
 
+def roadmap_matrix_(P, starts, goals, checkpts=True):
+    """The cost table between `starts` (ns, d) and `goals` (ng, d), states that are NOT samples, over the roadmap a prmstar_ / fmtstar_
+    call (connections = "R") left resident in P.ctx, at the price of ns fields computed 64 per pass over the graph
+    (mpfmt_roadmap_matrix).  Returns (cost (ns, ng), status (ns, ng)): every cell is what roadmap_query_ gives for that pair (status 0
+    solved, 1 no path, 2 start blocked, 3 goal blocked); for the path of a chosen cell ask roadmap_query_.
+    metadata["roadmap_matrix_info"] holds the call's info dict."""
+    if P.solution is None or P.ctx is None:
+        raise RuntimeError("roadmap_matrix_ needs the roadmap of a prmstar_ / fmtstar_ call")
+    if not isinstance(P.SS.dist, Euclidean):
+        raise RuntimeError("roadmap_matrix_ requires Euclidean SS")
+    S = np.ascontiguousarray(np.atleast_2d(np.asarray(starts, dtype=np.float64)))
+    G = np.ascontiguousarray(np.atleast_2d(np.asarray(goals, dtype=np.float64)))
+    P.CC._bind(P.ctx, P.SS)
+    cost, status, info = P.ctx.roadmap_matrix(S, G, checkpts=checkpts)
+    P.solution.metadata["roadmap_matrix_info"] = info
+    return cost, status
+
+
 # ---- post-processing (src/postprocessors.jl) ---------------------------------------------------------------------------------------
 def tree_paths(A, nodes, root=1):
     """The tree paths root -> node (1-based sample indices) out of a parent array A (metadata["tree"]: A[i - 1] = parent of i, 0 =
