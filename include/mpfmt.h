@@ -98,16 +98,32 @@ MPFMT_API int32_t mpfmt_upload_boxes(mpfmt_ctx* ctx, const double* lohi, int32_t
  * mask of a swept, unsharded resident graph (r-disc, imported or k-nearest) is brought up to date on the ctx's stream instead
  * of being thrown away: adding boxes only clears bits (new = old AND free against the added boxes), removing one only sets
  * bits of blocked entries whose segment box meets it (tested again against what remains).  The mask is the one a whole sweep
- * of the resulting list writes, bit for bit.  In every other state (no swept mask, a sharded ctx, a steering graph) the list
- * is edited and the mask invalidated, as mpfmt_upload_boxes does.  The steering spaces' masks are always re-swept.
+ * of the resulting list writes, bit for bit.
+ * A resident, swept steering graph (double integrator, Dubins, Reeds-Shepp) of an unsharded ctx follows in place too, mask AND
+ * per-entry segment counts (nseg), when dw is what the space's sweep requires (d / 2; 2 for the cars) and the resulting list is
+ * one the whole sweep accepts (the double integrator's box limit): with F(list) = (free, nseg) of an entry,
+ *   add:    free = old free AND free(added alone), nseg = min(old nseg, nseg(added alone)) -- the count of a blocked entry can drop;
+ *   remove: a blocked entry that is not free against the removed boxes alone is evaluated again against what remains (free and
+ *           nseg); every other entry keeps both.
+ * Mask and counts are byte for byte those of a whole sweep of the resulting list; the graph stays swept ("steer_swept" stays 1)
+ * and the next mpfmt_*_fmtstar_wavefront on the same parameters sweeps nothing.  If the update itself fails, the edited list
+ * stands and the graph is swept again.
+ * In every other state (no swept mask, a sharded ctx, a list beyond the sweep's limit) the list is edited and the mask
+ * invalidated, as mpfmt_upload_boxes does.
  *   mpfmt_boxes_add:    lohi [M_add][2][dw] (the ctx's dw), appended behind the current boxes.
  *   mpfmt_boxes_remove: ids 1-based, distinct; the remaining boxes keep their order.
  * Refused, leaving the ctx as it was: NULL with a positive count, an id out of range or repeated (MPFMT_ERR_ARG); no box set
  * uploaded, or the 2-D SAT world (MPFMT_ERR_STATE).  A count of 0 succeeds and does nothing.
  * mpfmt_get_stat: "boxes_delta_path" (1 in place, 0 invalidated), "boxes_delta_columns" (columns whose entries were read),
- * "boxes_delta_entries" (entries that reached an exact test); timing key "boxes_delta". */
+ * "boxes_delta_entries" (Euclidean graphs: entries that reached an exact test; steering graphs: entries evaluated against the
+ * delta boxes), "steer_swept" (1: a swept steering graph is resident); timing keys "boxes_delta" / "steer_delta". */
 MPFMT_API int32_t mpfmt_boxes_add(mpfmt_ctx* ctx, const double* lohi, int32_t M_add);
 MPFMT_API int32_t mpfmt_boxes_remove(mpfmt_ctx* ctx, const int64_t* ids, int32_t n_ids);
+/* The resident, swept steering mask (ceil(nnz / 64) words, bit e = entry e free) and segment counts (nnz bytes; nseg may be NULL)
+ * copied to the host as they are -- after in-place edits, what a whole sweep of the current list writes.  Nothing is swept
+ * (mpfmt_*_graph_edges_free always sweep again).  nnz: mpfmt_get_stat "nnz".  MPFMT_ERR_STATE when no swept steering graph is
+ * resident (mpfmt_get_stat "steer_swept" == 0); MPFMT_ERR_ARG when mask is NULL and nnz > 0. */
+MPFMT_API int32_t mpfmt_steer_mask_read(mpfmt_ctx* ctx, uint64_t* mask, uint8_t* nseg);
 
 /* ---- r-disc neighbour graph = ImmutableNNC(D::SparseMatrixCSC, r) (src/nearneighbors.jl:23-27):
  *      column v = inball(V, dist, DS, v, r) (src/nearneighbors.jl:179-183) for every v.

@@ -84,6 +84,7 @@ SYMBOLS = [
     ("mpfmt_upload_boxes", C.c_int32, [C.c_void_p, c_d_p, C.c_int32, C.c_int32, c_d_p, c_d_p, C.c_int32]),
     ("mpfmt_boxes_add", C.c_int32, [C.c_void_p, c_d_p, C.c_int32]),
     ("mpfmt_boxes_remove", C.c_int32, [C.c_void_p, c_i64_p, C.c_int32]),
+    ("mpfmt_steer_mask_read", C.c_int32, [C.c_void_p, c_u64_p, c_u8_p]),
     ("mpfmt_rdisc_count", C.c_int32, [C.c_void_p, C.c_double, c_i64_p, c_i64_p]),
     ("mpfmt_rdisc_fill", C.c_int32, [C.c_void_p, c_i64_p, c_d_p]),
     ("mpfmt_rdisc_query", C.c_int32, [C.c_void_p, C.c_int64, C.c_double, c_i64_p, c_d_p, C.c_int64, c_i64_p]),
@@ -507,7 +508,8 @@ class Context:
 
     def boxes_add(self, lohi):
         """Append boxes lohi (M_add, 2, dw) to the uploaded PointRobotNDBoxes set in place (mpfmt_boxes_add): the free-edge mask of a
-        swept resident graph is brought up to date instead of being thrown away (stat("boxes_delta_path") == 1)."""
+        swept resident graph -- Euclidean, or a steering graph with its segment counts -- is brought up to date instead of being thrown
+        away (stat("boxes_delta_path") == 1)."""
         lohi = np.ascontiguousarray(lohi, dtype=np.float64)
         if lohi.size == 0:
             lohi = np.zeros((0, 2, self.dw))
@@ -525,6 +527,15 @@ class Context:
         ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int64)
         self._chk(self._L.mpfmt_boxes_remove(self._h, _ip(ids), ids.size))
         self._cc_epoch += 1
+
+    def steer_mask_read(self):
+        """(mask, nseg) of the resident, swept steering graph as they are (mpfmt_steer_mask_read): after boxes_add / boxes_remove, the
+        bytes a whole sweep of the current list writes.  Sweeps nothing; MPFMTError (ERR_STATE) when no swept steering graph is resident."""
+        n = self.stat("nnz")
+        mask = np.zeros(max(nwords(n), 1), dtype=np.uint64)
+        nseg = np.zeros(max(n, 1), dtype=np.uint8)
+        self._chk(self._L.mpfmt_steer_mask_read(self._h, _up(mask), nseg.ctypes.data_as(c_u8_p)))
+        return mask[:nwords(n)], nseg[:n]
 
     def upload_shapes2d(self, shapes, ss_lo=None, ss_hi=None):
         """2-D SAT world: shapes = [("circle", (cx, cy), r) | ("polygon", [(x, y), ...]), ...] (a flat Compound2D)."""

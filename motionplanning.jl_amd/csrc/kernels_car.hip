@@ -13,6 +13,7 @@
 #include "mpfmt_internal.h"
 #include "mp_math.h"
 #include "sat2d_predicates.h"
+#include "steer_delta.h"
 
 #define CAR_TWOPI (2 * 3.141592653589793)
 
@@ -604,6 +605,67 @@ __global__ __launch_bounds__(256) void k_car_sweep(const double* __restrict__ X,
     if (lane == 0 && (e - lane) < nnz) mask[(e - lane) >> 6] = bits;
 }
 
+// ---- in-place box edits (steer_delta.h): add / remove on the flagged columns ---------------------------------------------------
+// F(list) of an entry is car_motion_free with cc.boxes / cc.M pointed at that list: the delta boxes (from LDS when lds_delta, else
+// from memory as the whole sweep reads its list) or the remaining list.  ctr[1] += entries whose F(delta) was evaluated.
+#define CAR_DELTA_LDS_BOXES 512
+template <int KIND, bool REMOVE>
+__global__ __launch_bounds__(SD_THREADS) void k_car_delta(const double* __restrict__ X, const int64_t* __restrict__ colptr,
+                                                         const int32_t* __restrict__ rowval, const int32_t* __restrict__ cols,
+                                                         unsigned long long* __restrict__ ctr, const double* __restrict__ delta, int nd,
+                                                         int lds_delta, const double* __restrict__ rem, int nrem, double rt, double sp,
+                                                         mpfmt_ss ss, unsigned long long* __restrict__ mask, uint8_t* __restrict__ nseg)
+{
+    __shared__ __attribute__((aligned(16))) double sdel[CAR_DELTA_LDS_BOXES * 4];
+    if (lds_delta) for (int t = threadIdx.x; t < nd * 4; t += blockDim.x) sdel[t] = delta[t];
+    __syncthreads();
+    mpfmt_ws2d cd, cr;
+    cd.kind = 0; cd.boxes = lds_delta ? (const double*)sdel : delta; cd.M = nd; cd.shapes = nullptr; cd.ns = 0; cd.aabb = mpfmt_aabb2d();
+    cr = cd; cr.boxes = rem; cr.M = nrem;
+    const int lane = threadIdx.x & 63;
+    const int64_t gwave = ((int64_t)blockIdx.x * SD_THREADS + threadIdx.x) >> 6;
+    const int64_t nwaves = (int64_t)gridDim.x * (SD_THREADS / 64);
+    const int64_t ncols = (int64_t)ctr[0];
+    unsigned long long tested_n = 0;
+    for (int64_t ci = gwave; ci < ncols; ci += nwaves) {
+        const int64_t x = (int64_t)__builtin_amdgcn_readfirstlane(cols[ci]);
+        const int64_t beg = colptr[x], end = colptr[x + 1];
+        for (int64_t wd = beg >> 6; wd * 64 < end; ++wd) {
+            const int64_t e = wd * 64 + lane;
+            const unsigned long long cur = sd_word(mask, wd);
+            const bool mine = e >= beg && e < end;
+            const bool isfree = (cur >> lane) & 1ull;
+            // add: every entry (a blocked one keeps its bit, but its count can drop); remove: free entries stay as they are
+            const bool cand = REMOVE ? (mine && !isfree) : mine;
+            if (__ballot(cand) == 0) continue;
+            bool change = false;
+            if (cand) {
+                const int64_t y = rowval[e];
+                int sd = 0;
+                const bool fd = car_motion_free<KIND>(X + 3 * y, X + 3 * x, rt, sp, cd, ss, &sd);
+                if (REMOVE) {
+                    if (!fd) {                                 // from nothing against what is left
+                        int sr = 0;
+                        change = car_motion_free<KIND>(X + 3 * y, X + 3 * x, rt, sp, cr, ss, &sr);
+                        nseg[e] = (uint8_t)min(sr, 255);
+                    }
+                } else {
+                    const int old = (int)nseg[e];
+                    sd = min(sd, 255);
+                    if (sd < old) nseg[e] = (uint8_t)sd;
+                    change = isfree && !fd;
+                }
+            }
+            const unsigned long long ch = __ballot(change);
+            if (lane == 0 && ch) {
+                if (REMOVE) atomicOr(&mask[wd], ch); else atomicAnd(&mask[wd], ~ch);
+            }
+            tested_n += (unsigned long long)__popcll(__ballot(cand));
+        }
+    }
+    if (lane == 0 && tested_n) atomicAdd(ctr + 1, tested_n);
+}
+
 // controls: [n][5][3] = (duration, speed, signed curvature), unused segments zero; nseg[i] = segments used
 template <int KIND>
 __global__ __launch_bounds__(256) void k_car_steer(const double* __restrict__ X0, const double* __restrict__ X1, int64_t n, double rt,
@@ -715,6 +777,31 @@ int32_t mpfmt_car_sweep(mpfmt_ctx* ctx)
     }
     tm2.end("car_sweep");
     ctx->steer_swept = true;
+    return MPFMT_OK;
+}
+
+// flag + update on ctx->stream for a resident, swept car graph: d_delta = the nd boxes added (already at the end of ctx->boxes) or a
+// copy of the nd boxes removed (ctx->boxes / ctx->M: the remaining list).  The caller owns bd_cols / bd_ctr.
+// Column cull: every waypoint lies on the steered path, no farther along it from the column's position than the
+// path is long, and the graph keeps length = cost <= steer_r.
+int32_t mpfmt_car_delta_launch(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove)
+{
+    const int64_t N = ctx->N;
+    const unsigned nbf = (unsigned)((N + SD_THREADS - 1) / SD_THREADS), nbu = sd_update_blocks(ctx);
+    const double rpad = ctx->steer_r * (1.0 + 1e-6) + 1e-300;
+    const int lds_delta = nd <= CAR_DELTA_LDS_BOXES ? 1 : 0;
+    const int nrem = remove ? ctx->M : 0;
+    const double* rem = remove ? (const double*)ctx->boxes.get() : nullptr;
+    unsigned long long* mask = (unsigned long long*)ctx->graph_free.get();
+    hipLaunchKernelGGL((k_sd_flag<3, 2, false>), dim3(nbf), dim3(SD_THREADS), 0, ctx->stream, ctx->Xo, N, d_delta, (int)nd, rpad, 0.0,
+                       ctx->bd_cols, ctx->bd_ctr);
+#define CAR_DELTA_GO(KIND, REM)                                                                                                       \
+    hipLaunchKernelGGL((k_car_delta<KIND, REM>), dim3(nbu), dim3(SD_THREADS), 0, ctx->stream, ctx->Xo, ctx->colptr, ctx->rowval, ctx->bd_cols, \
+                       ctx->bd_ctr, d_delta, (int)nd, lds_delta, rem, nrem, ctx->car_rt, ctx->car_sp, ctx->ss, mask, ctx->steer_nseg)
+    if (ctx->steer_kind == MPFMT_STEER_REEDSSHEPP) { if (remove) CAR_DELTA_GO(2, true); else CAR_DELTA_GO(2, false); }
+    else { if (remove) CAR_DELTA_GO(1, true); else CAR_DELTA_GO(1, false); }
+#undef CAR_DELTA_GO
+    HIPCHK(ctx, hipGetLastError());
     return MPFMT_OK;
 }
 

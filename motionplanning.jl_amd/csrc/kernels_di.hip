@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "di_steer.h"
+#include "steer_delta.h"
 
 // MODE 0: count   1: fill the staging CSC from the counts   2: count AND keep the accepted hits in slot lists (single pass)
 template <int M, int MODE>
@@ -271,6 +272,72 @@ __device__ __forceinline__ bool ws_point_in_ss(const double (&p)[2 * M], const m
     return ok != 0;
 }
 
+// One entry: the motion x0 -> x1 of duration t against nbox boxes at sbox ([nbox][2 M], LDS or global) -- or, M == 2 and cc.kind == 1,
+// the 2-D SAT world.  Stages in the reference's order: bounds of waypoint q, boxes on segment q, q = 0..3; stops at the first that
+// fails.  segs = segment tests the reference would have counted.  The whole sweep and the in-place updates (steer_delta.h) run THIS.
+template <int M>
+__device__ __forceinline__ bool di_motion_free(const double (&x0)[2 * M], const double (&x1)[2 * M], const double t, const double* sbox,
+                                               const int nbox, const mpfmt_ss& ss, const mpfmt_ws2d& cc, int& segs)
+{
+    constexpr int NS = 2 * M;
+    double wp[NS], wn[NS];
+    di_state<M>(x0, x1, t, 0.0, wp);
+    bool fr = true;
+    segs = 0;
+    for (int q = 0; q < 4 && fr; ++q) {
+        const double s = (q == 3) ? t : ((double)(q + 1) / 4.0) * t;
+        di_state<M>(x0, x1, t, s, wn);
+        if (!ws_point_in_ss<M>(wp, ss)) { fr = false; break; }
+        ++segs;
+        // segment wp -> wn in the workspace (first M coordinates) against every box, boxesND.jl:52-56
+        double l[M], h[M], pv[M], pw[M];
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+            pv[i] = wp[i]; pw[i] = wn[i];
+            l[i] = (pw[i] < pv[i]) ? pw[i] : pv[i];
+            h[i] = (pv[i] < pw[i]) ? pw[i] : pv[i];
+        }
+        if constexpr (M == 2) {
+            if (cc.kind == 1 && !motion_free_2d(pv[0], pv[1], pw[0], pw[1], cc.shapes, cc.ns, cc.aabb)) fr = false;      // robots2D.jl:13-14
+        }
+        for (int k = 0; k < nbox && fr; ++k) {
+            // box in registers, comparisons combined without control flow (an LDS operand behind && / || becomes
+            // one serial round trip per term)
+            double blo[M], bhi[M];
+#pragma unroll
+            for (int i = 0; i < M; ++i) { blo[i] = sbox[(int64_t)k * 2 * M + i]; bhi[i] = sbox[(int64_t)k * 2 * M + M + i]; }
+            int sep = 0;
+#pragma unroll
+            for (int i = 0; i < M; ++i) sep |= (int)(bhi[i] < l[i]) | (int)(blo[i] > h[i]);
+            if (!sep) {
+                double v2w[M];
+#pragma unroll
+                for (int i = 0; i < M; ++i) v2w[i] = pw[i] - pv[i];
+                int best = 0;
+#pragma unroll
+                for (int i = 0; i < M; ++i) {
+                    const double corner = (pv[i] < blo[i]) ? blo[i] : bhi[i];
+                    const double lam = (corner - pv[i]) / v2w[i];
+                    int cnt = 0;
+#pragma unroll
+                    for (int jx = 0; jx < M; ++jx) {
+                        if (jx == i) continue;
+                        const double prod = v2w[jx] * lam;
+                        const double xx = pv[jx] + prod;
+                        cnt += (int)(blo[jx] <= xx);
+                        cnt += (int)(xx <= bhi[jx]);
+                    }
+                    best = max(best, cnt);
+                }
+                if (best == 2 * (M - 1)) fr = false;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NS; ++i) wp[i] = wn[i];
+    }
+    return fr;
+}
+
 template <int M>
 __global__ __launch_bounds__(256) void k_di_sweep(const double* __restrict__ X, int64_t N, const int64_t* __restrict__ colptr,
                                                   const int32_t* __restrict__ rowval, const double* __restrict__ tval,
@@ -287,73 +354,91 @@ __global__ __launch_bounds__(256) void k_di_sweep(const double* __restrict__ X, 
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool act = e < nnz;
     bool fr = false;
-    int segs = 0;
     if (act) {
         // column of entry e: largest x with colptr[x] <= e
         int64_t lo = 0, hi = N;
         while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (colptr[mid] <= e) lo = mid; else hi = mid; }
         const int64_t x = lo, y = rowval[e];
         const double t = tval[e];
-        double x0[NS], x1[NS], wp[NS], wn[NS];
+        double x0[NS], x1[NS];
 #pragma unroll
         for (int i = 0; i < NS; ++i) { x0[i] = X[y * NS + i]; x1[i] = X[x * NS + i]; }
-        di_state<M>(x0, x1, t, 0.0, wp);
-        fr = true;
-        for (int q = 0; q < 4 && fr; ++q) {
-            const double s = (q == 3) ? t : ((double)(q + 1) / 4.0) * t;
-            di_state<M>(x0, x1, t, s, wn);
-            if (!ws_point_in_ss<M>(wp, ss)) { fr = false; break; }
-            ++segs;
-            // segment wp -> wn in the workspace (first M coordinates) against every box, boxesND.jl:52-56
-            double l[M], h[M], pv[M], pw[M];
-#pragma unroll
-            for (int i = 0; i < M; ++i) {
-                pv[i] = wp[i]; pw[i] = wn[i];
-                l[i] = (pw[i] < pv[i]) ? pw[i] : pv[i];
-                h[i] = (pv[i] < pw[i]) ? pw[i] : pv[i];
-            }
-            if constexpr (M == 2) {
-                if (cc.kind == 1 && !motion_free_2d(pv[0], pv[1], pw[0], pw[1], cc.shapes, cc.ns, cc.aabb)) fr = false;      // robots2D.jl:13-14
-            }
-            for (int k = 0; k < nbox && fr; ++k) {
-                // box in registers, comparisons combined without control flow (an LDS operand behind && / || becomes
-                // one serial round trip per term)
-                double blo[M], bhi[M];
-#pragma unroll
-                for (int i = 0; i < M; ++i) { blo[i] = sbox[(int64_t)k * 2 * M + i]; bhi[i] = sbox[(int64_t)k * 2 * M + M + i]; }
-                int sep = 0;
-#pragma unroll
-                for (int i = 0; i < M; ++i) sep |= (int)(bhi[i] < l[i]) | (int)(blo[i] > h[i]);
-                if (!sep) {
-                    double v2w[M];
-#pragma unroll
-                    for (int i = 0; i < M; ++i) v2w[i] = pw[i] - pv[i];
-                    int best = 0;
-#pragma unroll
-                    for (int i = 0; i < M; ++i) {
-                        const double corner = (pv[i] < blo[i]) ? blo[i] : bhi[i];
-                        const double lam = (corner - pv[i]) / v2w[i];
-                        int cnt = 0;
-#pragma unroll
-                        for (int jx = 0; jx < M; ++jx) {
-                            if (jx == i) continue;
-                            const double prod = v2w[jx] * lam;
-                            const double xx = pv[jx] + prod;
-                            cnt += (int)(blo[jx] <= xx);
-                            cnt += (int)(xx <= bhi[jx]);
-                        }
-                        best = max(best, cnt);
-                    }
-                    if (best == 2 * (M - 1)) fr = false;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < NS; ++i) wp[i] = wn[i];
-        }
+        int segs = 0;
+        fr = di_motion_free<M>(x0, x1, t, sbox, nbox, ss, cc, segs);
         nseg[e] = (uint8_t)segs;
     }
     const unsigned long long bits = __ballot(fr);
     if (lane == 0 && (e - lane) < nnz) mask[(e - lane) >> 6] = bits;
+}
+
+// ---- in-place box edits (steer_delta.h): add / remove on the flagged columns ---------------------------------------------------
+// LDS: the delta boxes [nd][2 M]; for the remove, the remaining list [nrem][2 M] behind them (both lists together are the list the
+// whole sweep held in LDS before the edit, so they fit).  ctr[1] += entries whose F(delta) was evaluated.
+template <int M, bool REMOVE>
+__global__ __launch_bounds__(SD_THREADS) void k_di_delta(const double* __restrict__ X, const int64_t* __restrict__ colptr,
+                                                        const int32_t* __restrict__ rowval, const double* __restrict__ tval,
+                                                        const int32_t* __restrict__ cols, unsigned long long* __restrict__ ctr,
+                                                        const double* __restrict__ delta, int nd, const double* __restrict__ rem, int nrem,
+                                                        mpfmt_ss ss, unsigned long long* __restrict__ mask, uint8_t* __restrict__ nseg)
+{
+    constexpr int NS = 2 * M;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* sdel = (double*)smem;
+    double* srem = sdel + (int64_t)nd * 2 * M;
+    for (int t = threadIdx.x; t < nd * 2 * M; t += blockDim.x) sdel[t] = delta[t];
+    if (REMOVE) for (int t = threadIdx.x; t < nrem * 2 * M; t += blockDim.x) srem[t] = rem[t];
+    __syncthreads();
+    mpfmt_ws2d cc;
+    cc.kind = 0; cc.boxes = nullptr; cc.M = 0; cc.shapes = nullptr; cc.ns = 0;
+    cc.aabb = mpfmt_aabb2d();
+    const int lane = threadIdx.x & 63;
+    const int64_t gwave = ((int64_t)blockIdx.x * SD_THREADS + threadIdx.x) >> 6;
+    const int64_t nwaves = (int64_t)gridDim.x * (SD_THREADS / 64);
+    const int64_t ncols = (int64_t)ctr[0];
+    unsigned long long tested_n = 0;
+    for (int64_t ci = gwave; ci < ncols; ci += nwaves) {
+        const int64_t x = (int64_t)__builtin_amdgcn_readfirstlane(cols[ci]);
+        const int64_t beg = colptr[x], end = colptr[x + 1];
+        double x1[NS];
+#pragma unroll
+        for (int i = 0; i < NS; ++i) x1[i] = X[x * NS + i];
+        for (int64_t wd = beg >> 6; wd * 64 < end; ++wd) {
+            const int64_t e = wd * 64 + lane;
+            const unsigned long long cur = sd_word(mask, wd);
+            const bool mine = e >= beg && e < end;
+            const bool isfree = (cur >> lane) & 1ull;
+            // add: every entry (a blocked one keeps its bit, but its count can drop); remove: free entries stay as they are
+            const bool cand = REMOVE ? (mine && !isfree) : mine;
+            if (__ballot(cand) == 0) continue;
+            bool change = false;
+            if (cand) {
+                const int64_t y = rowval[e];
+                const double t = tval[e];
+                double x0[NS];
+#pragma unroll
+                for (int i = 0; i < NS; ++i) x0[i] = X[y * NS + i];
+                int sd = 0;
+                const bool fd = di_motion_free<M>(x0, x1, t, sdel, nd, ss, cc, sd);
+                if (REMOVE) {
+                    if (!fd) {                                 // from nothing against what is left
+                        int sr = 0;
+                        change = di_motion_free<M>(x0, x1, t, srem, nrem, ss, cc, sr);
+                        nseg[e] = (uint8_t)sr;
+                    }
+                } else {
+                    const int old = (int)nseg[e];
+                    if (sd < old) nseg[e] = (uint8_t)sd;
+                    change = isfree && !fd;
+                }
+            }
+            const unsigned long long ch = __ballot(change);
+            if (lane == 0 && ch) {
+                if (REMOVE) atomicOr(&mask[wd], ch); else atomicAnd(&mask[wd], ~ch);
+            }
+            tested_n += (unsigned long long)__popcll(__ballot(cand));
+        }
+    }
+    if (lane == 0 && tested_n) atomicAdd(ctr + 1, tested_n);
 }
 
 // batch steer on explicit pairs: (cost, t*) = steer(L, x0, x1, r)
@@ -564,6 +649,35 @@ int32_t mpfmt_di_sweep(mpfmt_ctx* ctx)
         tm3.end("di_sweep");
     }
     ctx->steer_swept = true;
+    return MPFMT_OK;
+}
+
+// the list the whole sweep stages in LDS: M boxes of an m-dimensional workspace are within its limit
+bool mpfmt_di_sweep_fits(int64_t M, int m) { return (size_t)M * 2 * m * sizeof(double) + 16 <= 60 * 1024; }
+
+// flag + update on ctx->stream for a resident, swept double-integrator graph: d_delta = the nd boxes added (already at the end of
+// ctx->boxes) or a copy of the nd boxes removed (ctx->boxes / ctx->M: the remaining list).  The caller owns bd_cols / bd_ctr.
+int32_t mpfmt_di_delta_launch(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove)
+{
+    const int m = ctx->d / 2;
+    const int64_t N = ctx->N;
+    const int nrem = remove ? ctx->M : 0;
+    const size_t lds = (size_t)(nd + nrem) * 2 * m * sizeof(double) + 16;
+    if (lds > 60 * 1024) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "double-integrator box edit: the lists exceed the sweep's LDS limit");
+    const unsigned nbf = (unsigned)((N + SD_THREADS - 1) / SD_THREADS), nbu = sd_update_blocks(ctx);
+    const double pad_a = ctx->steer_r, pad_b = ctx->steer_r / sqrt(ctx->di_rho);
+    unsigned long long* mask = (unsigned long long*)ctx->graph_free.get();
+    DISPATCH_M(m, {
+        hipLaunchKernelGGL((k_sd_flag<2 * DM, DM, true>), dim3(nbf), dim3(SD_THREADS), 0, ctx->stream, ctx->Xo, N, d_delta, (int)nd, pad_a, pad_b,
+                           ctx->bd_cols, ctx->bd_ctr);
+        if (remove)
+            hipLaunchKernelGGL((k_di_delta<DM, true>), dim3(nbu), dim3(SD_THREADS), lds, ctx->stream, ctx->Xo, ctx->colptr, ctx->rowval, ctx->tval,
+                               ctx->bd_cols, ctx->bd_ctr, d_delta, (int)nd, ctx->boxes, nrem, ctx->ss, mask, ctx->steer_nseg);
+        else
+            hipLaunchKernelGGL((k_di_delta<DM, false>), dim3(nbu), dim3(SD_THREADS), lds, ctx->stream, ctx->Xo, ctx->colptr, ctx->rowval, ctx->tval,
+                               ctx->bd_cols, ctx->bd_ctr, d_delta, (int)nd, (const double*)nullptr, 0, ctx->ss, mask, ctx->steer_nseg);
+    });
+    HIPCHK(ctx, hipGetLastError());
     return MPFMT_OK;
 }
 

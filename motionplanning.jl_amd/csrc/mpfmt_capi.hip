@@ -402,11 +402,49 @@ static bool boxes_delta_in_place(const mpfmt_ctx* ctx)
            ctx->graph_free && ctx->step_state != 1;
 }
 
+// the same for a resident, swept steering graph (double integrator, cars): mask and segment counts follow (steer_delta.h).  The
+// conditions are those under which the space's whole sweep would accept the resulting list.
+static bool steer_delta_in_place(const mpfmt_ctx* ctx)
+{
+    if (!(ctx->world == 1 && ctx->cc_kind == 0 && ctx->steer_filled && ctx->steer_swept && ctx->nnz > 0 && ctx->graph_free && ctx->steer_nseg))
+        return false;
+    if (ctx->steer_kind == MPFMT_STEER_DI) {
+        const int m = ctx->d / 2;
+        return ctx->d % 2 == 0 && m >= 1 && m <= 6 && ctx->dw == m && (!ctx->ss.has || ctx->ss.d == ctx->d) && mpfmt_di_sweep_fits(ctx->M, m);
+    }
+    return ctx->d == 3 && ctx->dw == 2 && (!ctx->ss.has || ctx->ss.d == 3);
+}
+
+static int32_t steer_delta_apply(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove)
+{
+    int32_t rc;
+    if ((rc = mpfmt_side_join(ctx))) return rc;
+    if ((rc = ctx->bd_cols.ensure(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(ctx->N, 1)))) return rc;
+    if ((rc = ctx->bd_ctr.ensure(ctx, sizeof(unsigned long long) * 2))) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->bd_ctr, 0, sizeof(unsigned long long) * 2, ctx->stream));
+    mpfmt_timed tm(ctx);
+    rc = ctx->steer_kind == MPFMT_STEER_DI ? mpfmt_di_delta_launch(ctx, d_delta, nd, remove) : mpfmt_car_delta_launch(ctx, d_delta, nd, remove);
+    if (rc) return rc;
+    tm.end("steer_delta");
+    unsigned long long h[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(h, ctx->bd_ctr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->bd_columns = (int64_t)h[0]; ctx->bd_entries = (int64_t)h[1];
+    return MPFMT_OK;
+}
+
 // the list has been edited: the mask follows in place (delta = the boxes added or a copy of those removed) or goes stale
 static int32_t boxes_delta_finish(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove)
 {
     ctx->bd_columns = ctx->bd_entries = 0;
     ctx->pend_valid = false;                                 // (a pending list belongs to the obstacle set it was made against)
+    if (steer_delta_in_place(ctx)) {                         // (a steering graph is resident: the Euclidean graph state is not)
+        ctx->bd_path = 1;
+        ctx->graph_swept = false;
+        const int32_t rc = steer_delta_apply(ctx, d_delta, nd, remove);
+        if (rc) { ctx->steer_swept = false; ctx->bd_path = 0; return rc; }   // (the list stands, the mask is swept again)
+        return MPFMT_OK;
+    }
     ctx->steer_swept = false;
     ctx->bd_path = boxes_delta_in_place(ctx) ? 1 : 0;
     if (!ctx->bd_path) { ctx->graph_swept = false; return MPFMT_OK; }
@@ -1991,8 +2029,10 @@ static int32_t steer_fmtstar(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double 
 
 // fmtstar! in a steering space with the recursion on the device (kernels_wavefront.hip, directed form; the Reeds-Shepp graph is
 // structurally symmetric, so its rows are its columns and the same form applies): graph, waypoint sweep and the transpose (forward
-// sets) on the device, then cost-band batches; `single` reproduces the host recursion's pop order exactly.  A resident double-
-// integrator graph of the same (rho, r) is reused, and its sweep too while the obstacles stay; the car graphs are built anew.
+// sets) on the device, then cost-band batches; `single` reproduces the host recursion's pop order exactly.  A resident graph of
+// the same space and parameters -- (rho, r) for the double integrator; kind, turning radius, speed and r for the cars -- is reused, and
+// its sweep too while it is valid: it stays valid across mpfmt_boxes_add / mpfmt_boxes_remove, which bring the mask and the segment
+// counts up to date in place (steer_delta.h), and goes with mpfmt_upload_boxes, new bounds or new samples.
 static int32_t steer_fmtstar_wavefront(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b, double r, int64_t init_idx, int32_t checkpts,
                                        int32_t goal_kind, const double* goal_params, double band, int32_t flags, int64_t* A, double* C,
                                        int64_t* path, mpfmt_fmt_result* res, mpfmt_wf_info* info)
@@ -2007,7 +2047,8 @@ static int32_t steer_fmtstar_wavefront(mpfmt_ctx* ctx, mpfmt_steer kind, double 
     t[0] = now();
     if ((rc = steer_prelude(ctx, s, a, r, init_idx, goal_kind, X, F))) return rc;
     t[1] = now();
-    const bool resident = kind == MPFMT_STEER_DI && ctx->steer_filled && ctx->steer_kind == kind && ctx->di_rho == a && ctx->steer_r == r;
+    const bool resident = ctx->steer_filled && ctx->steer_kind == kind && ctx->steer_r == r &&
+                          (kind == MPFMT_STEER_DI ? ctx->di_rho == a : (ctx->car_rt == a && ctx->car_sp == b));
     if (!resident && (rc = steer_build(ctx, kind, a, b, r))) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     t[2] = now();
@@ -2083,6 +2124,21 @@ static int32_t steer_graph_edges_free(mpfmt_ctx* ctx, mpfmt_steer kind, uint64_t
         if (nseg) HIPCHK(ctx, hipMemcpyAsync(nseg, ctx->steer_nseg, (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
+    return MPFMT_OK;
+}
+
+// the resident, swept mask and counts as they are (after in-place box edits: what a whole sweep of the list would write); no sweep
+int32_t mpfmt_steer_mask_read(mpfmt_ctx* ctx, uint64_t* mask, uint8_t* nseg)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!ctx->steer_filled || !ctx->steer_swept) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no swept steering graph resident");
+    const int64_t nnz = ctx->nnz, words = (nnz + 63) / 64;
+    if (nnz == 0) return MPFMT_OK;
+    if (!mask) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "mask is NULL");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpyAsync(mask, ctx->graph_free, sizeof(uint64_t) * (size_t)words, hipMemcpyDeviceToHost, ctx->stream));
+    if (nseg) HIPCHK(ctx, hipMemcpyAsync(nseg, ctx->steer_nseg, (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return MPFMT_OK;
 }
 
@@ -2363,6 +2419,7 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "roadmap_near_total") == 0) { *value = ctx->roadmap_near_total; return MPFMT_OK; }
     if (strcmp(name, "shortcut_tests_evaluated") == 0) { *value = ctx->shortcut_tests; return MPFMT_OK; }
     if (strcmp(name, "shortcut_checks") == 0) { *value = ctx->shortcut_checks; return MPFMT_OK; }
+    if (strcmp(name, "steer_swept") == 0) { *value = (ctx->steer_filled && ctx->steer_swept) ? 1 : 0; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_path") == 0) { *value = ctx->bd_path; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_columns") == 0) { *value = ctx->bd_columns; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_entries") == 0) { *value = ctx->bd_entries; return MPFMT_OK; }

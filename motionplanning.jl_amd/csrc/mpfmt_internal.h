@@ -544,6 +544,10 @@ int32_t mpfmt_launch_graph_sweep(mpfmt_ctx* ctx, const int32_t* spec_fail = null
 
 // kernels_boxdelta.hip --------------------------------------------------------------------------
 int32_t mpfmt_boxdelta_apply(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove);
+// the same for a resident, swept steering graph (steer_delta.h): mask AND segment counts; flag + update launched on ctx->stream
+int32_t mpfmt_di_delta_launch(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove);      // kernels_di.hip
+int32_t mpfmt_car_delta_launch(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove);     // kernels_car.hip
+bool mpfmt_di_sweep_fits(int64_t M, int m);              // M boxes of an m-dimensional workspace are within the whole sweep's LDS limit
 
 // kernels_di.hip ----------------------------------------------------------------------------------
 #include <functional>

@@ -239,7 +239,8 @@ def _cc_bound_to(P):
 
 def addobstacle_(P, o):
     """In-place addobstacle (boxesND.jl): appends the box to P.CC.boxes; when P.CC is bound to P.ctx the context's list and the
-    resident free-edge mask follow in place (Context.boxes_add), so the next solve on the same samples sweeps nothing again."""
+    resident free-edge mask follow in place (Context.boxes_add), so the next solve on the same samples sweeps nothing again -- in the
+    Euclidean spaces and, mask and segment counts, in the double-integrator and car spaces (fmtstar_ with band=...)."""
     CC = P.CC
     if not isinstance(CC, PointRobotNDBoxes):
         raise TypeError("in-place obstacle edits are for PointRobotNDBoxes (the 2-D shape world is rebuilt: CC.addobstacle)")
@@ -276,6 +277,12 @@ def removeobstacle_(P, i):
     return P
 
 
+def _holds_swept_steering_graph(CC, SS, ctx):
+    """ctx holds CC's list, bound with SS (nothing changed its checker since), and a swept steering graph."""
+    return (isinstance(CC, PointRobotNDBoxes) and CC._ctx is ctx and CC._ss is SS and CC._bound is not None
+            and CC._bound[1] == getattr(ctx, "_cc_epoch", None) and hasattr(ctx, "stat") and ctx.stat("steer_swept") == 1)
+
+
 def is_free_state(v, CC, SS, ctx):
     """in_state_space(v, SS) && is_free_state(state2workspace(v), CC)   (statespaces.jl:151-152); v: (d,) or (n, d)."""
     V = np.atleast_2d(np.asarray(v, dtype=np.float64))
@@ -285,6 +292,14 @@ def is_free_state(v, CC, SS, ctx):
         out = _lib.unpack_bits(ctx.states_free(V), len(V))
     else:                                                   # workspace = leading coordinates (OutputMatrix [I 0])
         inb = np.all((SS.lo <= V) & (V <= SS.hi), axis=1)
+        if _holds_swept_steering_graph(CC, SS, ctx):
+            # binding the checker to the workspace alone and back is two uploads, and an upload throws away the swept mask that
+            # boxes_add / boxes_remove keep up to date: the point test (comparisons only, k_points_free) is made here instead
+            Pw = V[:, :SS.workspace_dim]
+            out = inb.copy()
+            for b in CC.boxes:
+                out &= np.any(~(b.lo <= Pw) | ~(Pw <= b.hi), axis=1)
+            return bool(out[0]) if np.ndim(v) == 1 else out
         CC._bind_workspace(ctx, SS)                           # the checker alone, no state-space bounds (they were applied above)
         out = _lib.unpack_bits(ctx.states_free(np.ascontiguousarray(V[:, :SS.workspace_dim])), len(V)) & inb
         CC._bind(ctx, SS)
