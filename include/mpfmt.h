@@ -242,7 +242,8 @@ MPFMT_API int32_t mpfmt_host_fmt_recursion(int64_t N, int32_t d, const double* X
 
 /* ---- roadmap queries (PRM*): exact shortest paths over the free-edge graph.  The reference names the graph planner and never
  *      built it (src/problems.jl:57, "# TODO: graph (PRM)"); the semantics here are this library's.
- *      The graph is the ctx's resident graph slot -- r-disc or k-nearest -- in the device-native CSC: entry b of column x with row y
+ *      The graph is the ctx's resident graph slot -- r-disc, k-nearest, or a filled and swept steering graph (double integrator,
+ *      Dubins, Reeds-Shepp: the same device slots and the same direction convention) -- in the device-native CSC: entry b of column x with row y
  *      is the DIRECTED edge y -> x of weight nzval[b]; its free bit is mask bit b = is_free_motion(V[y], V[x]) (the reading of
  *      mpfmt_host_fmt_recursion).  An edge is USABLE iff its bit is set and, with checkpts != 0, the point bit F[x] of its target is
  *      set (fmt.jl:71); the source itself is exempt from F.
@@ -262,10 +263,13 @@ MPFMT_API int32_t mpfmt_host_fmt_recursion(int64_t N, int32_t d, const double* X
  * mpfmt_graph_sssp : the same field on the device for nsrc sources (1-based), one after another (mpfmt_graph_sssp_multi below runs 64 per
  *      pass), over the resident graph and mask
  *      WITHOUT copying or transposing them.  C / A are nsrc x N, source-major (A may be NULL); info[nsrc] (may be NULL).
- *      checkpts != 0 sweeps the point bitmap on the device first.  MPFMT_ERR_STATE: no resident r-disc / k-nearest graph, no mask
+ *      checkpts != 0 sweeps the point bitmap on the device first (on a steering ctx: the bitmap of the steering planners,
+ *      is_free_state = the state-space bounds on all d coordinates and the point test on the first dw).  MPFMT_ERR_STATE: no
+ *      resident r-disc / k-nearest / steering graph, no mask
  *      for the current graph and obstacle set (a mask goes stale with mpfmt_upload_boxes / mpfmt_upload_shapes2d /
  *      mpfmt_set_state_bounds: sweep again -- this call never sweeps edges on its own), or a sharded ctx; MPFMT_ERR_ARG: a source
- *      out of range.  A refused call leaves the ctx as it was.
+ *      out of range.  A refused call leaves the ctx as it was.  A steering mask stays valid across mpfmt_boxes_add / _remove (they
+ *      bring it up to date in place) and goes stale like the Euclidean one.
  * mpfmt_prmstar / mpfmt_knn_prmstar : the planner: mpfmt_graph_step_device(r) (k-nearest: the build + sweep of mpfmt_knn_fmtstar)
  *      -- graph and mask are reused when they are resident for this r (k) and obstacle set, a stale mask is swept again --, the
  *      checkpts sweep, the field from init_idx and goal extraction: the goal node is the reached sample inside the goal region of
@@ -290,6 +294,52 @@ MPFMT_API int32_t mpfmt_prmstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int3
                       int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
 MPFMT_API int32_t mpfmt_knn_prmstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
                           int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
+
+/* ---- cost-to-go: the field of a target set, and the PRM* planners of the steering spaces.
+ *      Notation of the roadmap queries above: entry b of column x with row y is the DIRECTED edge y -> x of weight w_yx = nzval[b].
+ *      It is USABLE iff mask bit b is set and, with checkpts, F[x] is set.  There is no exemption: a target t with F[t] clear keeps
+ *      G[t] = 0 and simply has no usable edge into it.
+ *      Costs for a target set T (1-based, duplicates allowed; ntgt = 0 is legal: all +Inf, reached = 0): G[t] = 0 for every t in T,
+ *      whatever F[t] is; otherwise G[y] = the least value of fl(G[x] + w_yx) over usable edges, i.e. the least fixed point of
+ *      G[y] = min(G0[y], min_x fl(G[x] + w_yx)); +Inf when no target is reachable from y.  This is the fold of a path from the
+ *      target BACKWARDS, (((0 + w_last) + ...) + w_first): it is NOT bit-equal to the forward fold of the same path that
+ *      mpfmt_graph_sssp computes, and on a quasi-metric graph (double integrator, Dubins, k-nearest) the two fields differ by more
+ *      than rounding.  fl(a + w) is nondecreasing in a and >= a, so any relaxation order that runs until nothing changes gives the
+ *      bits of Dijkstra on the reversed graph: mpfmt_graph_sssp_to and mpfmt_host_graph_sssp_to agree bit for bit, no tolerance.
+ *      Successors: S[y] (1-based; 0 for targets and for unreached samples) = the usable x of lowest (G[x], x) among those with
+ *      fl(G[x] + w_yx) == G[y]: a function of the finished G alone.  S may be NULL.  Following S from a reached y arrives at a
+ *      target in fewer than N hops under the condition stated for the parents above.
+ * mpfmt_host_graph_sssp_to : a binary-heap Dijkstra over the reversed edges on the host (the arrays and the argument checks of
+ *      mpfmt_host_graph_sssp, plus MPFMT_ERR_ARG for a target out of range or ntgt < 0).  No ctx, no device.
+ * mpfmt_graph_sssp_to : the same field on the device over whatever swept graph is resident (r-disc, k-nearest, steering), read in
+ *      place: a push along the entries of the columns whose label changed, 64-bit atomic minima on the labels, rounds as separate
+ *      launches.  info (may be NULL) has the fields of mpfmt_sssp_info: reached counts G < +Inf, targets included; relaxations
+ *      counts fl(G[x] + w) evaluated.  The refusals of mpfmt_graph_sssp (MPFMT_ERR_ARG: a target out of range); a refused call
+ *      leaves the ctx as it was.  It shares the buffers of mpfmt_graph_sssp (the parent buffer only when S is asked for) and adds 8 N bytes of its own, with S only.
+ *      Timers: "sssp_to_push" (all rounds), "sssp_to_successors"; stats "sssp_rounds", "sssp_relaxations", "sssp_reached", and
+ *      "sssp_to_columns" / "sssp_to_entries_read" (columns walked and their entries, all rounds: a round reads only the columns of
+ *      samples that changed), "sssp_to_atomics" (atomic minima issued).
+ * mpfmt_di_prmstar / mpfmt_dubins_prmstar / mpfmt_reedsshepp_prmstar : mpfmt_prmstar in the steering spaces: the prelude of the
+ *      steering FMT* planners (MPFMT_ERR_INFEASIBLE for a blocked init), the graph of the space -- a resident graph of the same
+ *      space and parameters is reused, and its sweep while it is valid, which includes after mpfmt_boxes_add / _remove --, the
+ *      cost-to-come field from init_idx and the goal extraction of mpfmt_prmstar: the reached sample in the region of lowest
+ *      (C, index).  The goal predicate is that of the steering FMT* planners: POINT = the exact state, RECT / BALL on the first dw
+ *      coordinates.  res as in mpfmt_prmstar; collision_checks = 0.
+ * Tracked fields (mpfmt_field_*) and external states (mpfmt_roadmap_*) stay refused on a steering graph: MPFMT_ERR_STATE,
+ *      "Euclidean graphs only". */
+MPFMT_API int32_t mpfmt_host_graph_sssp_to(int64_t N, const int64_t* colptr, const int32_t* rowval, const double* nzval,
+                                           const uint64_t* efree, const uint64_t* F, const int64_t* targets, int64_t ntgt,
+                                           double* G, int64_t* S);
+MPFMT_API int32_t mpfmt_graph_sssp_to(mpfmt_ctx* ctx, const int64_t* targets, int64_t ntgt, int32_t checkpts,
+                                      double* G, int64_t* S, mpfmt_sssp_info* info);
+MPFMT_API int32_t mpfmt_di_prmstar(mpfmt_ctx* ctx, double rho, double r, int64_t init_idx, int32_t checkpts, int32_t goal_kind,
+                                   const double* goal_params, int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
+MPFMT_API int32_t mpfmt_dubins_prmstar(mpfmt_ctx* ctx, double turn_radius, double speed, double r, int64_t init_idx, int32_t checkpts,
+                                       int32_t goal_kind, const double* goal_params, int64_t* A, double* C, int64_t* path,
+                                       mpfmt_fmt_result* res);
+MPFMT_API int32_t mpfmt_reedsshepp_prmstar(mpfmt_ctx* ctx, double turn_radius, double speed, double r, int64_t init_idx, int32_t checkpts,
+                                           int32_t goal_kind, const double* goal_params, int64_t* A, double* C, int64_t* path,
+                                           mpfmt_fmt_result* res);
 
 /* ---- a cost-to-come field kept valid across box edits: repair, not recompute (DESIGN.md "a tracked field").
  *      Notation of the roadmap queries above: entry b of column x with row y is the edge y -> x; it is usable iff mask bit b is set
@@ -419,7 +469,7 @@ MPFMT_API int32_t mpfmt_host_roadmap_query(int64_t N, int32_t d, const double* X
  *      512-byte row read.  The least fixed point is unique and independent of the schedule (the roadmap queries above), so every value is
  *      BIT-IDENTICAL to what the one-field calls return; only rounds, relaxations and times differ.
  * mpfmt_graph_sssp_multi : the argument and result contract of mpfmt_graph_sssp -- sources 1-based (duplicates allowed), C / A nsrc x N
- *      source-major (A may be NULL: no parent pass runs and no parent buffer is held), info[nsrc] (may be NULL), r-disc or k-nearest graph,
+ *      source-major (A may be NULL: no parent pass runs and no parent buffer is held), info[nsrc] (may be NULL), the same resident graphs,
  *      the same refusals and codes, and it never sweeps edges on its own.  Sources run in groups of up to 64, one group per pass; nsrc == 0
  *      succeeds and does nothing.  C and A equal those of mpfmt_graph_sssp for the same source, bit for bit.  info[q].reached is exact per
  *      source; info[q].rounds, .relaxations and .ms_device are the GROUP's values, repeated for each of its members, and relaxations counts

@@ -209,6 +209,58 @@ function hip_graph_sssp(DS::HIPDistanceDS, N::Int, sources::Vector{Int}; checkpt
     C, A, info
 end
 
+# ---- PRM* over the steering graphs and the cost-to-go field (include/mpfmt.h "cost-to-go").  The symbols are named here once; the C
+#      caller that executes these calls with the same widths is tests/abi_c/abi_caller10.c. ----
+# (the three planners are executed by abi_caller10.c, not by abi_caller3.c, which holds the Euclidean planners' symbols)
+const sym_host_graph_sssp_to = :mpfmt_host_graph_sssp_to
+const sym_graph_sssp_to = :mpfmt_graph_sssp_to
+const sym_di_prmstar = Symbol("mpfmt_di_prmstar")
+const sym_dubins_prmstar = Symbol("mpfmt_dubins_prmstar")
+const sym_reedsshepp_prmstar = Symbol("mpfmt_reedsshepp_prmstar")
+# the feedback policy over the resident swept graph (r-disc, k-nearest or steering): from every sample the optimal cost to the target
+# set and the next sample on the way; G[i] = Inf: no target reachable, S[i] = 0: target or unreached
+function hip_graph_sssp_to(DS::HIPDistanceDS, N::Int, targets::Vector{Int}; checkpts = true)
+    G = Vector{Float64}(N); S = Vector{Int}(N); info = Ref{SsspInfo}()
+    chk(DS.ctx, ccall((sym_graph_sssp_to, libmpfmt), Int32, (Ptr{Void}, Ptr{Int64}, Int64, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{SsspInfo}),
+                      DS.ctx, targets, length(targets), checkpts, G, S, info))
+    G, S, info[]
+end
+# the same field on the host over exported arrays (colptr 0-based, rowval 0-based Int32, packed masks; F may be C_NULL)
+function host_graph_sssp_to(colptr::Vector{Int}, rowval::Vector{Int32}, nzval::Vector{Float64}, efree::Vector{UInt64}, F, targets::Vector{Int})
+    N = length(colptr) - 1
+    G = Vector{Float64}(N); S = Vector{Int}(N)
+    rc = ccall((sym_host_graph_sssp_to, libmpfmt), Int32,
+               (Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Int64}),
+               N, colptr, rowval, nzval, efree, F, targets, length(targets), G, S)
+    rc == 0 || error("mpfmt_host_graph_sssp_to rejected its arguments")
+    G, S
+end
+# PRM* in the double-integrator space (rho, cost radius r) and in the car spaces (kind = :dubins or :reedsshepp; turning radius, speed, r)
+function hip_steer_prmstar!(P::MPProblem, kind::Symbol, a::Float64, b::Float64, r::Float64; init_idx = 1, checkpts = true)
+    DS = P.V.DS; N = length(P.V)
+    A = Vector{Int}(N); C = Vector{Float64}(N); path = Vector{Int}(N); res = Ref{FmtResult}()
+    g = [P.goal.center; P.goal.radius]
+    rc = kind == :di ?
+        ccall((sym_di_prmstar, libmpfmt), Int32,
+              (Ptr{Void}, Float64, Float64, Int64, Int32, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{FmtResult}),
+              DS.ctx, a, r, init_idx, checkpts, 1, g, A, C, path, res) :
+        kind == :dubins ?
+        ccall((sym_dubins_prmstar, libmpfmt), Int32,
+              (Ptr{Void}, Float64, Float64, Float64, Int64, Int32, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{FmtResult}),
+              DS.ctx, a, b, r, init_idx, checkpts, 1, g, A, C, path, res) :
+        ccall((sym_reedsshepp_prmstar, libmpfmt), Int32,
+              (Ptr{Void}, Float64, Float64, Float64, Int64, Int32, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{FmtResult}),
+              DS.ctx, a, b, r, init_idx, checkpts, 1, g, A, C, path, res)
+    rc == -6 && (warn("Initial state is infeasible!"); P.status = :failed; return Inf)
+    chk(DS.ctx, rc)
+    P.status = res[].status == 1 ? :solved : :failed
+    P.solution = MPSolution(P.status, res[].cost, (res[].ms_graph + res[].ms_sweep + res[].ms_host_loop) / 1e3,
+                            Dict("collision_checks" => res[].collision_checks, "tree" => A, "cost" => res[].cost,
+                                 "path" => path[1:res[].path_len], "planner" => "prmstar", "r" => r, "num_samples" => N,
+                                 "cost_to_come" => C))
+    P.status, P.solution.cost, P.solution.elapsed
+end
+
 # states that are NOT samples (the robot's present pose, candidate goals) against the resident roadmap: nothing is rebuilt.
 # S, G: d x n matrices (one state per column).  hip_roadmap_query -> (cost[n], path_ptr[n + 1] 0-based, path (1-based samples), info[n]);
 # hip_roadmap_attach -> the goal half for many goals over ONE field C (a column of hip_graph_sssp): (cost[n], parent[n], 0 = none)

@@ -109,6 +109,15 @@ SYMBOLS = [
     ("mpfmt_host_graph_sssp", C.c_int32, [C.c_int64, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p, C.c_int64, c_d_p, c_i64_p]),
     ("mpfmt_graph_sssp", C.c_int32, [C.c_void_p, c_i64_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(SsspInfo)]),
     ("mpfmt_graph_sssp_multi", C.c_int32, [C.c_void_p, c_i64_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(SsspInfo)]),
+    ("mpfmt_host_graph_sssp_to", C.c_int32, [C.c_int64, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p, c_i64_p, C.c_int64, c_d_p,
+                                             c_i64_p]),
+    ("mpfmt_graph_sssp_to", C.c_int32, [C.c_void_p, c_i64_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(SsspInfo)]),
+    ("mpfmt_di_prmstar", C.c_int32, [C.c_void_p, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32, c_d_p,
+                                     c_i64_p, c_d_p, c_i64_p, C.POINTER(FmtResult)]),
+    ("mpfmt_dubins_prmstar", C.c_int32, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32, c_d_p,
+                                         c_i64_p, c_d_p, c_i64_p, C.POINTER(FmtResult)]),
+    ("mpfmt_reedsshepp_prmstar", C.c_int32, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32, c_d_p,
+                                             c_i64_p, c_d_p, c_i64_p, C.POINTER(FmtResult)]),
     ("mpfmt_field_begin", C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(FieldInfo)]),
     ("mpfmt_field_update", C.c_int32, [C.c_void_p, C.POINTER(FieldInfo)]),
     ("mpfmt_field_read", C.c_int32, [C.c_void_p, c_d_p, c_i64_p]),
@@ -335,6 +344,26 @@ def host_graph_sssp(colptr0, rowval0, nzval, efree, F=None, source=1, want_paren
     if rc != 0:
         raise MPFMTError(rc, "mpfmt_host_graph_sssp rejected its arguments")
     return Cc[:N], (None if A is None else A[:N])
+
+
+def host_graph_sssp_to(colptr0, rowval0, nzval, efree, F=None, targets=(), want_successors=True):
+    """PRM* cost-to-go field of a target set (1-based) by a host Dijkstra over the reversed edges of the device-native arrays
+    (include/mpfmt.h, "cost-to-go"); host only, no GPU needed.  Arguments as host_graph_sssp.  Returns (G, S): G = +Inf where no target
+    is reachable, 0 on the targets; S 1-based successors (0 = target or unreached; None without want_successors)."""
+    colptr0 = np.ascontiguousarray(colptr0, dtype=np.int64)
+    N = colptr0.size - 1
+    rowval0 = np.ascontiguousarray(rowval0, dtype=np.int32)
+    nzval = np.ascontiguousarray(nzval, dtype=np.float64)
+    efree = np.ascontiguousarray(efree, dtype=np.uint64)
+    Fp = None if F is None else np.ascontiguousarray(F, dtype=np.uint64)
+    tg = np.ascontiguousarray(np.atleast_1d(np.asarray(targets, dtype=np.int64)))
+    G = np.empty(max(N, 1), dtype=np.float64)
+    S = np.empty(max(N, 1), dtype=np.int64) if want_successors else None
+    rc = lib().mpfmt_host_graph_sssp_to(N, _ip(colptr0), rowval0.ctypes.data_as(C.POINTER(C.c_int32)), _dp(nzval), _up(efree), _up(Fp),
+                                        _ip(tg) if tg.size else None, int(tg.size), _dp(G), _ip(S))
+    if rc != 0:
+        raise MPFMTError(rc, "mpfmt_host_graph_sssp_to rejected its arguments")
+    return G[:N], (None if S is None else S[:N])
 
 
 def host_field_repair(colptr0, rowval0, nzval, efree, F, dirty, C_old, A_old, source=1):
@@ -692,7 +721,8 @@ class Context:
 
     # ---- PRM* roadmap queries: shortest paths over the resident free-edge graph ------------------------------
     def graph_sssp(self, sources, checkpts=True, want_parents=True):
-        """Cost-to-come fields over the resident graph and mask (graph_step_device, or knn_graph + knn_graph_edges_free) for the
+        """Cost-to-come fields over the resident graph and mask (graph_step_device, knn_graph + knn_graph_edges_free, or a steering graph
+        and its sweep: di_graph / dubins_graph / reedsshepp_graph + *_graph_edges_free, or what a steering planner left) for the
         1-based `sources`: dict(C (nsrc, N), +Inf = unreached; A (nsrc, N) 1-based parents or None; info = one dict per source with
         reached, rounds, relaxations, ms_device)."""
         src = np.ascontiguousarray(np.atleast_1d(sources), dtype=np.int64)
@@ -705,7 +735,8 @@ class Context:
                     info=[{k: getattr(info[i], k) for k, _ in SsspInfo._fields_} for i in range(n)])
 
     def graph_sssp_multi(self, sources, checkpts=True, want_parents=True):
-        """graph_sssp with up to 64 sources per pass over the graph (mpfmt_graph_sssp_multi): the same dict, C and A bit-identical;
+        """graph_sssp with up to 64 sources per pass over the graph (mpfmt_graph_sssp_multi), on the same resident graphs (Euclidean or
+        steering): the same dict, C and A bit-identical;
         info[q]["rounds"], ["relaxations"] and ["ms_device"] are those of the source's group of 64."""
         src = np.ascontiguousarray(np.atleast_1d(sources), dtype=np.int64)
         n = src.size
@@ -715,6 +746,18 @@ class Context:
         self._chk(self._L.mpfmt_graph_sssp_multi(self._h, _ip(src), n, int(bool(checkpts)), _dp(Cc), _ip(A), info))
         return dict(C=Cc[:n, :self.N], A=None if A is None else A[:n, :self.N],
                     info=[{k: getattr(info[i], k) for k, _ in SsspInfo._fields_} for i in range(n)])
+
+    def graph_sssp_to(self, targets, checkpts=True, want_successors=True):
+        """The cost-to-go field of the 1-based `targets` over whatever swept graph is resident (r-disc, k-nearest, steering;
+        mpfmt_graph_sssp_to): dict(G (N,), +Inf = no target reachable, 0 on the targets; S (N,) 1-based successors, 0 = target or
+        unreached, None without want_successors; info = reached, rounds, relaxations, ms_device)."""
+        tg = np.ascontiguousarray(np.atleast_1d(np.asarray(targets, dtype=np.int64)))
+        G = np.empty(max(self.N, 1), dtype=np.float64)
+        S = np.empty(max(self.N, 1), dtype=np.int64) if want_successors else None
+        info = SsspInfo()
+        self._chk(self._L.mpfmt_graph_sssp_to(self._h, _ip(tg) if tg.size else None, int(tg.size), int(bool(checkpts)), _dp(G), _ip(S),
+                                              C.byref(info)))
+        return dict(G=G[:self.N], S=None if S is None else S[:self.N], info={k: getattr(info, k) for k, _ in SsspInfo._fields_})
 
     # ---- a cost-to-come field kept valid across box edits (include/mpfmt.h) ---------------------------------------------------
     def field_begin(self, source=1, checkpts=True):
@@ -1018,6 +1061,15 @@ class Context:
                                                              _dp(g), _ip(A), _dp(Cc), _ip(path), C.byref(res)))
         return self._fmt_out(res, A, Cc, path)
 
+    def _steer_prmstar(self, space, params, goal_kind, goal_params, init_idx, checkpts):
+        g = np.ascontiguousarray(goal_params, dtype=np.float64)
+        A, Cc, path = self._fmt_arrays()
+        res = FmtResult()
+        self._chk(getattr(self._L, f"mpfmt_{space}_prmstar")(self._h, *map(float, params), int(init_idx), int(bool(checkpts)), int(goal_kind),
+                                                             _dp(g), _ip(A), _dp(Cc), _ip(path), C.byref(res)))
+        self.nnz = int(res.nnz)
+        return self._fmt_out(res, A, Cc, path)
+
     def _steer_fmtstar_wavefront(self, space, params, goal_kind, goal_params, band, single, init_idx, checkpts, want_tree=True):
         g = np.ascontiguousarray(goal_params, dtype=np.float64)
         A, Cc, path = self._fmt_arrays(want_tree)
@@ -1194,6 +1246,15 @@ class Context:
 
     def di_fmtstar(self, rho, r, goal_kind, goal_params, init_idx=1, checkpts=True):
         return self._steer_fmtstar("di", (rho, r), goal_kind, goal_params, init_idx, checkpts)
+
+    def di_prmstar(self, rho, r, goal_kind, goal_params, init_idx=1, checkpts=True):
+        """PRM* in the double-integrator space (mpfmt_di_prmstar): the graph and its sweep (reused while resident and valid, also after
+        boxes_add / boxes_remove), the exact cost-to-come field of init_idx and the best goal sample; the dict of prmstar."""
+        return self._steer_prmstar("di", (rho, r), goal_kind, goal_params, init_idx, checkpts)
+
+    def car_prmstar(self, car, turn_radius, speed, r, goal_kind, goal_params, init_idx=1, checkpts=True):
+        """dubins / reedsshepp PRM* (mpfmt_dubins_prmstar, mpfmt_reedsshepp_prmstar); the dict of prmstar."""
+        return self._steer_prmstar(car, (turn_radius, speed, r), goal_kind, goal_params, init_idx, checkpts)
 
     def car_fmtstar_wavefront(self, car, turn_radius, speed, r, goal_kind, goal_params, band=0.0, single=False, init_idx=1, checkpts=True):
         """dubins / reedsshepp planner with the recursion on the device."""

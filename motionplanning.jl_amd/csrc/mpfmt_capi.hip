@@ -1386,10 +1386,17 @@ int32_t mpfmt_knn_fmtstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t c
 
 // ---- PRM* roadmap queries: shortest paths over the resident free-edge graph (kernels_sssp.hip) -------------------------------------------
 
-// the checks every roadmap query starts with; nothing in the ctx has been touched when one of them refuses
+// the checks every field over the resident graph starts with -- r-disc, k-nearest or a filled and swept steering graph (the same device
+// slots and the same direction convention); nothing in the ctx has been touched when one of them refuses
 static int32_t sssp_ready(mpfmt_ctx* ctx)
 {
     if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "roadmap queries run on an unsharded ctx");
+    if (ctx->Xo && ctx->steer_filled) {
+        if (!ctx->steer_swept || !ctx->graph_free)                  // (as for the Euclidean mask; only checkpts asks for an obstacle set)
+            return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no free-edge mask for the resident steering graph and the current obstacle set (sweep it: "
+                                                    "mpfmt_di_graph_edges_free, mpfmt_dubins_graph_edges_free, mpfmt_reedsshepp_graph_edges_free)");
+        return MPFMT_OK;
+    }
     if (!ctx->Xo || !ctx->graph_filled) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no resident r-disc or k-nearest graph (mpfmt_graph_step_device, mpfmt_knn_count)");
     if (!ctx->graph_swept || !ctx->graph_free)
         return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no free-edge mask for the resident graph and the current obstacle set (sweep it: mpfmt_graph_step_device, "
@@ -1397,12 +1404,35 @@ static int32_t sssp_ready(mpfmt_ctx* ctx)
     return MPFMT_OK;
 }
 
-// the checkpts bitmap of the current samples and obstacle set into ctx->sssp_F
+// what the tracked fields and the external-state queries ask: a Euclidean graph (the steering delta kernels flag no dirty columns for a
+// tracked field, and an external state would need a steer to a non-sample)
+static int32_t sssp_ready_euclid(mpfmt_ctx* ctx)
+{
+    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "roadmap queries run on an unsharded ctx");
+    if (ctx->Xo && ctx->steer_filled)
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, "tracked fields and external states: Euclidean graphs only (the resident graph is a steering graph)");
+    return sssp_ready(ctx);
+}
+
+static int32_t steer_point_bitmap(mpfmt_ctx* ctx);      // (with the steering planners' prelude, below)
+
+// the Euclidean checkpts bitmap of the current samples and obstacle set into ctx->sssp_F
 static int32_t sssp_point_bitmap(mpfmt_ctx* ctx)
 {
     int32_t rc;
     if ((rc = ctx->sssp_F.ensure(ctx, sizeof(uint64_t) * (size_t)((ctx->N + 63) / 64)))) return rc;
     return mpfmt_launch_points_free(ctx, nullptr, ctx->N, ctx->sssp_F);
+}
+
+// the checkpts bitmap of a field over the RESIDENT graph, for the entry points that sssp_ready has just admitted: what is resident is a
+// steering graph (the bitmap of the steering planners) or a Euclidean one.  Planners that build a graph of their own do not come here: a
+// steering graph left in the ctx says nothing about the graph they are about to build.
+static int32_t sssp_resident_bitmap(mpfmt_ctx* ctx)
+{
+    if (!ctx->steer_filled) return sssp_point_bitmap(ctx);
+    int32_t rc;
+    if ((rc = ctx->sssp_F.ensure(ctx, sizeof(uint64_t) * (size_t)((ctx->N + 63) / 64)))) return rc;
+    return steer_point_bitmap(ctx);
 }
 
 int32_t mpfmt_graph_sssp(mpfmt_ctx* ctx, const int64_t* sources, int64_t nsrc, int32_t checkpts, double* C, int64_t* A, mpfmt_sssp_info* info)
@@ -1415,7 +1445,7 @@ int32_t mpfmt_graph_sssp(mpfmt_ctx* ctx, const int64_t* sources, int64_t nsrc, i
     if (checkpts && !ctx->have_boxes && ctx->cc_kind == 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "checkpts needs an obstacle set");
     if ((rc = check_idx(ctx, sources, nsrc, "sources"))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (checkpts && nsrc > 0 && (rc = sssp_point_bitmap(ctx))) return rc;
+    if (checkpts && nsrc > 0 && (rc = sssp_resident_bitmap(ctx))) return rc;
     const int64_t N = ctx->N;
     for (int64_t q = 0; q < nsrc; ++q)
         if ((rc = mpfmt_sssp_device(ctx, sources[q] - 1, checkpts ? ctx->sssp_F : nullptr, C + q * N, A ? A + q * N : nullptr, info ? info + q : nullptr)))
@@ -1435,8 +1465,23 @@ int32_t mpfmt_graph_sssp_multi(mpfmt_ctx* ctx, const int64_t* sources, int64_t n
     if ((rc = check_idx(ctx, sources, nsrc, "sources"))) return rc;
     if (nsrc == 0) return MPFMT_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (checkpts && (rc = sssp_point_bitmap(ctx))) return rc;
+    if (checkpts && (rc = sssp_resident_bitmap(ctx))) return rc;
     return mpfmt_sssp_multi_device(ctx, sources, nsrc, checkpts ? ctx->sssp_F.get() : nullptr, C, A, info);
+}
+
+// the cost-to-go field of a target set over whatever swept graph is resident (kernels_sssp_to.hip)
+int32_t mpfmt_graph_sssp_to(mpfmt_ctx* ctx, const int64_t* targets, int64_t ntgt, int32_t checkpts, double* G, int64_t* S, mpfmt_sssp_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (ntgt < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "ntgt < 0");
+    if (!G || (ntgt > 0 && !targets)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "targets / G is NULL");
+    int32_t rc;
+    if ((rc = sssp_ready(ctx))) return rc;
+    if (checkpts && !ctx->have_boxes && ctx->cc_kind == 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "checkpts needs an obstacle set");
+    if ((rc = check_idx(ctx, targets, ntgt, "targets"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (checkpts && (rc = sssp_resident_bitmap(ctx))) return rc;
+    return mpfmt_sssp_to_device(ctx, targets, ntgt, checkpts ? ctx->sssp_F.get() : nullptr, G, S, info);
 }
 
 // ---- a tracked field: kept valid across in-place box edits (kernels_field.hip) -----------------------------------------------------------
@@ -1445,7 +1490,7 @@ int32_t mpfmt_field_begin(mpfmt_ctx* ctx, int64_t source, int32_t checkpts, mpfm
 {
     if (!ctx) return MPFMT_ERR_ARG;
     int32_t rc;
-    if ((rc = sssp_ready(ctx))) return rc;
+    if ((rc = sssp_ready_euclid(ctx))) return rc;
     if (checkpts && !ctx->have_boxes && ctx->cc_kind == 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "checkpts needs an obstacle set");
     if ((rc = check_idx(ctx, &source, 1, "source"))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1458,7 +1503,7 @@ int32_t mpfmt_field_update(mpfmt_ctx* ctx, mpfmt_field_info* info)
     if (!ctx) return MPFMT_ERR_ARG;
     if (!mpfmt_field_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked field (mpfmt_field_begin)");
     int32_t rc;
-    if ((rc = sssp_ready(ctx))) return rc;
+    if ((rc = sssp_ready_euclid(ctx))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const bool history = mpfmt_field_history(ctx);                       // no build and no whole sweep since the field was last valid
     if (history && !ctx->fld_dirty_any) {                                 // nothing was flagged: the field stands
@@ -1496,6 +1541,8 @@ int32_t mpfmt_field_goal(mpfmt_ctx* ctx, int32_t goal_kind, const double* goal_p
     if (!ctx) return MPFMT_ERR_ARG;
     if (!path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
     if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
+    if (ctx->Xo && ctx->steer_filled)
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, "tracked fields and external states: Euclidean graphs only (the resident graph is a steering graph)");
     if (!mpfmt_field_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked field (mpfmt_field_begin)");
     if (ctx->fld_dirty_any || !mpfmt_field_history(ctx) || !ctx->graph_swept)
         return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the box set was edited since the tracked field was last valid (mpfmt_field_update)");
@@ -1551,12 +1598,14 @@ static int32_t roadmap_ready(mpfmt_ctx* ctx)
 {
     // (what the ctx IS comes before what it has ready: a wrong checker or workspace is named as such, not as the stale mask its upload left)
     if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "roadmap queries run on an unsharded ctx");
+    if (ctx->Xo && ctx->steer_filled)
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, "tracked fields and external states: Euclidean graphs only (the resident graph is a steering graph)");
     if (ctx->knn_k > 0 && ctx->graph_filled) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "external states attach to an r-disc graph: the resident graph is a k-nearest one");
     if (ctx->cc_kind != 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "external states need the N-D box checker (the 2-D SAT world is resident)");
     if (ctx->have_boxes && ctx->Xo && ctx->dw != ctx->d)
         return mpfmt_fail(ctx, MPFMT_ERR_STATE, "external states need an identity workspace (dw = %d, d = %d)", ctx->dw, ctx->d);
     int32_t rc;
-    if ((rc = sssp_ready(ctx))) return rc;
+    if ((rc = sssp_ready_euclid(ctx))) return rc;
     if (!(ctx->graph_r >= 0.0)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no resident r-disc graph");
     if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
     return MPFMT_OK;
@@ -1855,7 +1904,7 @@ static int32_t prmstar_impl(mpfmt_ctx* ctx, double r, int64_t k, int64_t init_id
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     t[3] = now();
-    if ((rc = sssp_ready(ctx))) return rc;
+    if ((rc = sssp_ready_euclid(ctx))) return rc;
     t[4] = now();
     mpfmt_sssp_info inf;
     if ((rc = mpfmt_sssp_device(ctx, init_idx - 1, checkpts ? ctx->sssp_F : nullptr, C, A, &inf))) return rc;
@@ -1922,6 +1971,49 @@ static steer_space steer_space_of(const mpfmt_ctx* ctx, mpfmt_steer kind)
     return {kind, 3, 2, kind == MPFMT_STEER_REEDSSHEPP};
 }
 
+// is_free_state of every sample of a steering space: the states on the host (X) and the bitmap F.  Shared by the planners' prelude and
+// by the checkpts bitmap of the fields over a resident steering graph (steer_point_bitmap).
+static int32_t steer_state_bitmap(mpfmt_ctx* ctx, const steer_space& s, std::vector<double>& X, std::vector<uint64_t>& F)
+{
+    const int64_t N = ctx->N;
+    int32_t rc;
+    std::vector<double> P;
+    if ((rc = mpfmt_states_host(ctx, s.dw, X, P))) return rc;
+    F.assign((size_t)(N + 63) / 64, 0);
+    const mpfmt_ss keep = ctx->ss;
+    ctx->ss.has = 0;
+    rc = mpfmt_states_free(ctx, P.data(), N, F.data());
+    ctx->ss = keep;
+    if (rc) return rc;
+    if (keep.has)
+        for (int64_t i = 0; i < N; ++i) {
+            const double* v = &X[(size_t)i * s.d];
+            bool ok = true;
+            for (int q = 0; q < s.d; ++q) ok = ok && (keep.lo[q] <= v[q]) && (v[q] <= keep.hi[q]);
+            if (!ok) F[i >> 6] &= ~(1ull << (i & 63));
+        }
+    return MPFMT_OK;
+}
+
+// that bitmap for the resident steering graph, left on the device in ctx->sssp_F (allocated by the caller)
+static int32_t steer_upload_bitmap(mpfmt_ctx* ctx, const std::vector<uint64_t>& F)
+{
+    HIPCHK(ctx, hipMemcpyAsync(ctx->sssp_F, F.data(), sizeof(uint64_t) * F.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return MPFMT_OK;
+}
+
+static int32_t steer_point_bitmap(mpfmt_ctx* ctx)
+{
+    const steer_space s = steer_space_of(ctx, ctx->steer_kind);
+    if (ctx->dw != s.dw) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "workspace dim %d does not fit the resident steering graph (%d)", ctx->dw, s.dw);
+    std::vector<double> X;
+    std::vector<uint64_t> F;
+    int32_t rc;
+    if ((rc = steer_state_bitmap(ctx, s, X, F))) return rc;
+    return steer_upload_bitmap(ctx, F);
+}
+
 // The planners' common prelude: the checks of the ctx against the space, then the states on the host (X) and the checkpts bitmap F,
 // is_free_state(v, CC, SS) = in_state_space(v) && point-vs-obstacles on the workspace coordinates.  The point test runs on the
 // workspace points with the state-space bounds (which have the states' dimension) switched off; they are applied here.
@@ -1943,21 +2035,7 @@ static int32_t steer_prelude(mpfmt_ctx* ctx, const steer_space& s, double rho, d
     if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
     if (ctx->dw != s.dw) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "workspace dim %d != state dim / 2 = %d", ctx->dw, s.dw);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    std::vector<double> P;
-    if ((rc = mpfmt_states_host(ctx, s.dw, X, P))) return rc;
-    F.assign((size_t)(N + 63) / 64, 0);
-    const mpfmt_ss keep = ctx->ss;
-    ctx->ss.has = 0;
-    rc = mpfmt_states_free(ctx, P.data(), N, F.data());
-    ctx->ss = keep;
-    if (rc) return rc;
-    if (keep.has)
-        for (int64_t i = 0; i < N; ++i) {
-            const double* v = &X[(size_t)i * s.d];
-            bool ok = true;
-            for (int q = 0; q < s.d; ++q) ok = ok && (keep.lo[q] <= v[q]) && (v[q] <= keep.hi[q]);
-            if (!ok) F[i >> 6] &= ~(1ull << (i & 63));
-        }
+    if ((rc = steer_state_bitmap(ctx, s, X, F))) return rc;
     if (!bit(F, init_idx - 1)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
     return MPFMT_OK;
 }
@@ -2063,6 +2141,87 @@ static int32_t steer_fmtstar_wavefront(mpfmt_ctx* ctx, mpfmt_steer kind, double 
     mpfmt_wf_info_now(ctx, info);
     return MPFMT_OK;
 }
+
+// PRM* in a steering space: the prelude, the graph and the sweep exactly as steer_fmtstar_wavefront takes them (a resident graph of the
+// same space and parameters is reused, and its sweep while it is valid), then the cost-to-come field from init_idx over the resident
+// graph (kernels_sssp.hip) and the goal extraction of prmstar_impl with the goal predicate of steer_fmtstar.
+static int32_t steer_prmstar(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b, double r, int64_t init_idx, int32_t checkpts,
+                             int32_t goal_kind, const double* goal_params, int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!A || !C || !path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
+    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "prmstar runs on an unsharded ctx");
+    memset(res, 0, sizeof *res);
+    res->cost = INFINITY;
+    const steer_space s = steer_space_of(ctx, kind);
+    std::vector<double> X;
+    std::vector<uint64_t> F;
+    int32_t rc;
+    stamp t[6];
+    t[0] = now();
+    if ((rc = steer_prelude(ctx, s, a, r, init_idx, goal_kind, X, F))) return rc;
+    t[1] = now();
+    const bool resident = ctx->steer_filled && ctx->steer_kind == kind && ctx->steer_r == r &&
+                          (kind == MPFMT_STEER_DI ? ctx->di_rho == a : (ctx->car_rt == a && ctx->car_sp == b));
+    if (!resident && (rc = steer_build(ctx, kind, a, b, r))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    t[2] = now();
+    if (!ctx->steer_swept && (rc = steer_sweep(ctx, kind))) return rc;       // (a graph just built is not swept yet)
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    t[3] = now();
+    if ((rc = sssp_ready(ctx))) return rc;
+    if (checkpts) {
+        if ((rc = ctx->sssp_F.ensure(ctx, sizeof(uint64_t) * F.size()))) return rc;
+        if ((rc = steer_upload_bitmap(ctx, F))) return rc;
+    }
+    t[4] = now();
+    const int64_t N = ctx->N;
+    mpfmt_sssp_info inf;
+    if ((rc = mpfmt_sssp_device(ctx, init_idx - 1, checkpts ? ctx->sssp_F.get() : nullptr, C, A, &inf))) return rc;
+    auto goal_hit = [&](int64_t z) {
+        const double* v = &X[(size_t)z * s.d];
+        if (goal_kind == MPFMT_GOAL_POINT) {                          // StateGoal: exact state equality (goals.jl:128-131)
+            for (int q = 0; q < s.d; ++q) if (!(v[q] == goal_params[q])) return false;
+            return true;
+        }
+        return mpfmt_is_goal_pt(v, s.dw, goal_kind, goal_params);      // workspace goals act on the first dw coordinates
+    };
+    // goal node: the reached sample inside the goal region of lowest (C, index)
+    int64_t z = -1;
+    for (int64_t i = 0; i < N; ++i)
+        if (C[i] < INFINITY && (z < 0 || C[i] < C[z]) && goal_hit(i)) z = i;
+    std::vector<int64_t> rev;
+    if (z >= 0) {
+        int64_t cur = z;
+        rev.push_back(cur + 1);
+        while (cur != init_idx - 1 && (int64_t)rev.size() <= N) {
+            const int64_t p = A[cur];
+            if (p == 0) break;
+            cur = p - 1;
+            rev.push_back(cur + 1);
+        }
+        res->status = 1; res->cost = C[z]; res->z = z + 1;
+    } else {
+        rev.push_back(init_idx);
+        res->status = 0; res->cost = INFINITY; res->z = init_idx;
+    }
+    for (size_t i = 0; i < rev.size() && i < (size_t)N; ++i) path[i] = rev[rev.size() - 1 - i];
+    res->path_len = (int64_t)std::min<size_t>(rev.size(), (size_t)N);
+    res->collision_checks = 0;
+    t[5] = now();
+    fmt_times(ctx, res, t);
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_di_prmstar(mpfmt_ctx* ctx, double rho, double r, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                         int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{ return steer_prmstar(ctx, MPFMT_STEER_DI, rho, 0.0, r, init_idx, checkpts, goal_kind, goal_params, A, C, path, res); }
+int32_t mpfmt_dubins_prmstar(mpfmt_ctx* ctx, double turn_radius, double speed, double r, int64_t init_idx, int32_t checkpts, int32_t goal_kind,
+                             const double* goal_params, int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{ return steer_prmstar(ctx, MPFMT_STEER_DUBINS, turn_radius, speed, r, init_idx, checkpts, goal_kind, goal_params, A, C, path, res); }
+int32_t mpfmt_reedsshepp_prmstar(mpfmt_ctx* ctx, double turn_radius, double speed, double r, int64_t init_idx, int32_t checkpts, int32_t goal_kind,
+                                 const double* goal_params, int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{ return steer_prmstar(ctx, MPFMT_STEER_REEDSSHEPP, turn_radius, speed, r, init_idx, checkpts, goal_kind, goal_params, A, C, path, res); }
 
 // the graph accessors: (a, b) as for steer_build; tval (the double integrator's optimal times) may be NULL
 static int32_t steer_graph_count(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b, double r, int64_t* colptr, int64_t* nnz)
@@ -2411,6 +2570,9 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "sssp_rounds") == 0) { *value = ctx->sssp_rounds; return MPFMT_OK; }
     if (strcmp(name, "sssp_relaxations") == 0) { *value = ctx->sssp_relax; return MPFMT_OK; }
     if (strcmp(name, "sssp_reached") == 0) { *value = ctx->sssp_reached; return MPFMT_OK; }
+    if (strcmp(name, "sssp_to_columns") == 0) { *value = ctx->sssp_to_columns; return MPFMT_OK; }
+    if (strcmp(name, "sssp_to_entries_read") == 0) { *value = ctx->sssp_to_entries; return MPFMT_OK; }
+    if (strcmp(name, "sssp_to_atomics") == 0) { *value = ctx->sssp_to_atomics; return MPFMT_OK; }
     if (strcmp(name, "sssp_multi_groups") == 0) { *value = ctx->ms_groups; return MPFMT_OK; }
     if (strcmp(name, "sssp_multi_rounds") == 0) { *value = ctx->ms_rounds; return MPFMT_OK; }
     if (strcmp(name, "sssp_multi_rows_read") == 0) { *value = ctx->ms_rows; return MPFMT_OK; }

@@ -343,6 +343,58 @@ int32_t mpfmt_host_graph_sssp(int64_t N, const int64_t* colptr, const int32_t* r
     return MPFMT_OK;
 }
 
+// PRM* cost-to-go field of a target set (include/mpfmt.h, "cost-to-go"): a binary-heap Dijkstra over the REVERSED edges.  Entry b of
+// column x with row y is the edge y -> x; a settled x offers fl(G[x] + w) to the rows of its own column, so the reversed graph IS the
+// CSC and the scan reads the columns in place (usable: free bit set, F[x] set; no exemption).  The values are the least fixed point of
+// G[y] = min(G0[y], min_x fl(G[x] + w_yx)), the one the device's push reaches (csrc/kernels_sssp_to.hip).  Successors come from a
+// final pass over the finished G: per reached non-target y the usable x of lowest (G[x], x) with fl(G[x] + w) == G[y]; the pass walks
+// the columns, so the candidates of a y arrive in no particular order and the minimum is kept per y.
+int32_t mpfmt_host_graph_sssp_to(int64_t N, const int64_t* colptr, const int32_t* rowval, const double* nzval, const uint64_t* efree,
+                                 const uint64_t* F, const int64_t* targets, int64_t ntgt, double* G, int64_t* S)
+{
+    if (!colptr || !efree || !G || N < 1 || ntgt < 0 || (ntgt > 0 && !targets)) return MPFMT_ERR_ARG;
+    if (colptr[0] != 0) return MPFMT_ERR_ARG;
+    for (int64_t j = 0; j < N; ++j) if (colptr[j + 1] < colptr[j]) return MPFMT_ERR_ARG;
+    const int64_t nnz = colptr[N];
+    if (nnz > 0 && (!rowval || !nzval)) return MPFMT_ERR_ARG;
+    for (int64_t e = 0; e < nnz; ++e) if (rowval[e] < 0 || rowval[e] >= N || !(nzval[e] >= 0.0)) return MPFMT_ERR_ARG;
+    for (int64_t q = 0; q < ntgt; ++q) if (targets[q] < 1 || targets[q] > N) return MPFMT_ERR_ARG;
+    auto bitp = [](const uint64_t* m, int64_t i) { return (m[i >> 6] >> (i & 63)) & 1ull; };
+    std::vector<uint8_t> is_tgt((size_t)N, 0);
+    for (int64_t i = 0; i < N; ++i) G[i] = INFINITY;
+    Heap heap;
+    for (int64_t q = 0; q < ntgt; ++q) {
+        const int64_t t = targets[q] - 1;
+        if (!is_tgt[t]) { is_tgt[t] = 1; G[t] = 0.0; heap.push(t, 0.0); }
+    }
+    while (!heap.empty()) {
+        const double gx = heap.pri[0];
+        const int64_t x = heap.pop();
+        if (gx > G[x]) continue;                                               // a stale entry: x was settled at a lower label
+        if (F && !bitp(F, x)) continue;                                        // no usable edge into x
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b) {
+            if (!bitp(efree, b)) continue;
+            const int64_t y = rowval[b];
+            const double c = gx + nzval[b];
+            if (c < G[y]) { G[y] = c; heap.push(y, c); }
+        }
+    }
+    if (!S) return MPFMT_OK;
+    std::vector<double> best((size_t)N, INFINITY);
+    for (int64_t i = 0; i < N; ++i) S[i] = 0;
+    for (int64_t x = 0; x < N; ++x) {
+        const double gx = G[x];
+        if (!(gx < INFINITY) || (F && !bitp(F, x))) continue;
+        for (int64_t b = colptr[x]; b < colptr[x + 1]; ++b) {
+            if (!bitp(efree, b)) continue;
+            const int64_t y = rowval[b];
+            if (is_tgt[y] || !(gx + nzval[b] == G[y])) continue;
+            if (S[y] == 0 || gx < best[y]) { S[y] = x + 1; best[y] = gx; }     // (x ascends: an equal G[x] keeps the lower index)
+        }
+    }
+    return MPFMT_OK;
+}
+
 // The repair of a tracked field on the host (include/mpfmt.h, "a cost-to-come field kept valid across box edits"): steps 2-4 over the
 // device-native arrays.  C / A hold the old field; efree / F are the new mask and point bitmap; dirty marks the columns the edits
 // flagged.  I0 is tested on the dirty columns through the parent's entry (rows are distinct inside a column: the entry of A[x] is the

@@ -405,6 +405,12 @@ struct mpfmt_ctx {
     mpfmt_dbuf<uint64_t> sssp_F;          // [ceil(N/64)] checkpts bitmap of the call
     hipEvent_t sssp_ev[2] = {nullptr, nullptr};
     int64_t sssp_rounds = 0, sssp_relax = 0, sssp_reached = 0;      // stats of the last source
+    // cost-to-go (kernels_sssp_to.hip): G and S live in sssp_C / sssp_A, the ring in sssp_bm (+ a fourth bitmap: the targets)
+    mpfmt_dbuf<unsigned long long> sssp_to_best;      // [N] successor pass 1: lowest bits(G[x]) among the exact achievers of y
+    mpfmt_dbuf<int64_t> sssp_to_tgt;      // [ntgt] 1-based targets of the call
+    mpfmt_dbuf<void> sssp_to_state;       // sssp_to_state (device) and its pinned host mirror
+    mpfmt_hbuf<void> sssp_to_state_host;
+    int64_t sssp_to_atomics = 0, sssp_to_entries = 0, sssp_to_columns = 0;      // stats of the last cost-to-go field
 
     // ---- adaptive shortcutting (kernels_shortcut.hip): stats of the last batch ----
     int64_t shortcut_tests = 0, shortcut_checks = 0;
@@ -589,6 +595,10 @@ void mpfmt_wf_info_now(mpfmt_ctx* ctx, mpfmt_wf_info* info);
 // nullptr) receive the field; the labels and parents also stay in ctx->sssp_C / sssp_A
 int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, double* C_host, int64_t* A_host, mpfmt_sssp_info* info);
 void mpfmt_sssp_free(mpfmt_ctx* ctx);
+// kernels_sssp_to.hip: the cost-to-go field of a target set (1-based, on the host, validated) over the resident graph and mask; G_host [N],
+// S_host [N] or nullptr (no successor passes); labels and successors also stay in ctx->sssp_C / sssp_A
+int32_t mpfmt_sssp_to_device(mpfmt_ctx* ctx, const int64_t* targets1, int64_t ntgt, const uint64_t* d_F, double* G_host, int64_t* S_host,
+                             mpfmt_sssp_info* info);
 // kernels_field.hip: the tracked field.  d_F: the point bitmap of the current obstacle set or nullptr (checkpts = false)
 int32_t mpfmt_field_compute(mpfmt_ctx* ctx, int64_t source0, int32_t checkpts, const uint64_t* d_F, mpfmt_field_info* info);   // whole field into the tracked buffers
 int32_t mpfmt_field_repair(mpfmt_ctx* ctx, const uint64_t* d_F, mpfmt_field_info* info);                                       // steps 2-4 on the tracked buffers

@@ -618,7 +618,9 @@ def prmstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_i
     rule (fmt.jl:38-41) and connection types as fmtstar_.  The whole r-disc (connections = "R") or k-nearest ("K") graph and its
     free-edge mask are built on the device, then the EXACT cost-to-come of every sample from init over the free-edge graph
     (mpfmt_prmstar / mpfmt_knn_prmstar); the answer is the goal sample of lowest cost.  Fills P.solution like fmtstar_, with
-    metadata["planner"] = "prmstar" and metadata["cost_to_come"] = the field (inf = unreachable).  Euclidean state spaces.
+    metadata["planner"] = "prmstar" and metadata["cost_to_come"] = the field (inf = unreachable).  In LinearQuadratic, DubinsExact
+    and ReedsSheppExact spaces the steering graph of the space takes the r-disc graph's place (mpfmt_di_prmstar, mpfmt_dubins_prmstar,
+    mpfmt_reedsshepp_prmstar), with fmtstar_'s radius rule and goal mapping; connections = "K" and keep_field = True are Euclidean only.
     keep_field = True: the context keeps the field of init_idx (Context.field_begin), so that after addobstacle_ / addblocker_ /
     removeobstacle_ a replan_(P) repairs it instead of computing it again."""
     t0 = time.time()
@@ -626,11 +628,16 @@ def prmstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_i
     P.CC.count = 0
     if connections not in ("R", "K"):
         raise ValueError("Connection type must be radial (:R) or k-nearest (:K)")
-    if isinstance(P.SS.dist, (LinearQuadratic, DubinsExact, ReedsSheppExact)):
-        raise ValueError("prmstar_ is built for Euclidean state spaces only (not the double integrator or the cars)")
+    steering = isinstance(P.SS.dist, (LinearQuadratic, DubinsExact, ReedsSheppExact))
+    if steering and connections == "K":
+        raise ValueError("connections = :K is built for Euclidean state spaces only (not the double integrator or the cars)")
+    if steering and keep_field:
+        raise ValueError("keep_field = True is built for Euclidean state spaces only (tracked fields need a Euclidean graph)")
     r_given = r
     if connections == "K":
         k = default_k(rm, dim(P.SS), N) if k is None else int(k)
+    if steering and r > 0:
+        setup_steering(P.SS, r)
     if not is_free_state(P.init, P.CC, P.SS, P.ctx):
         warnings.warn("Initial state is infeasible!")
         P.status = "failed"
@@ -640,11 +647,20 @@ def prmstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_i
     if r == 0 and connections == "R":
         d = dim(P.SS)
         r = rm * 2 * (1 / d * free_volume_ub / (math.pi ** (d / 2) / math.gamma(d / 2 + 1)) * math.log(N) / N) ** (1 / d)
+        if steering:
+            setup_steering(P.SS, r)
     ctx = P.ctx
     P.CC._bind(ctx, P.SS)
     gkind, gpar = P.goal.kind, P.goal.params()
+    if isinstance(P.SS.dist, (DubinsExact, ReedsSheppExact)) and gkind == _lib.GOAL_POINT and len(gpar) == SS_WS(P.SS):
+        gkind, gpar = _lib.GOAL_BALL, np.concatenate([gpar, [0.0]])       # (PointGoal is a workspace goal: fmtstar_)
     if connections == "K":
         res = ctx.knn_prmstar(k, gkind, gpar, init_idx=init_idx, checkpts=checkpts)
+    elif isinstance(P.SS.dist, LinearQuadratic):
+        res = ctx.di_prmstar(P.SS.dist.rho, r, gkind, gpar, init_idx=init_idx, checkpts=checkpts)
+    elif steering:
+        car = "dubins" if isinstance(P.SS.dist, DubinsExact) else "reedsshepp"
+        res = ctx.car_prmstar(car, P.SS.dist.r, P.SS.dist.s, r, gkind, gpar, init_idx=init_idx, checkpts=checkpts)
     else:
         res = ctx.prmstar(r, gkind, gpar, init_idx=init_idx, checkpts=checkpts)
     P.status = "solved" if res["status"] == 1 else "failed"
@@ -722,6 +738,56 @@ def roadmap_matrix_(P, starts, goals, checkpts=True):
     cost, status, info = P.ctx.roadmap_matrix(S, G, checkpts=checkpts)
     P.solution.metadata["roadmap_matrix_info"] = info
     return cost, status
+
+
+def _goal_members(P):
+    """The 1-based samples inside P.goal: a goal of k coordinates acts on the first k coordinates of a state (the workspace goals of the
+    steering spaces; the whole state where k = d); PointGoal is exact equality."""
+    V = np.asarray(P.V.V, dtype=np.float64)
+    g = P.goal
+    if g.kind == _lib.GOAL_RECT:
+        k = len(g.lo)
+        inside = np.all((g.lo <= V[:, :k]) & (V[:, :k] <= g.hi), axis=1)
+    elif g.kind == _lib.GOAL_BALL:
+        k = len(g.center)
+        inside = np.sqrt(np.sum((V[:, :k] - g.center) ** 2, axis=1)) <= g.radius
+    else:
+        k = len(g.pt)
+        inside = np.all(V[:, :k] == g.pt, axis=1)
+    return np.flatnonzero(inside).astype(np.int64) + 1
+
+
+def cost_to_go_(P, checkpts=True):
+    """The feedback policy over the roadmap a prmstar_ / fmtstar_(band = ...) call left resident in P.ctx, in any space: from every
+    sample the optimal cost to the samples inside P.goal and the next sample on the way (mpfmt_graph_sssp_to).  On the directed
+    graphs (double integrator, Dubins, k-nearest) this is not the cost-to-come of a goal sample.  Returns (G, S): G = inf where the goal
+    cannot be reached, 0 on the goal samples; S 1-based successors (0 = goal sample or unreached).  Stores metadata["cost_to_go"] and
+    metadata["successor"]."""
+    if P.solution is None or P.ctx is None:
+        raise RuntimeError("cost_to_go_ needs the roadmap of a prmstar_ / fmtstar_ call")
+    P.CC._bind(P.ctx, P.SS)
+    out = P.ctx.graph_sssp_to(_goal_members(P), checkpts=checkpts)
+    P.solution.metadata["cost_to_go"] = out["G"]
+    P.solution.metadata["successor"] = out["S"]
+    P.solution.metadata["cost_to_go_info"] = out["info"]
+    return out["G"], out["S"]
+
+
+def successor_paths(S, nodes):
+    """The counterpart of tree_paths for a successor array S (metadata["successor"]: S[i - 1] = the next sample after i, 0 = none): the
+    paths node -> ... -> target (1-based), each ending at the first sample without a successor.  A node with S = 0 raises: it is a
+    target, which needs no path, or a sample that reaches none (metadata["cost_to_go"] tells them apart)."""
+    out = []
+    for v in nodes:
+        p = [int(v)]
+        if int(S[p[-1] - 1]) == 0:
+            raise ValueError("sample %d has no successor: it is a target or does not reach one" % int(v))
+        while int(S[p[-1] - 1]) != 0:
+            if len(p) > len(S):
+                raise ValueError("the successors of sample %d do not arrive at a target" % int(v))
+            p.append(int(S[p[-1] - 1]))
+        out.append(np.array(p, dtype=np.int64))
+    return out
 
 
 # ---- post-processing (src/postprocessors.jl) ---------------------------------------------------------------------------------------
