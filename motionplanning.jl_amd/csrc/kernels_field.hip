@@ -7,11 +7,10 @@
 //              clear; their labels become +Inf and their bits enter the round-0 candidates (k_field_i0).  The closure over the
 //              descendants is "a sample whose parent's label is +Inf takes +Inf" until a pass changes nothing (k_field_close, lane per
 //              sample, N-sized; an unreached sample has no children, so +Inf IS the mark); the host reads the pass counters once per
-//              FIELD_BATCH passes and a pass whose predecessor changed nothing returns at once;
+//              RELAX_BATCH passes and a pass whose predecessor changed nothing returns at once;
 //   relax      k_field_relax: one wavefront per column, lanes over entries, the fold and the aligned 8-byte label loads and stores of
 //              k_sssp_relax, and its cost band (a column with C[x] <= mlow = the lowest label written in the round before cannot
-//              improve).  One ring of three bitmaps drives it, read as in kernels_sssp.hip (round t reads slot t % 3, marks
-//              (t + 1) % 3, clears (t + 2) % 3):
+//              improve).  One ring of three bitmaps drives it, the ring of relax_core.h:
 //                round 0      the slot holds the candidates I u D; a candidate looks at all its usable rows with finite labels, mlow = 0;
 //                symmetric    (the library's own r-disc build: the rows of a column are its out-neighbours) a column that lowers its
 //                             label marks its ROWS: the slot holds the next round's candidates and only they are read;
@@ -19,31 +18,20 @@
 //                             k_sssp_relax: every column is a candidate and looks at the rows of the slot.  Nothing rests on a symmetry
 //                             the library does not guarantee;
 //              while the rounds run, the dirty bitmap's storage holds the set of columns read so far (the stat counts them once);
-//   parents    k_field_parents: k_sssp_parents over the finished labels, which also writes Ab and counts the reached samples.
+//   parents    k_field_parents: the parent pass of k_sssp_parents (parents_body of relax_core.h) over the finished labels, which also
+//              writes Ab and counts the reached samples.
 //
 // Why the band holds without a row filter (symmetric mode): a label written in round t >= 1 is fl(C[y] + w) for a row y of a candidate
 // x.  If y has not changed since x last looked at it, x holds min(..., fl(C[y] + w)) already.  If it has, it changed in round t - 1 or
 // in round t itself, and by induction over the writes every such label is >= mlow(t); so the value is >= mlow(t) and a column at or
 // below mlow(t) cannot improve.
-#include "mpfmt_internal.h"
-#include <cmath>
-#include <algorithm>
+#include "relax_core.h"
 
-#define FIELD_BATCH 8                        // rounds / closure passes issued between two reads of the state
-#define FIELD_INF_BITS 0x7FF0000000000000ull
-
-struct field_slot { unsigned long long changed, minbits; };
 struct field_state {
-    field_slot slot[3];
-    unsigned long long close_changed[3];     // ring of the closure's pass counters
+    band_slot slot[3];
+    count_slot close[3];                     // ring of the closure's pass counters
     unsigned long long relax, rounds, reached, invalidated, dirty, distinct, visits, entries;
 };
-
-__device__ __forceinline__ double field_wave_min(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off));
-    return v;
-}
 
 // the flagged columns of a delta call into the dirty bitmap (words are shared between wavefronts: atomicOr)
 __global__ __launch_bounds__(256) void k_field_dirty(const int32_t* __restrict__ cols, int64_t n, int64_t N, unsigned long long* __restrict__ D)
@@ -58,10 +46,8 @@ __global__ __launch_bounds__(256) void k_field_dirty(const int32_t* __restrict__
 __global__ __launch_bounds__(256) void k_field_state_init(field_state* __restrict__ st)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        st->slot[0].changed = 0; st->slot[0].minbits = 0ull;                 // (mlow(0) = 0: every label is >= 0)
-        st->slot[1].changed = 0; st->slot[1].minbits = FIELD_INF_BITS;
-        st->slot[2].changed = 0; st->slot[2].minbits = FIELD_INF_BITS;
-        st->close_changed[0] = st->close_changed[1] = st->close_changed[2] = 0;
+        band_ring_init(st->slot, 0);
+        st->close[0].changed = st->close[1].changed = st->close[2].changed = 0;
         st->relax = st->rounds = st->reached = st->invalidated = st->dirty = st->distinct = st->visits = st->entries = 0;
     }
 }
@@ -87,21 +73,19 @@ __global__ __launch_bounds__(256) void k_field_i0(int64_t N, int64_t words, int6
     if (lane == 0) {
         ring[w] = dw | m; ring[words + w] = 0ull; ring[2 * words + w] = 0ull;
         if (dw) atomicAdd(&st->dirty, (unsigned long long)__popcll(dw));
-        if (m) { atomicAdd(&st->invalidated, (unsigned long long)__popcll(m)); atomicAdd(&st->close_changed[0], (unsigned long long)__popcll(m)); }
+        if (m) { atomicAdd(&st->invalidated, (unsigned long long)__popcll(m)); atomicAdd(&st->close[0].changed, (unsigned long long)__popcll(m)); }
     }
 }
 
-// one pass of the closure: a reached sample whose parent has lost its label loses its own.  Pass p reads close_changed[p % 3] (what
-// pass p - 1 did; I0 is pass -1), counts into [(p + 1) % 3] and clears [(p + 2) % 3].  Labels are read in place: a pass may see the
-// +Inf another lane wrote in the same pass, which only shortens the loop.
+// one pass of the closure: a reached sample whose parent has lost its label loses its own.  The pass counters are a ring of
+// relax_core.h (pass p reads what pass p - 1 did; I0 is pass -1).  Labels are read in place: a pass may see the +Inf another lane wrote
+// in the same pass, which only shortens the loop.
 __global__ __launch_bounds__(256) void k_field_close(int64_t N, int64_t src, int pass, double* C, const int64_t* __restrict__ A,
                                                      unsigned long long* ring0, field_state* st)
 {
-    const int s_in = pass % 3, s_out = (pass + 1) % 3, s_clr = (pass + 2) % 3;
-    const unsigned long long cin = st->close_changed[s_in];
+    const ring_idx r = ring_at(pass);
     const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (x == 0) st->close_changed[s_clr] = 0;
-    if (cin == 0) return;
+    if (ring_step(st->close, r, x) == 0) return;
     const int lane = threadIdx.x & 63;
     bool inv = false;
     if (x < N && x != src) {
@@ -112,7 +96,7 @@ __global__ __launch_bounds__(256) void k_field_close(int64_t N, int64_t src, int
     if (lane == 0 && m) {
         atomicOr(&ring0[x >> 6], m);
         atomicAdd(&st->invalidated, (unsigned long long)__popcll(m));
-        atomicAdd(&st->close_changed[s_out], (unsigned long long)__popcll(m));
+        atomicAdd(&st->close[r.out].changed, (unsigned long long)__popcll(m));
     }
 }
 
@@ -128,30 +112,23 @@ __global__ __launch_bounds__(256) void k_field_relax(int64_t N, int64_t words, i
                                                      const uint64_t* __restrict__ efree, const uint64_t* __restrict__ F, double* C,
                                                      uint64_t* ring, unsigned long long* seen, field_state* st)
 {
-    const int s_in = round % 3, s_out = (round + 1) % 3, s_clr = (round + 2) % 3;
-    const unsigned long long cin = st->slot[s_in].changed;
-    const double mlow = __longlong_as_double((long long)st->slot[s_in].minbits);
+    const ring_idx r = ring_at(round);
+    const double mlow = label_of_bits(st->slot[r.in].minbits);
     const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gtid == 0) {
-        st->slot[s_clr].changed = 0; st->slot[s_clr].minbits = FIELD_INF_BITS;
-        if (cin) st->rounds += 1;
-    }
-    if (cin == 0) return;
     const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
-    uint64_t* bclr = ring + (int64_t)s_clr * words;
-    for (int64_t w = gtid; w < words; w += nthreads) bclr[w] = 0ull;
-    const uint64_t* bin = ring + (int64_t)s_in * words;
-    unsigned long long* bout = (unsigned long long*)(ring + (int64_t)s_out * words);
+    const uint64_t* bin;
+    unsigned long long* bout;
+    if (!ring_round(st->slot, &st->rounds, ring, words, r, gtid, nthreads, bin, bout)) return;
     const bool by_column = sym || first;
     const int lane = threadIdx.x & 63;
     const int64_t nwaves = nthreads >> 6;
     unsigned long long nrel = 0, nchg = 0, nvis = 0, ndis = 0, nent = 0;
     double lmin = INFINITY;
     for (int64_t x = gtid >> 6; x < N; x += nwaves) {
-        if (by_column && !((bin[x >> 6] >> (x & 63)) & 1ull)) continue;
+        if (by_column && !bit_of(bin, x)) continue;
         const double cx = C[x];
         if (cx <= mlow) continue;                                             // (the source, C = 0, always: its exemption from F)
-        if (F && !((F[x >> 6] >> (x & 63)) & 1ull)) continue;
+        if (F && !bit_of(F, x)) continue;
         const int64_t b0 = colptr[x], b1 = colptr[x + 1];
         if (lane == 0) {
             const unsigned long long bit = 1ull << (x & 63);
@@ -159,18 +136,8 @@ __global__ __launch_bounds__(256) void k_field_relax(int64_t N, int64_t words, i
             ++nvis; nent += (unsigned long long)(b1 - b0);
             if (!(old & bit)) ++ndis;
         }
-        double best = INFINITY;
-        for (int64_t b = b0 + lane; b < b1; b += 64) {
-            const int32_t y = rowval[b];
-            if (!by_column && !((bin[y >> 6] >> (y & 63)) & 1ull)) continue;
-            if (!((efree[b >> 6] >> (b & 63)) & 1ull)) continue;
-            const double cy = C[y];
-            if (!(cy < INFINITY)) continue;
-            const double c = cy + nzval[b];
-            ++nrel;
-            best = fmin(best, c);
-        }
-        best = field_wave_min(best);
+        const double best = by_column ? column_fold<false, true>(b0, b1, lane, rowval, nzval, efree, bin, C, nrel)
+                                      : column_fold<true, true>(b0, b1, lane, rowval, nzval, efree, bin, C, nrel);
         if (best < cx) {
             if (lane == 0) {
                 C[x] = best;
@@ -185,14 +152,14 @@ __global__ __launch_bounds__(256) void k_field_relax(int64_t N, int64_t words, i
                 }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) nrel += __shfl_xor(nrel, off);
+    nrel = wave_sum(nrel);
     if (lane == 0) {
         if (nrel) atomicAdd(&st->relax, nrel);
         if (nvis) { atomicAdd(&st->visits, nvis); atomicAdd(&st->entries, nent); }
         if (ndis) atomicAdd(&st->distinct, ndis);
         if (nchg) {
-            atomicAdd(&st->slot[s_out].changed, nchg);
-            atomicMin(&st->slot[s_out].minbits, (unsigned long long)__double_as_longlong(lmin));      // (labels are >= 0: their bit patterns order like the values)
+            atomicAdd(&st->slot[r.out].changed, nchg);
+            atomicMin(&st->slot[r.out].minbits, label_bits(lmin));
         }
     }
 }
@@ -202,32 +169,7 @@ __global__ __launch_bounds__(256) void k_field_parents(int64_t N, int64_t src, c
                                                        const double* __restrict__ nzval, const uint64_t* __restrict__ efree,
                                                        const double* __restrict__ C, int64_t* __restrict__ A, int64_t* __restrict__ Ab, field_state* st)
 {
-    const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    unsigned long long nreach = 0;
-    for (int64_t x = gtid >> 6; x < N; x += nwaves) {
-        const double cx = C[x];
-        if (!(cx < INFINITY)) { if (lane == 0) { A[x] = 0; Ab[x] = 0; } continue; }
-        ++nreach;
-        if (x == src) { if (lane == 0) { A[x] = 0; Ab[x] = 0; } continue; }
-        double cb = INFINITY; int32_t yb = 0x7fffffff; int64_t eb = 0;
-        for (int64_t b = colptr[x] + lane; b < colptr[x + 1]; b += 64) {
-            if (!((efree[b >> 6] >> (b & 63)) & 1ull)) continue;
-            const int32_t y = rowval[b];
-            const double cy = C[y];
-            if (!(cy + nzval[b] == cx)) continue;
-            if (cy < cb || (cy == cb && y < yb)) { cb = cy; yb = y; eb = b; }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const double oc = __shfl_xor(cb, off);
-            const int32_t oy = __shfl_xor(yb, off);
-            const int64_t oe = __shfl_xor(eb, off);
-            if (oc < cb || (oc == cb && oy < yb)) { cb = oc; yb = oy; eb = oe; }
-        }
-        if (lane == 0) { A[x] = yb == 0x7fffffff ? 0 : (int64_t)yb + 1; Ab[x] = eb; }
-    }
-    if (lane == 0 && nreach) atomicAdd(&st->reached, nreach);
+    parents_body<false, true>(N, src, colptr, rowval, nzval, efree, C, nullptr, A, Ab, &st->reached);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
@@ -246,12 +188,6 @@ static int32_t field_buffers(mpfmt_ctx* ctx)
         ctx->fld_N = N;
     }
     return MPFMT_OK;
-}
-
-static unsigned field_wave_blocks(const mpfmt_ctx* ctx)
-{
-    const int64_t blocks_all = (ctx->N + 3) / 4;                              // one wavefront per column, grid-stride (kernels_sssp.hip)
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks_all, (int64_t)ctx->num_cus * 16));
 }
 
 static void field_stats(mpfmt_ctx* ctx, const field_state* sh, int32_t path, float ms, mpfmt_field_info* info)
@@ -283,7 +219,7 @@ int32_t mpfmt_field_compute(mpfmt_ctx* ctx, int64_t source0, int32_t checkpts, c
     hipLaunchKernelGGL(k_field_state_init, dim3(1), dim3(64), 0, ctx->stream, st);
     {
         mpfmt_timed tm(ctx);
-        hipLaunchKernelGGL(k_field_parents, dim3(field_wave_blocks(ctx)), dim3(256), 0, ctx->stream, N, source0, ctx->colptr, ctx->rowval, ctx->nzval,
+        hipLaunchKernelGGL(k_field_parents, dim3(relax_wave_blocks(ctx, N)), dim3(256), 0, ctx->stream, N, source0, ctx->colptr, ctx->rowval, ctx->nzval,
                            ctx->graph_free, ctx->fld_C, ctx->fld_A, ctx->fld_Ab, st);
         tm.end("field_parents");
     }
@@ -323,7 +259,7 @@ int32_t mpfmt_field_repair(mpfmt_ctx* ctx, const uint64_t* d_F, mpfmt_field_info
     uint64_t* D = ctx->fld_bm.get();
     uint64_t* ring = D + words;
     const unsigned nb_n = (unsigned)((std::max<int64_t>(N, 1) + 255) / 256);  // lane per sample: a wavefront = one word
-    const unsigned nb = field_wave_blocks(ctx);
+    const unsigned nb = relax_wave_blocks(ctx, N);
     // the library's own r-disc build is symmetric by construction; a k-nearest graph is directed and an imported one is the caller's
     const int sym = (ctx->knn_k == 0 && !ctx->graph_imported) ? 1 : 0;
     HIPCHK(ctx, hipEventRecord(ctx->sssp_ev[0], ctx->stream));
@@ -331,18 +267,12 @@ int32_t mpfmt_field_repair(mpfmt_ctx* ctx, const uint64_t* d_F, mpfmt_field_info
         mpfmt_timed tm(ctx);
         hipLaunchKernelGGL(k_field_state_init, dim3(1), dim3(64), 0, ctx->stream, st);
         hipLaunchKernelGGL(k_field_i0, dim3(nb_n), dim3(256), 0, ctx->stream, N, words, src, ctx->graph_free, d_F, ctx->fld_C, ctx->fld_Ab, D, ring, st);
-        // every pass that changes something gives +Inf to at least one more sample: N passes bound the loop
-        int64_t pass = 0;
-        bool done = false;
-        while (!done) {
-            if (pass > N + FIELD_BATCH) return mpfmt_fail(ctx, MPFMT_ERR_HIP, "the closure of the invalidated set did not settle within N passes");
-            for (int q = 0; q < FIELD_BATCH; ++q, ++pass)
-                hipLaunchKernelGGL(k_field_close, dim3(nb_n), dim3(256), 0, ctx->stream, N, src, (int)(pass % 3), ctx->fld_C, ctx->fld_A,
-                                   (unsigned long long*)ring, st);
-            HIPCHK(ctx, hipMemcpyAsync(sh, st, sizeof(field_state), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            done = sh->close_changed[pass % 3] == 0;                           // what the batch's last pass did
-        }
+        // (every pass that changes something gives +Inf to at least one more sample)
+        auto pass = [&](int64_t p) {
+            hipLaunchKernelGGL(k_field_close, dim3(nb_n), dim3(256), 0, ctx->stream, N, src, ring_slot(p), ctx->fld_C, ctx->fld_A,
+                               (unsigned long long*)ring, st);
+        };
+        if ((rc = relax_rounds(ctx, N, st, sh, sh->close, pass, "the closure of the invalidated set did not settle within N passes"))) return rc;
         // the dirty set has entered ring slot 0: its storage now collects the columns read
         HIPCHK(ctx, hipMemsetAsync(D, 0, sizeof(uint64_t) * (size_t)words, ctx->stream));
         hipLaunchKernelGGL(k_field_arm, dim3(1), dim3(64), 0, ctx->stream, st);
@@ -350,17 +280,12 @@ int32_t mpfmt_field_repair(mpfmt_ctx* ctx, const uint64_t* d_F, mpfmt_field_info
     }
     {
         mpfmt_timed tm(ctx);
-        int64_t round = 0;
-        bool done = false;
-        while (!done) {
-            if (round > N + FIELD_BATCH) return mpfmt_fail(ctx, MPFMT_ERR_HIP, "the field repair did not settle within N rounds");
-            for (int q = 0; q < FIELD_BATCH; ++q, ++round)
-                hipLaunchKernelGGL(k_field_relax, dim3(nb), dim3(256), 0, ctx->stream, N, words, (int)(round % 3), round == 0 ? 1 : 0, sym, ctx->colptr,
-                                   ctx->rowval, ctx->nzval, ctx->graph_free, d_F, ctx->fld_C, ring, (unsigned long long*)D, st);
-            HIPCHK(ctx, hipMemcpyAsync(sh, st, sizeof(field_state), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            done = sh->slot[round % 3].changed == 0;
-        }
+        auto round = [&](int64_t t) {
+            hipLaunchKernelGGL(k_field_relax, dim3(nb), dim3(256), 0, ctx->stream, N, words, ring_slot(t), t == 0 ? 1 : 0, sym,
+                               ctx->colptr, ctx->rowval, ctx->nzval, ctx->graph_free, d_F, ctx->fld_C, ring,
+                               (unsigned long long*)D, st);
+        };
+        if ((rc = relax_rounds(ctx, N, st, sh, sh->slot, round, "the field repair did not settle within N rounds"))) return rc;
         HIPCHK(ctx, hipMemsetAsync(D, 0, sizeof(uint64_t) * (size_t)words, ctx->stream));      // the field is valid again: nothing is dirty
         tm.end("field_relax");
     }

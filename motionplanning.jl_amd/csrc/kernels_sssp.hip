@@ -6,38 +6,16 @@
 //   round t:  for every column x that may still improve:  C[x] = min(C[x], min over usable entries whose row y changed in round t-1
 //             of fl(C[y] + w)); a column that improved marks itself in the next round's bitmap.
 //
-// * one wavefront per column, lanes over its entries, xor-shuffle minimum;
-// * three sample bitmaps in rotation: round t reads B[t % 3], marks B[(t+1) % 3] and clears B[(t+2) % 3] (last read by round t-1),
-//   so no round needs a memset of its own;
-// * the cost band: mlow(t) = the lowest label written in round t-1.  Every label written in round t is fl(C[y] + w) >= C[y] >= mlow(t)
-//   for a y of the bitmap (by induction over the writes of the round), so a column with C[x] <= mlow(t) cannot improve and is skipped
-//   before any of its entries is read: the settled interior stops costing bandwidth.  (The source, C = 0, is always skipped: that is
-//   its exemption from F.)
-// * labels are read and written in place while the round runs (plain aligned 8-byte loads and stores, never torn).  A reader may see
-//   the label of this round or the one before -- the L2 of another XCD may hold the older one -- both are upper bounds of the fixed
-//   point that only ever decrease, and the writer's bit in B[(t+1) % 3] makes the reader look again next round: values are
-//   independent of the schedule, `rounds` and `relaxations` are not;
-// * the per-round counters live in a ring of three slots like the bitmaps; the host reads them once per SSSP_BATCH rounds, and a round
-//   whose predecessor changed nothing returns at once, so the tail of a batch costs empty launches only;
+// * one wavefront per column, lanes over its entries, xor-shuffle minimum (column_fold of relax_core.h);
+// * the ring of three sample bitmaps and round slots, the cost band, the in-place label reads and the host loop are those of
+//   relax_core.h, where their arguments are written down;
 // * parents come from a separate pass over the finished labels (k_sssp_parents), a function of C alone.
-#include "mpfmt_internal.h"
-#include <cmath>
-#include <algorithm>
+#include "relax_core.h"
 
-#define SSSP_BATCH 8                         // rounds issued between two reads of the round state
-#define SSSP_INF_BITS 0x7FF0000000000000ull
-
-struct sssp_slot { unsigned long long changed, minbits; };
 struct sssp_state {
-    sssp_slot slot[3];
+    band_slot slot[3];
     unsigned long long relax, rounds, reached, pad;
 };
-
-__device__ __forceinline__ double wave_min(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off));
-    return v;
-}
 
 __global__ __launch_bounds__(256) void k_sssp_init(int64_t N, int64_t words, int64_t src, double* __restrict__ C, uint64_t* __restrict__ bm,
                                                    sssp_state* __restrict__ st)
@@ -46,9 +24,7 @@ __global__ __launch_bounds__(256) void k_sssp_init(int64_t N, int64_t words, int
     if (i < N) C[i] = i == src ? 0.0 : INFINITY;
     if (i < 3 * words) bm[i] = (i == (src >> 6)) ? 1ull << (src & 63) : 0ull;
     if (i == 0) {
-        st->slot[0].changed = 1; st->slot[0].minbits = 0ull;
-        st->slot[1].changed = 0; st->slot[1].minbits = SSSP_INF_BITS;
-        st->slot[2].changed = 0; st->slot[2].minbits = SSSP_INF_BITS;
+        band_ring_init(st->slot, 1);
         st->relax = 0; st->rounds = 0; st->reached = 0; st->pad = 0;
     }
 }
@@ -58,20 +34,13 @@ __global__ __launch_bounds__(256) void k_sssp_relax(int64_t N, int64_t words, in
                                                     const uint64_t* __restrict__ efree, const uint64_t* __restrict__ F, double* C,
                                                     uint64_t* bm, sssp_state* st)
 {
-    const int s_in = round % 3, s_out = (round + 1) % 3, s_clr = (round + 2) % 3;
-    const unsigned long long cin = st->slot[s_in].changed;
-    const double mlow = __longlong_as_double((long long)st->slot[s_in].minbits);
+    const ring_idx r = ring_at(round);
+    const double mlow = label_of_bits(st->slot[r.in].minbits);
     const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gtid == 0) {                                        // (the slot round + 2 will mark: nobody reads or writes it during this round)
-        st->slot[s_clr].changed = 0; st->slot[s_clr].minbits = SSSP_INF_BITS;
-        if (cin) st->rounds += 1;
-    }
-    if (cin == 0) return;
     const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
-    uint64_t* bclr = bm + (int64_t)s_clr * words;
-    for (int64_t w = gtid; w < words; w += nthreads) bclr[w] = 0ull;
-    const uint64_t* bin = bm + (int64_t)s_in * words;
-    unsigned long long* bout = (unsigned long long*)(bm + (int64_t)s_out * words);
+    const uint64_t* bin;
+    unsigned long long* bout;
+    if (!ring_round(st->slot, &st->rounds, bm, words, r, gtid, nthreads, bin, bout)) return;
     const int lane = threadIdx.x & 63;
     const int64_t nwaves = nthreads >> 6;
     unsigned long long nrel = 0, nchg = 0;
@@ -79,18 +48,8 @@ __global__ __launch_bounds__(256) void k_sssp_relax(int64_t N, int64_t words, in
     for (int64_t x = gtid >> 6; x < N; x += nwaves) {
         const double cx = C[x];
         if (cx <= mlow) continue;
-        if (F && !((F[x >> 6] >> (x & 63)) & 1ull)) continue;
-        const int64_t b0 = colptr[x], b1 = colptr[x + 1];
-        double best = INFINITY;
-        for (int64_t b = b0 + lane; b < b1; b += 64) {
-            const int32_t y = rowval[b];
-            if (!((bin[y >> 6] >> (y & 63)) & 1ull)) continue;
-            if (!((efree[b >> 6] >> (b & 63)) & 1ull)) continue;
-            const double c = C[y] + nzval[b];
-            ++nrel;
-            best = fmin(best, c);
-        }
-        best = wave_min(best);
+        if (F && !bit_of(F, x)) continue;
+        const double best = column_fold<true, false>(colptr[x], colptr[x + 1], lane, rowval, nzval, efree, bin, C, nrel);
         if (best < cx) {
             if (lane == 0) {
                 C[x] = best;
@@ -100,12 +59,12 @@ __global__ __launch_bounds__(256) void k_sssp_relax(int64_t N, int64_t words, in
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) nrel += __shfl_xor(nrel, off);
+    nrel = wave_sum(nrel);
     if (lane == 0) {
         if (nrel) atomicAdd(&st->relax, nrel);
         if (nchg) {
-            atomicAdd(&st->slot[s_out].changed, nchg);
-            atomicMin(&st->slot[s_out].minbits, (unsigned long long)__double_as_longlong(lmin));      // (labels are >= 0: their bit patterns order like the values)
+            atomicAdd(&st->slot[r.out].changed, nchg);
+            atomicMin(&st->slot[r.out].minbits, label_bits(lmin));
         }
     }
 }
@@ -115,31 +74,7 @@ __global__ __launch_bounds__(256) void k_sssp_parents(int64_t N, int64_t src, co
                                                       const double* __restrict__ nzval, const uint64_t* __restrict__ efree,
                                                       const double* __restrict__ C, int64_t* __restrict__ A, sssp_state* st)
 {
-    const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    unsigned long long nreach = 0;
-    for (int64_t x = gtid >> 6; x < N; x += nwaves) {
-        const double cx = C[x];
-        if (!(cx < INFINITY)) { if (lane == 0) A[x] = 0; continue; }
-        ++nreach;
-        if (x == src) { if (lane == 0) A[x] = 0; continue; }
-        double cb = INFINITY; int32_t yb = 0x7fffffff;
-        for (int64_t b = colptr[x] + lane; b < colptr[x + 1]; b += 64) {
-            if (!((efree[b >> 6] >> (b & 63)) & 1ull)) continue;
-            const int32_t y = rowval[b];
-            const double cy = C[y];
-            if (!(cy + nzval[b] == cx)) continue;
-            if (cy < cb || (cy == cb && y < yb)) { cb = cy; yb = y; }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const double oc = __shfl_xor(cb, off);
-            const int32_t oy = __shfl_xor(yb, off);
-            if (oc < cb || (oc == cb && oy < yb)) { cb = oc; yb = oy; }
-        }
-        if (lane == 0) A[x] = yb == 0x7fffffff ? 0 : (int64_t)yb + 1;
-    }
-    if (lane == 0 && nreach) atomicAdd(&st->reached, nreach);
+    parents_body<false, false>(N, src, colptr, rowval, nzval, efree, C, nullptr, A, nullptr, &st->reached);
 }
 
 void mpfmt_sssp_free(mpfmt_ctx* ctx)
@@ -160,9 +95,7 @@ __global__ __launch_bounds__(256) void k_sssp_seed_clear(int64_t N, int64_t word
     if (i < N) { C[i] = INFINITY; seed[i] = INFINITY; }
     if (i < 3 * words) bm[i] = 0ull;
     if (i == 0) {
-        st->slot[0].changed = 0; st->slot[0].minbits = 0ull;
-        st->slot[1].changed = 0; st->slot[1].minbits = SSSP_INF_BITS;
-        st->slot[2].changed = 0; st->slot[2].minbits = SSSP_INF_BITS;
+        band_ring_init(st->slot, 0);
         st->relax = 0; st->rounds = 0; st->reached = 0; st->pad = 0;
     }
 }
@@ -190,31 +123,7 @@ __global__ __launch_bounds__(256) void k_sssp_parents_seeded(int64_t N, const in
                                                              const double* __restrict__ C, const double* __restrict__ seed,
                                                              int64_t* __restrict__ A, sssp_state* st)
 {
-    const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    unsigned long long nreach = 0;
-    for (int64_t x = gtid >> 6; x < N; x += nwaves) {
-        const double cx = C[x];
-        if (!(cx < INFINITY)) { if (lane == 0) A[x] = 0; continue; }
-        ++nreach;
-        if (seed[x] == cx) { if (lane == 0) A[x] = -1; continue; }
-        double cb = INFINITY; int32_t yb = 0x7fffffff;
-        for (int64_t b = colptr[x] + lane; b < colptr[x + 1]; b += 64) {
-            if (!((efree[b >> 6] >> (b & 63)) & 1ull)) continue;
-            const int32_t y = rowval[b];
-            const double cy = C[y];
-            if (!(cy + nzval[b] == cx)) continue;
-            if (cy < cb || (cy == cb && y < yb)) { cb = cy; yb = y; }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const double oc = __shfl_xor(cb, off);
-            const int32_t oy = __shfl_xor(yb, off);
-            if (oc < cb || (oc == cb && oy < yb)) { cb = oc; yb = oy; }
-        }
-        if (lane == 0) A[x] = yb == 0x7fffffff ? 0 : (int64_t)yb + 1;
-    }
-    if (lane == 0 && nreach) atomicAdd(&st->reached, nreach);
+    parents_body<true, false>(N, -1, colptr, rowval, nzval, efree, C, seed, A, nullptr, &st->reached);
 }
 
 // One field over the resident graph and mask: from a sample (source0 >= 0: k_sssp_init, k_sssp_parents) or from the usable entries of an
@@ -234,9 +143,7 @@ static int32_t sssp_run(mpfmt_ctx* ctx, int64_t source0, const sssp_seeds* sd, c
     for (int k = 0; k < 2; ++k) if (!ctx->sssp_ev[k]) HIPCHK(ctx, hipEventCreate(&ctx->sssp_ev[k]));
     sssp_state* st = (sssp_state*)ctx->sssp_state.get();
     sssp_state* sh = (sssp_state*)ctx->sssp_state_host.get();
-    // one wavefront per column, grid-stride: enough waves to fill the chip several times over (a skipped column costs one load)
-    const int64_t blocks_all = (N + 3) / 4;
-    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks_all, (int64_t)ctx->num_cus * 16));
+    const unsigned nb = relax_wave_blocks(ctx, N);
     const unsigned nb_init = (unsigned)((std::max<int64_t>(N, 3 * words) + 255) / 256);
     HIPCHK(ctx, hipEventRecord(ctx->sssp_ev[0], ctx->stream));
     {
@@ -249,18 +156,11 @@ static int32_t sssp_run(mpfmt_ctx* ctx, int64_t source0, const sssp_seeds* sd, c
                 hipLaunchKernelGGL(k_sssp_seed, dim3((unsigned)((sd->n + 255) / 256)), dim3(256), 0, ctx->stream, sd->n, sd->idx1, sd->dist, sd->bits,
                                    ctx->sssp_C, ctx->sssp_seed, ctx->sssp_bm, st);
         }
-        // every non-final round lowers at least one label for good, and a label is the fold of a simple path: N rounds bound the loop
-        int64_t round = 0;
-        bool done = false;
-        while (!done) {
-            if (round > N + SSSP_BATCH) return mpfmt_fail(ctx, MPFMT_ERR_HIP, "shortest-path relaxation did not settle within N rounds");
-            for (int q = 0; q < SSSP_BATCH; ++q, ++round)
-                hipLaunchKernelGGL(k_sssp_relax, dim3(nb), dim3(256), 0, ctx->stream, N, words, (int)(round % 3), ctx->colptr, ctx->rowval, ctx->nzval,
-                                   ctx->graph_free, d_F, ctx->sssp_C, ctx->sssp_bm, st);
-            HIPCHK(ctx, hipMemcpyAsync(sh, st, sizeof(sssp_state), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            done = sh->slot[round % 3].changed == 0;        // what the batch's last round marked for the next one
-        }
+        auto round = [&](int64_t t) {
+            hipLaunchKernelGGL(k_sssp_relax, dim3(nb), dim3(256), 0, ctx->stream, N, words, ring_slot(t), ctx->colptr, ctx->rowval,
+                               ctx->nzval, ctx->graph_free, d_F, ctx->sssp_C, ctx->sssp_bm, st);
+        };
+        if ((rc = relax_rounds(ctx, N, st, sh, sh->slot, round, "shortest-path relaxation did not settle within N rounds"))) return rc;
         tm.end("sssp_relax");
     }
     {

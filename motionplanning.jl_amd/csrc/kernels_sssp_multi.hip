@@ -9,7 +9,7 @@
 // * one wavefront per column, grid-stride; the column's entries are read 64 at a time (rowval, nzval, mask bit, the row's bit in the
 //   changed-sample bitmap), a ballot picks the entries to visit, row index and weight are made wave-uniform by readlane and every lane
 //   evaluates fl(L[y][lane] + w) -- unfused fp64, one add, what k_sssp_relax evaluates -- with four row loads in flight;
-// * the changed-sample bitmaps are per SAMPLE (any source changed it), three in rotation as in kernels_sssp.hip: a superset of every
+// * the changed-sample bitmaps are per SAMPLE (any source changed it), three in rotation, the ring of relax_core.h: a superset of every
 //   source's own frontier, so each lane sees at least what its single-source round would, plus candidates that are labels of real paths
 //   too: every value stays an upper bound of the source's least fixed point, and the fixed point is reached when nothing changes;
 // * the cost band is per LANE: mlow[s](t) = the lowest label written for source s in round t-1.  A label written for s in round t is
@@ -20,22 +20,24 @@
 //   enter a column, never improve and are not counted;
 // * checkpts: a column with F[x] clear is skipped for every lane.  A source with F clear keeps its label 0 (its exemption): 0 is never
 //   above mlow, and no lane may enter an F-clear column;
-// * round state: a ring of three slots (changed count, 64 band minima), read by the host once per MS_BATCH rounds; a round whose
-//   predecessor changed nothing returns at once;
+// * round state: the ring of relax_core.h with a slot of its own (changed count, 64 band minima);
 // * parents: a separate pass over the finished labels, lanes over sources (k_ms_parents), which also counts `reached` per lane;
 // * copy-out: a tiled transpose [N][64] -> [64][chunk] through LDS (k_ms_transpose), then strided copies into the caller's arrays.
 // The cost matrix between external starts and goals (mpfmt_roadmap_matrix) seeds a group's labels from the starts' near lists
 // (k_ms_seed) and reduces every goal's head list over the 64 fields at once (k_ms_goal).
-#include "mpfmt_internal.h"
-#include <cmath>
-#include <algorithm>
+#include "relax_core.h"
 
-#define MS_BATCH 8                           // rounds issued between two reads of the round state
 #define MS_W 64                              // sources per group = lanes of a wavefront
-#define MS_INF_BITS 0x7FF0000000000000ull
 #define MS_CHUNK 65536                       // samples per transposed chunk of the copy-out (32 MiB of staging)
 
-struct ms_slot { unsigned long long changed, pad; unsigned long long minbits[MS_W]; };
+struct ms_slot {                             // a band minimum per source; the first MS_W threads of the grid reset them
+    unsigned long long changed, pad; unsigned long long minbits[MS_W];
+    __device__ __forceinline__ void clear(int64_t gtid)
+    {
+        if (gtid < MS_W) minbits[gtid] = LABEL_INF_BITS;
+        if (gtid == 0) changed = 0;
+    }
+};
 struct ms_state {
     ms_slot slot[3];
     unsigned long long rows, rounds, pad[2];
@@ -69,8 +71,8 @@ __device__ __forceinline__ double ms_visit(unsigned long long m, int32_t y, doub
 __device__ __forceinline__ void ms_state_reset(ms_state* st, int64_t i, int n, unsigned long long changed0)
 {
     if (i < MS_W) {
-        st->slot[0].minbits[i] = i < n ? 0ull : MS_INF_BITS;
-        st->slot[1].minbits[i] = MS_INF_BITS; st->slot[2].minbits[i] = MS_INF_BITS;
+        st->slot[0].minbits[i] = i < n ? 0ull : LABEL_INF_BITS;
+        st->slot[1].minbits[i] = LABEL_INF_BITS; st->slot[2].minbits[i] = LABEL_INF_BITS;
         st->reached[i] = 0;
     }
     if (i == 0) {
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(256) void k_ms_seed(int64_t i0, const int64_t* __re
         atomicOr((unsigned long long*)&bm[y >> 6], 1ull << (y & 63));
         ++cnt;
     }
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+    cnt = wave_sum(cnt);
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&st->slot[0].changed, cnt);
 }
 
@@ -134,29 +136,21 @@ __global__ __launch_bounds__(256) void k_ms_relax(int64_t N, int64_t words, int 
                                                   ms_state* st)
 {
     __shared__ double s_min[4][MS_W];
-    const int s_in = round % 3, s_out = (round + 1) % 3, s_clr = (round + 2) % 3;
+    const ring_idx r = ring_at(round);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long cin = st->slot[s_in].changed;
-    const double mlow = __longlong_as_double((long long)st->slot[s_in].minbits[lane]);
+    const double mlow = label_of_bits(st->slot[r.in].minbits[lane]);
     const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gtid < MS_W) st->slot[s_clr].minbits[gtid] = MS_INF_BITS;      // (the slot round + 2 will mark: nobody reads or writes it during this round)
-    if (gtid == 0) {
-        st->slot[s_clr].changed = 0;
-        if (cin) st->rounds += 1;
-    }
-    if (cin == 0) return;
     const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
-    uint64_t* bclr = bm + (int64_t)s_clr * words;
-    for (int64_t w = gtid; w < words; w += nthreads) bclr[w] = 0ull;
-    const uint64_t* bin = bm + (int64_t)s_in * words;
-    unsigned long long* bout = (unsigned long long*)(bm + (int64_t)s_out * words);
+    const uint64_t* bin;
+    unsigned long long* bout;
+    if (!ring_round(st->slot, &st->rounds, bm, words, r, gtid, nthreads, bin, bout)) return;
     const int64_t nwaves = nthreads >> 6;
     unsigned long long nrows = 0, nchg = 0;
     double lmin = INFINITY;
     for (int64_t x = gtid >> 6; x < N; x += nwaves) {
         const double cx = L[x * MS_W + lane];
         if (!__ballot(cx > mlow)) continue;
-        if (F && !((F[x >> 6] >> (x & 63)) & 1ull)) continue;
+        if (F && !bit_of(F, x)) continue;
         const int64_t b0 = colptr[x], b1 = colptr[x + 1];
         double best = INFINITY;
         for (int64_t c0 = b0; c0 < b1; c0 += 64) {
@@ -164,7 +158,7 @@ __global__ __launch_bounds__(256) void k_ms_relax(int64_t N, int64_t words, int 
             const bool valid = b < b1;
             const int32_t y = valid ? rowval[b] : 0;
             const double w = valid ? nzval[b] : 0.0;
-            const bool ok = valid && ((bin[y >> 6] >> (y & 63)) & 1ull) && ((efree[b >> 6] >> (b & 63)) & 1ull);
+            const bool ok = valid && bit_of(bin, y) && bit_of(efree, b);
             const unsigned long long m = __ballot(ok);
             nrows += (unsigned long long)__popcll(m);
             best = ms_visit(m, y, w, L, lane, best);
@@ -182,12 +176,24 @@ __global__ __launch_bounds__(256) void k_ms_relax(int64_t N, int64_t words, int 
     __syncthreads();
     if (wv == 0) {
         lmin = fmin(fmin(s_min[0][lane], s_min[1][lane]), fmin(s_min[2][lane], s_min[3][lane]));
-        const unsigned long long mb = (unsigned long long)__double_as_longlong(lmin);      // (labels are >= 0: their bit patterns order like the values)
-        if (lmin < INFINITY && mb < st->slot[s_out].minbits[lane]) atomicMin(&st->slot[s_out].minbits[lane], mb);
+        const unsigned long long mb = label_bits(lmin);
+        if (lmin < INFINITY && mb < st->slot[r.out].minbits[lane]) atomicMin(&st->slot[r.out].minbits[lane], mb);
     }
     if (lane == 0) {
         if (nrows) atomicAdd(&st->rows, nrows);
-        if (nchg) atomicAdd(&st->slot[s_out].changed, nchg);
+        if (nchg) atomicAdd(&st->slot[r.out].changed, nchg);
+    }
+}
+
+// reached[lane] += the counts of the block's four wavefronts: one atomicAdd per lane and block
+__device__ __forceinline__ void ms_count_reached(unsigned long long nreach, int lane, int wv, ms_state* st)
+{
+    __shared__ unsigned long long s_cnt[4][MS_W];
+    s_cnt[wv][lane] = nreach;
+    __syncthreads();
+    if (wv == 0) {
+        nreach = s_cnt[0][lane] + s_cnt[1][lane] + s_cnt[2][lane] + s_cnt[3][lane];
+        if (nreach) atomicAdd(&st->reached[lane], nreach);
     }
 }
 
@@ -198,7 +204,6 @@ __global__ __launch_bounds__(256) void k_ms_parents(int64_t N, int n, const int6
                                                     const uint64_t* __restrict__ efree, const double* __restrict__ L, int64_t* __restrict__ At,
                                                     ms_state* st)
 {
-    __shared__ unsigned long long s_cnt[4][MS_W];
     const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -209,7 +214,7 @@ __global__ __launch_bounds__(256) void k_ms_parents(int64_t N, int n, const int6
         const bool reached = cx < INFINITY;
         nreach += reached ? 1 : 0;
         const bool want = reached && x != mine;
-        double cb = INFINITY; int32_t yb = 0x7fffffff;
+        double cb = INFINITY; int32_t yb = PARENT_NONE;
         if (__ballot(want)) {
             const int64_t b0 = colptr[x], b1 = colptr[x + 1];
             for (int64_t c0 = b0; c0 < b1; c0 += 64) {
@@ -217,43 +222,32 @@ __global__ __launch_bounds__(256) void k_ms_parents(int64_t N, int n, const int6
                 const bool valid = b < b1;
                 const int32_t y = valid ? rowval[b] : 0;
                 const double w = valid ? nzval[b] : 0.0;
-                unsigned long long m = __ballot(valid && ((efree[b >> 6] >> (b & 63)) & 1ull));
+                unsigned long long m = __ballot(valid && bit_of(efree, b));
                 while (m) {
                     const int j0 = __builtin_ctzll(m); m &= m - 1;
                     const int j1 = m ? __builtin_ctzll(m) : j0; m &= m - 1 + (m == 0);
                     const int32_t y0 = __builtin_amdgcn_readlane(y, j0), y1 = __builtin_amdgcn_readlane(y, j1);
                     const double c0v = L[(int64_t)y0 * MS_W + lane], c1v = L[(int64_t)y1 * MS_W + lane];
                     const double w0 = ms_readlane(w, j0), w1 = ms_readlane(w, j1);
-                    if (c0v + w0 == cx && (c0v < cb || (c0v == cb && y0 < yb))) { cb = c0v; yb = y0; }
-                    if (c1v + w1 == cx && (c1v < cb || (c1v == cb && y1 < yb))) { cb = c1v; yb = y1; }
+                    if (c0v + w0 == cx && parent_before(c0v, y0, cb, yb)) { cb = c0v; yb = y0; }
+                    if (c1v + w1 == cx && parent_before(c1v, y1, cb, yb)) { cb = c1v; yb = y1; }
                 }
             }
         }
-        At[x * MS_W + lane] = (want && yb != 0x7fffffff) ? (int64_t)yb + 1 : 0;
+        At[x * MS_W + lane] = (want && yb != PARENT_NONE) ? (int64_t)yb + 1 : 0;
     }
-    s_cnt[wv][lane] = nreach;
-    __syncthreads();
-    if (wv == 0) {
-        nreach = s_cnt[0][lane] + s_cnt[1][lane] + s_cnt[2][lane] + s_cnt[3][lane];
-        if (nreach) atomicAdd(&st->reached[lane], nreach);
-    }
+    ms_count_reached(nreach, lane, wv, st);
 }
 
 // reached per lane without a parent pass
 __global__ __launch_bounds__(256) void k_ms_reached(int64_t N, const double* __restrict__ L, ms_state* st)
 {
-    __shared__ unsigned long long s_cnt[4][MS_W];
     const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     unsigned long long nreach = 0;
     for (int64_t x = gtid >> 6; x < N; x += nwaves) nreach += L[x * MS_W + lane] < INFINITY ? 1 : 0;
-    s_cnt[wv][lane] = nreach;
-    __syncthreads();
-    if (wv == 0) {
-        nreach = s_cnt[0][lane] + s_cnt[1][lane] + s_cnt[2][lane] + s_cnt[3][lane];
-        if (nreach) atomicAdd(&st->reached[lane], nreach);
-    }
+    ms_count_reached(nreach, lane, wv, st);
 }
 
 // in [N][64] -> out [n][cnt] for the samples x0 .. x0 + cnt (8-byte items: labels, or parents); one 64 x 64 tile per workgroup through LDS
@@ -348,31 +342,20 @@ static int32_t ms_ensure(mpfmt_ctx* ctx, bool parents, bool stage)
     return MPFMT_OK;
 }
 
-static unsigned ms_grid(const mpfmt_ctx* ctx)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((ctx->N + 3) / 4, (int64_t)ctx->num_cus * 16));
-}
-
-// the rounds of one group, in the host loop of kernels_sssp.hip: MS_BATCH launches, one read of the round state
+// the rounds of one group (relax_rounds of relax_core.h)
 static int32_t ms_rounds(mpfmt_ctx* ctx, const uint64_t* d_F)
 {
     const int64_t N = ctx->N, words = (N + 63) / 64;
     ms_state* st = (ms_state*)ctx->ms_state.get();
     ms_state* sh = (ms_state*)ctx->ms_state_host.get();
-    const unsigned nb = ms_grid(ctx);
+    const unsigned nb = relax_wave_blocks(ctx, N);
+    int32_t rc;
     mpfmt_timed tm(ctx);
-    // every non-final round lowers at least one label for good, and a label is the fold of a simple path: N rounds bound the loop
-    int64_t round = 0;
-    bool done = false;
-    while (!done) {
-        if (round > N + MS_BATCH) return mpfmt_fail(ctx, MPFMT_ERR_HIP, "shortest-path relaxation did not settle within N rounds");
-        for (int q = 0; q < MS_BATCH; ++q, ++round)
-            hipLaunchKernelGGL(k_ms_relax, dim3(nb), dim3(256), 0, ctx->stream, N, words, (int)(round % 3), ctx->colptr, ctx->rowval, ctx->nzval,
-                               ctx->graph_free, d_F, ctx->ms_L.get(), ctx->ms_bm.get(), st);
-        HIPCHK(ctx, hipMemcpyAsync(sh, st, sizeof(ms_state), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        done = sh->slot[round % 3].changed == 0;            // what the batch's last round marked for the next one
-    }
+    auto round = [&](int64_t t) {
+        hipLaunchKernelGGL(k_ms_relax, dim3(nb), dim3(256), 0, ctx->stream, N, words, ring_slot(t), ctx->colptr, ctx->rowval, ctx->nzval,
+                           ctx->graph_free, d_F, ctx->ms_L.get(), ctx->ms_bm.get(), st);
+    };
+    if ((rc = relax_rounds(ctx, N, st, sh, sh->slot, round, "shortest-path relaxation did not settle within N rounds"))) return rc;
     tm.end("sssp_multi_relax");
     return MPFMT_OK;
 }
@@ -399,7 +382,7 @@ int32_t mpfmt_sssp_multi_device(mpfmt_ctx* ctx, const int64_t* sources1, int64_t
     if ((rc = ms_ensure(ctx, A_host != nullptr, true))) return rc;
     ms_state* st = (ms_state*)ctx->ms_state.get();
     ms_state* sh = (ms_state*)ctx->ms_state_host.get();
-    const unsigned nb = ms_grid(ctx);
+    const unsigned nb = relax_wave_blocks(ctx, ctx->N);
     const unsigned nb_init = (unsigned)((std::max<int64_t>(N * MS_W, 3 * words) + 255) / 256);
     ctx->ms_groups = ctx->ms_rounds = ctx->ms_rows = 0;
     for (int64_t q0 = 0; q0 < nsrc; q0 += MS_W) {

@@ -11,8 +11,8 @@
 //             decrease, so it can cost a wasted atomic, never a missed one), then a 64-bit atomicMin on the bit pattern (labels are
 //             non-negative doubles: their bits order like their values); a returned old value above cand marks y in B[(t+1) % 3].
 //
-// * rounds are separate launches; three bitmaps in rotation exactly as in kernels_sssp.hip (read t % 3, mark (t+1) % 3, clear
-//   (t+2) % 3); a fourth bitmap holds the targets for the successor passes;
+// * rounds are separate launches; three bitmaps in rotation, the ring of relax_core.h (its slots carry the count alone: the push has no
+//   cost band); a fourth bitmap holds the targets for the successor passes;
 // * the work unit of a wavefront is a quarter (16 bits) of a bitmap word: the unit is wave-uniform, so the column loop has no divergence;
 // * the value of G[x] a round pushes may be the one of the kernel boundary or one lowered meanwhile by another wavefront: both are upper
 //   bounds of the fixed point, and whoever lowered x marked it for the next round.  Nothing waits on another workgroup;
@@ -21,14 +21,10 @@
 // * unlike the pull, a round reads only the columns of the samples that changed: `columns` / `entries_read` / `atomics` record it;
 // * successors are a function of the finished G alone, in two passes over the columns of reached x: pass 1 atomicMin of bits(G[x])
 //   into best[y] among exact achievers, pass 2 atomicMin of x into S[y] among those with bits(G[x]) == best[y]: deterministic.
-#include "mpfmt_internal.h"
-#include <cmath>
-#include <algorithm>
-
-#define SSSP_TO_BATCH 8                      // rounds issued between two reads of the round state (SSSP_BATCH of kernels_sssp.hip)
+#include "relax_core.h"
 
 struct sssp_to_state {
-    unsigned long long changed[3];
+    count_slot slot[3];
     unsigned long long rounds, relax, atomics, entries, columns, reached;
 };
 
@@ -39,7 +35,7 @@ __global__ __launch_bounds__(256) void k_sssp_to_init(int64_t N, int64_t words, 
     if (i < N) G[i] = INFINITY;
     if (i < 4 * words) bm[i] = 0ull;
     if (i == 0) {
-        st->changed[0] = st->changed[1] = st->changed[2] = 0;
+        st->slot[0].changed = st->slot[1].changed = st->slot[2].changed = 0;
         st->rounds = st->relax = st->atomics = st->entries = st->columns = st->reached = 0;
     }
 }
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(256) void k_sssp_to_targets(int64_t ntgt, int64_t w
         atomicOr((unsigned long long*)&bm[t >> 6], 1ull << (t & 63));
         atomicOr((unsigned long long*)&bm[3 * words + (t >> 6)], 1ull << (t & 63));
     }
-    if (e == 0) st->changed[0] = 1;
+    if (e == 0) st->slot[0].changed = 1;
 }
 
 __global__ __launch_bounds__(256) void k_sssp_to_push(int64_t N, int64_t words, int round, const int64_t* __restrict__ colptr,
@@ -63,19 +59,12 @@ __global__ __launch_bounds__(256) void k_sssp_to_push(int64_t N, int64_t words, 
                                                       const uint64_t* __restrict__ efree, const uint64_t* __restrict__ F, double* G,
                                                       uint64_t* bm, sssp_to_state* st)
 {
-    const int s_in = round % 3, s_out = (round + 1) % 3, s_clr = (round + 2) % 3;
-    const unsigned long long cin = st->changed[s_in];
+    const ring_idx r = ring_at(round);
     const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gtid == 0) {                                        // (the slot round + 2 will mark: nobody reads or writes it during this round)
-        st->changed[s_clr] = 0;
-        if (cin) st->rounds += 1;
-    }
-    if (cin == 0) return;
     const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
-    uint64_t* bclr = bm + (int64_t)s_clr * words;
-    for (int64_t w = gtid; w < words; w += nthreads) bclr[w] = 0ull;
-    const uint64_t* bin = bm + (int64_t)s_in * words;
-    unsigned long long* bout = (unsigned long long*)(bm + (int64_t)s_out * words);
+    const uint64_t* bin;
+    unsigned long long* bout;
+    if (!ring_round(st->slot, &st->rounds, bm, words, r, gtid, nthreads, bin, bout)) return;
     unsigned long long* Gb = (unsigned long long*)G;
     const int lane = threadIdx.x & 63;
     const int64_t nwaves = nthreads >> 6;
@@ -93,25 +82,23 @@ __global__ __launch_bounds__(256) void k_sssp_to_push(int64_t N, int64_t words, 
             const int64_t b0 = colptr[x], b1 = colptr[x + 1];
             if (lane == 0) { ++ncol; nent += (unsigned long long)(b1 - b0); }
             for (int64_t b = b0 + lane; b < b1; b += 64) {
-                if (!((efree[b >> 6] >> (b & 63)) & 1ull)) continue;
+                if (!bit_of(efree, b)) continue;
                 const int32_t y = rowval[b];
                 const double cand = gx + nzval[b];
                 ++nrel;
                 if (!(cand < G[y])) continue;
-                const unsigned long long cb = (unsigned long long)__double_as_longlong(cand);
+                const unsigned long long cb = label_bits(cand);
                 const unsigned long long old = atomicMin(&Gb[y], cb);
                 ++natom;
                 if (old > cb) { atomicOr(&bout[y >> 6], 1ull << (y & 63)); ++nchg; }
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        nrel += __shfl_xor(nrel, off); natom += __shfl_xor(natom, off); nchg += __shfl_xor(nchg, off);
-    }
+    nrel = wave_sum(nrel); natom = wave_sum(natom); nchg = wave_sum(nchg);
     if (lane == 0) {
         if (nrel) atomicAdd(&st->relax, nrel);
         if (natom) atomicAdd(&st->atomics, natom);
-        if (nchg) atomicAdd(&st->changed[s_out], nchg);
+        if (nchg) atomicAdd(&st->slot[r.out].changed, nchg);
         if (ncol) { atomicAdd(&st->columns, ncol); atomicAdd(&st->entries, nent); }
     }
 }
@@ -179,9 +166,8 @@ int32_t mpfmt_sssp_to_device(mpfmt_ctx* ctx, const int64_t* targets1, int64_t nt
     double* G = ctx->sssp_C;
     unsigned long long* S = (unsigned long long*)ctx->sssp_A.get();
     // one wavefront per quarter word of the changed-sample bitmap, grid-stride
-    const int64_t blocks_units = words;                                      // 4 quarter words per 256-thread block
-    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks_units, (int64_t)ctx->num_cus * 16));
-    const unsigned nb_cols = (unsigned)std::max<int64_t>(1, std::min<int64_t>((N + 3) / 4, (int64_t)ctx->num_cus * 16));
+    const unsigned nb = relax_wave_blocks(ctx, 4 * words);
+    const unsigned nb_cols = relax_wave_blocks(ctx, N);                      // the successor passes: one wavefront per column
     const unsigned nb_init = (unsigned)((std::max<int64_t>(N, 4 * words) + 255) / 256);
     const unsigned nb_n = (unsigned)((N + 255) / 256);
     if (ntgt > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->sssp_to_tgt, targets1, sizeof(int64_t) * (size_t)ntgt, hipMemcpyHostToDevice, ctx->stream));
@@ -192,18 +178,11 @@ int32_t mpfmt_sssp_to_device(mpfmt_ctx* ctx, const int64_t* targets1, int64_t nt
         if (ntgt > 0)
             hipLaunchKernelGGL(k_sssp_to_targets, dim3((unsigned)((ntgt + 255) / 256)), dim3(256), 0, ctx->stream, ntgt, words, ctx->sssp_to_tgt, G,
                                ctx->sssp_bm, st);
-        // every non-final round lowers at least one label for good, and a label is the fold of a simple path: N rounds bound the loop
-        int64_t round = 0;
-        bool done = false;
-        while (!done) {
-            if (round > N + SSSP_TO_BATCH) return mpfmt_fail(ctx, MPFMT_ERR_HIP, "cost-to-go relaxation did not settle within N rounds");
-            for (int q = 0; q < SSSP_TO_BATCH; ++q, ++round)
-                hipLaunchKernelGGL(k_sssp_to_push, dim3(nb), dim3(256), 0, ctx->stream, N, words, (int)(round % 3), ctx->colptr, ctx->rowval,
-                                   ctx->nzval, ctx->graph_free, d_F, G, ctx->sssp_bm, st);
-            HIPCHK(ctx, hipMemcpyAsync(sh, st, sizeof(sssp_to_state), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            done = sh->changed[round % 3] == 0;             // what the batch's last round marked for the next one
-        }
+        auto round = [&](int64_t t) {
+            hipLaunchKernelGGL(k_sssp_to_push, dim3(nb), dim3(256), 0, ctx->stream, N, words, ring_slot(t), ctx->colptr, ctx->rowval,
+                               ctx->nzval, ctx->graph_free, d_F, G, ctx->sssp_bm, st);
+        };
+        if ((rc = relax_rounds(ctx, N, st, sh, sh->slot, round, "cost-to-go relaxation did not settle within N rounds"))) return rc;
         tm.end("sssp_to_push");
     }
     {

@@ -1435,21 +1435,35 @@ static int32_t sssp_resident_bitmap(mpfmt_ctx* ctx)
     return steer_point_bitmap(ctx);
 }
 
+// The prelude of a field call over the resident graph: the ready check (euclid: the Euclidean graph the tracked field asks for), the
+// checkpts refusal, the 1-based index list idx[0 .. n) (`what` names it in the error), hipSetDevice, and with checkpts the point bitmap:
+// *d_F = ctx->sssp_F, or nullptr without checkpts.  A caller that will run nothing (no source) passes d_F = nullptr and gets the checks
+// alone.  Nothing in the ctx has been touched when a check refuses.
+static int32_t field_prelude(mpfmt_ctx* ctx, const int64_t* idx, int64_t n, const char* what, bool euclid, int32_t checkpts, const uint64_t** d_F)
+{
+    int32_t rc;
+    if (d_F) *d_F = nullptr;
+    if ((rc = euclid ? sssp_ready_euclid(ctx) : sssp_ready(ctx))) return rc;
+    if (checkpts && !ctx->have_boxes && ctx->cc_kind == 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "checkpts needs an obstacle set");
+    if ((rc = check_idx(ctx, idx, n, what))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!checkpts || !d_F) return MPFMT_OK;
+    if ((rc = sssp_resident_bitmap(ctx))) return rc;                     // (the Euclidean bitmap whenever euclid: no steering graph got past)
+    *d_F = ctx->sssp_F.get();
+    return MPFMT_OK;
+}
+
 int32_t mpfmt_graph_sssp(mpfmt_ctx* ctx, const int64_t* sources, int64_t nsrc, int32_t checkpts, double* C, int64_t* A, mpfmt_sssp_info* info)
 {
     if (!ctx) return MPFMT_ERR_ARG;
     if (nsrc < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "nsrc < 0");
     if (nsrc > 0 && (!sources || !C)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "sources / C is NULL");
     int32_t rc;
-    if ((rc = sssp_ready(ctx))) return rc;
-    if (checkpts && !ctx->have_boxes && ctx->cc_kind == 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "checkpts needs an obstacle set");
-    if ((rc = check_idx(ctx, sources, nsrc, "sources"))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (checkpts && nsrc > 0 && (rc = sssp_resident_bitmap(ctx))) return rc;
+    const uint64_t* d_F = nullptr;
+    if ((rc = field_prelude(ctx, sources, nsrc, "sources", false, checkpts, nsrc > 0 ? &d_F : nullptr))) return rc;
     const int64_t N = ctx->N;
     for (int64_t q = 0; q < nsrc; ++q)
-        if ((rc = mpfmt_sssp_device(ctx, sources[q] - 1, checkpts ? ctx->sssp_F : nullptr, C + q * N, A ? A + q * N : nullptr, info ? info + q : nullptr)))
-            return rc;
+        if ((rc = mpfmt_sssp_device(ctx, sources[q] - 1, d_F, C + q * N, A ? A + q * N : nullptr, info ? info + q : nullptr))) return rc;
     return MPFMT_OK;
 }
 
@@ -1460,13 +1474,10 @@ int32_t mpfmt_graph_sssp_multi(mpfmt_ctx* ctx, const int64_t* sources, int64_t n
     if (nsrc < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "nsrc < 0");
     if (nsrc > 0 && (!sources || !C)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "sources / C is NULL");
     int32_t rc;
-    if ((rc = sssp_ready(ctx))) return rc;
-    if (checkpts && !ctx->have_boxes && ctx->cc_kind == 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "checkpts needs an obstacle set");
-    if ((rc = check_idx(ctx, sources, nsrc, "sources"))) return rc;
+    const uint64_t* d_F = nullptr;
+    if ((rc = field_prelude(ctx, sources, nsrc, "sources", false, checkpts, nsrc > 0 ? &d_F : nullptr))) return rc;
     if (nsrc == 0) return MPFMT_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (checkpts && (rc = sssp_resident_bitmap(ctx))) return rc;
-    return mpfmt_sssp_multi_device(ctx, sources, nsrc, checkpts ? ctx->sssp_F.get() : nullptr, C, A, info);
+    return mpfmt_sssp_multi_device(ctx, sources, nsrc, d_F, C, A, info);
 }
 
 // the cost-to-go field of a target set over whatever swept graph is resident (kernels_sssp_to.hip)
@@ -1476,12 +1487,9 @@ int32_t mpfmt_graph_sssp_to(mpfmt_ctx* ctx, const int64_t* targets, int64_t ntgt
     if (ntgt < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "ntgt < 0");
     if (!G || (ntgt > 0 && !targets)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "targets / G is NULL");
     int32_t rc;
-    if ((rc = sssp_ready(ctx))) return rc;
-    if (checkpts && !ctx->have_boxes && ctx->cc_kind == 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "checkpts needs an obstacle set");
-    if ((rc = check_idx(ctx, targets, ntgt, "targets"))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (checkpts && (rc = sssp_resident_bitmap(ctx))) return rc;
-    return mpfmt_sssp_to_device(ctx, targets, ntgt, checkpts ? ctx->sssp_F.get() : nullptr, G, S, info);
+    const uint64_t* d_F;
+    if ((rc = field_prelude(ctx, targets, ntgt, "targets", false, checkpts, &d_F))) return rc;
+    return mpfmt_sssp_to_device(ctx, targets, ntgt, d_F, G, S, info);
 }
 
 // ---- a tracked field: kept valid across in-place box edits (kernels_field.hip) -----------------------------------------------------------
@@ -1490,12 +1498,9 @@ int32_t mpfmt_field_begin(mpfmt_ctx* ctx, int64_t source, int32_t checkpts, mpfm
 {
     if (!ctx) return MPFMT_ERR_ARG;
     int32_t rc;
-    if ((rc = sssp_ready_euclid(ctx))) return rc;
-    if (checkpts && !ctx->have_boxes && ctx->cc_kind == 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "checkpts needs an obstacle set");
-    if ((rc = check_idx(ctx, &source, 1, "source"))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (checkpts && (rc = sssp_point_bitmap(ctx))) return rc;
-    return mpfmt_field_compute(ctx, source - 1, checkpts ? 1 : 0, checkpts ? ctx->sssp_F.get() : nullptr, info);
+    const uint64_t* d_F;
+    if ((rc = field_prelude(ctx, &source, 1, "source", true, checkpts, &d_F))) return rc;
+    return mpfmt_field_compute(ctx, source - 1, checkpts ? 1 : 0, d_F, info);
 }
 
 int32_t mpfmt_field_update(mpfmt_ctx* ctx, mpfmt_field_info* info)
@@ -1503,10 +1508,12 @@ int32_t mpfmt_field_update(mpfmt_ctx* ctx, mpfmt_field_info* info)
     if (!ctx) return MPFMT_ERR_ARG;
     if (!mpfmt_field_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked field (mpfmt_field_begin)");
     int32_t rc;
-    if ((rc = sssp_ready_euclid(ctx))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     const bool history = mpfmt_field_history(ctx);                       // no build and no whole sweep since the field was last valid
-    if (history && !ctx->fld_dirty_any) {                                 // nothing was flagged: the field stands
+    const bool stands = history && !ctx->fld_dirty_any;                   // nothing was flagged: the field stands, and no bitmap is needed
+    const int32_t checkpts = ctx->fld_checkpts;                           // (begun over an obstacle set, and a ctx never loses its set)
+    const uint64_t* d_F = nullptr;
+    if ((rc = field_prelude(ctx, nullptr, 0, nullptr, true, checkpts, stands ? nullptr : &d_F))) return rc;
+    if (stands) {
         ctx->fld_path = 1;
         ctx->fld_invalidated = ctx->fld_dirty_columns = ctx->fld_columns_read = ctx->fld_column_visits = ctx->fld_entries_read = 0;
         ctx->fld_rounds = ctx->fld_relax = 0;
@@ -1516,9 +1523,6 @@ int32_t mpfmt_field_update(mpfmt_ctx* ctx, mpfmt_field_info* info)
         }
         return MPFMT_OK;
     }
-    const int32_t checkpts = ctx->fld_checkpts;
-    if (checkpts && (rc = sssp_point_bitmap(ctx))) return rc;
-    const uint64_t* d_F = checkpts ? ctx->sssp_F.get() : nullptr;
     if (!history) return mpfmt_field_compute(ctx, ctx->fld_source0, checkpts, d_F, info);
     if ((rc = mpfmt_field_repair(ctx, d_F, info))) { mpfmt_field_drop_internal(ctx); return rc; }      // (a repair cut short leaves no field)
     return MPFMT_OK;
@@ -1557,28 +1561,11 @@ int32_t mpfmt_field_goal(mpfmt_ctx* ctx, int32_t goal_kind, const double* goal_p
     HIPCHK(ctx, hipMemcpyAsync(C.data(), ctx->fld_C, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(A.data(), ctx->fld_A, sizeof(int64_t) * (size_t)N, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    // goal node: the reached sample inside the goal region of lowest (C, index) (prmstar_impl)
+    // goal node: the reached sample inside the goal region of lowest (C, index)
     int64_t z = -1;
     for (int64_t i = 0; i < N; ++i)
         if (C[i] < INFINITY && (z < 0 || C[i] < C[z]) && mpfmt_is_goal_pt(&X[(size_t)i * d], d, goal_kind, goal_params)) z = i;
-    std::vector<int64_t> rev;
-    if (z >= 0) {
-        int64_t cur = z;
-        rev.push_back(cur + 1);
-        while (cur != init_idx - 1 && (int64_t)rev.size() <= N) {
-            const int64_t p = A[cur];
-            if (p == 0) break;
-            cur = p - 1;
-            rev.push_back(cur + 1);
-        }
-        res->status = 1; res->cost = C[z]; res->z = z + 1;
-    } else {
-        rev.push_back(init_idx);
-        res->status = 0; res->cost = INFINITY; res->z = init_idx;
-    }
-    for (size_t i = 0; i < rev.size() && i < (size_t)N; ++i) path[i] = rev[rev.size() - 1 - i];
-    res->path_len = (int64_t)std::min<size_t>(rev.size(), (size_t)N);
-    res->collision_checks = 0;
+    mpfmt_walk_back(N, C.data(), A.data(), init_idx, z, path, res);
     res->nnz = ctx->nnz;
     res->ms_host_loop = std::chrono::duration<double, std::milli>(now() - t0).count();
     return MPFMT_OK;
@@ -1914,24 +1901,7 @@ static int32_t prmstar_impl(mpfmt_ctx* ctx, double r, int64_t k, int64_t init_id
     int64_t z = -1;
     for (int64_t i = 0; i < N; ++i)
         if (C[i] < INFINITY && (z < 0 || C[i] < C[z]) && mpfmt_is_goal_pt(&X[(size_t)i * d], d, goal_kind, goal_params)) z = i;
-    std::vector<int64_t> rev;
-    if (z >= 0) {
-        int64_t cur = z;
-        rev.push_back(cur + 1);
-        while (cur != init_idx - 1 && (int64_t)rev.size() <= N) {
-            const int64_t p = A[cur];
-            if (p == 0) break;
-            cur = p - 1;
-            rev.push_back(cur + 1);
-        }
-        res->status = 1; res->cost = C[z]; res->z = z + 1;
-    } else {
-        rev.push_back(init_idx);
-        res->status = 0; res->cost = INFINITY; res->z = init_idx;
-    }
-    for (size_t i = 0; i < rev.size() && i < (size_t)N; ++i) path[i] = rev[rev.size() - 1 - i];
-    res->path_len = (int64_t)std::min<size_t>(rev.size(), (size_t)N);
-    res->collision_checks = 0;
+    mpfmt_walk_back(N, C, A, init_idx, z, path, res);
     t[5] = now();
     fmt_times(ctx, res, t);
     return MPFMT_OK;
@@ -2190,24 +2160,7 @@ static int32_t steer_prmstar(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double 
     int64_t z = -1;
     for (int64_t i = 0; i < N; ++i)
         if (C[i] < INFINITY && (z < 0 || C[i] < C[z]) && goal_hit(i)) z = i;
-    std::vector<int64_t> rev;
-    if (z >= 0) {
-        int64_t cur = z;
-        rev.push_back(cur + 1);
-        while (cur != init_idx - 1 && (int64_t)rev.size() <= N) {
-            const int64_t p = A[cur];
-            if (p == 0) break;
-            cur = p - 1;
-            rev.push_back(cur + 1);
-        }
-        res->status = 1; res->cost = C[z]; res->z = z + 1;
-    } else {
-        rev.push_back(init_idx);
-        res->status = 0; res->cost = INFINITY; res->z = init_idx;
-    }
-    for (size_t i = 0; i < rev.size() && i < (size_t)N; ++i) path[i] = rev[rev.size() - 1 - i];
-    res->path_len = (int64_t)std::min<size_t>(rev.size(), (size_t)N);
-    res->collision_checks = 0;
+    mpfmt_walk_back(N, C, A, init_idx, z, path, res);
     t[5] = now();
     fmt_times(ctx, res, t);
     return MPFMT_OK;

@@ -278,6 +278,30 @@ void mpfmt_directed_fmt_recursion(int64_t N, const int64_t* colptr_, const int32
     res->cost = C[z]; res->z = z + 1; res->collision_checks = count; res->path_len = (int64_t)rev.size(); res->nnz = nnz;
 }
 
+// The goal walk of the roadmap planners over a finished field: labels C, parents A (1-based, 0 = none), the source init_idx (1-based)
+// and the goal node z the caller picked (0-based; -1: no reached sample is a goal).  path = init_idx ... z + 1 by the parents, or
+// [init_idx] without a goal node.  A walk stops at the source, at a parent of 0, and after N hops whatever A holds: path has N slots.
+void mpfmt_walk_back(int64_t N, const double* C, const int64_t* A, int64_t init_idx, int64_t z, int64_t* path, mpfmt_fmt_result* res)
+{
+    std::vector<int64_t> rev;
+    if (z >= 0) {
+        int64_t cur = z;
+        rev.push_back(cur + 1);
+        while (cur != init_idx - 1 && (int64_t)rev.size() <= N) {
+            const int64_t p = A[cur];
+            if (p == 0) break;
+            cur = p - 1;
+            rev.push_back(cur + 1);
+        }
+        res->status = 1; res->cost = C[z]; res->z = z + 1;
+    } else {
+        rev.push_back(init_idx);
+        res->status = 0; res->cost = INFINITY; res->z = init_idx;
+    }
+    for (size_t i = 0; i < rev.size() && i < (size_t)N; ++i) path[i] = rev[rev.size() - 1 - i];
+    res->path_len = (int64_t)std::min<size_t>(rev.size(), (size_t)N);
+    res->collision_checks = 0;
+}
 
 // PRM* cost-to-come field over the free-edge graph (include/mpfmt.h, "roadmap queries"): a binary-heap Dijkstra from one source
 // over the device-native CSC.  Entry b of column x with row y is the edge y -> x, so the scan of a settled y needs its out-edges:

@@ -21,4 +21,7 @@ void mpfmt_directed_fmt_recursion(int64_t N, const int64_t* colptr, const int32_
                                   const uint8_t* nseg, const uint64_t* F, int64_t init_idx, const std::function<bool(int64_t)>& goal_hit,
                                   int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res, const mpfmt_csr_view* pre,
                                   const uint64_t* fwd_mask = nullptr);
+// the goal walk of the roadmap planners: path and status / cost / z / path_len / collision_checks of res from a finished field and the
+// chosen goal node z (0-based, -1 = none)
+void mpfmt_walk_back(int64_t N, const double* C, const int64_t* A, int64_t init_idx, int64_t z, int64_t* path, mpfmt_fmt_result* res);
 int64_t mpfmt_validate_csc(int64_t N, const int64_t* colptr, const int64_t* rowval, char* err, size_t errlen);

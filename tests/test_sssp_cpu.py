@@ -90,6 +90,7 @@ def toy(tmp_path_factory):
         buf = open(pout, "rb").read()
         assert np.frombuffer(buf, np.int32, 1)[0] == 0
         return np.frombuffer(buf, np.float64, N, 4).copy(), np.frombuffer(buf, np.int64, N, 4 + 8 * N).copy()
+    run.exe = exe
     return run
 
 
@@ -209,6 +210,14 @@ def test_duplicates_and_an_island(toy):
     assert C.tobytes() == want_C.tobytes() and np.array_equal(A, want_A)
     assert np.all(C[100:] == INF) and np.all(A[100:] == 0) and np.isfinite(C[:100]).sum() > 80
     assert check_tree(N, colptr, rowval, nzval, efree, C, A, 1)
+
+
+def test_goal_walk_cases_under_the_sanitizers(toy):
+    """mpfmt_walk_back (the goal walk of mpfmt_prmstar, the steering PRM* planners and mpfmt_field_goal) in the sanitizer-built caller,
+    N = 5: a goal three hops out; no goal node (path [init_idx], status 0, cost +Inf); a chain cut by a parent of 0; and a parent array
+    with a 2-cycle that never reaches the source -- the walk stops, path_len <= N, nothing is written past path[N-1]."""
+    p = subprocess.run([toy.exe, "walk"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "runtime error" not in p.stderr and "ERROR" not in p.stderr, p.stdout + p.stderr
 
 
 def test_host_graph_sssp_rejects_bad_arguments():
