@@ -401,6 +401,73 @@ MPFMT_API int32_t mpfmt_field_drop(mpfmt_ctx* ctx);
 MPFMT_API int32_t mpfmt_host_field_repair(int64_t N, const int64_t* colptr, const int32_t* rowval, const double* nzval, const uint64_t* efree,
                                 const uint64_t* F, const uint64_t* dirty, int64_t source, double* C, int64_t* A, int64_t* invalidated);
 
+/* ---- a cost-to-go field kept valid across box edits, on any resident swept graph.
+ *      Notation of the cost-to-go above: entry b of column x with row y is the edge y -> x; it is usable iff mask bit b is set and,
+ *      with checkpts, F[x] is set; G = 0 on the targets whatever their F; G* is the least fixed point; S[y] = the usable x of lowest
+ *      (G[x], x) among those with fl(G[x] + w_yx) == G[y].
+ *      A TRACKED COST-TO-GO FIELD is (targets, checkpts, G, S), held in buffers of its own that no other call writes: G and S are
+ *      exactly what mpfmt_graph_sssp_to returns for the targets.  It is admitted wherever mpfmt_graph_sssp_to is: r-disc, imported,
+ *      k-nearest, double integrator, Dubins, Reeds-Shepp; unsharded ctx, not the 2-D SAT world.
+ *      The REPAIR runs after any sequence of in-place box edits (mpfmt_boxes_add / _remove, mixed):
+ *        1. F is recomputed when checkpts is set (on a steering graph: the bitmap of the steering planners).
+ *        2. Invalidate.  I0 = the non-target y with G[y] < Inf whose successor edge y -> S[y] is no longer usable: its mask bit is now
+ *           clear, or checkpts is set and F[S[y]] is clear.  I = I0 plus every y whose successor chain passes through I0; G = +Inf on
+ *           I.  (Only a y whose S[y] is a flagged column or has lost its point bit is looked at for this; the entry of the edge is
+ *           found by binary search of y in the ascending column S[y].)
+ *           I0 also takes every non-target y with G[y] < Inf whose successor chain S[y], S[S[y]], ... stays at the label of y for
+ *           MPFMT_TOGO_EQUAL_HOPS = 64 hops without arriving at a target.  Where a group of equal-cost samples hangs together by
+ *           zero-length or absorbed edges only (the case excluded above for walks along S) the successors may run in a circle, and
+ *           no chain then shows what supports the group's labels; such a y loses its label at every repair that runs and gets it
+ *           back from the push.  A chain of more than 64 legitimate equal-label hops is treated the same way: more work, same result.
+ *           I is exactly the closure of this I0, and "togo_invalidated" reports |I|: it counts these samples too.
+ *        3. Seed.  The pushers of round 0 are a set P0 with
+ *             P0 >= {x : G[x] < Inf, (no checkpts or F[x]), x in D or column x has a row in I}  and  P0 <= D u Nout(I),
+ *           D = the columns the delta kernels flagged since the field was last valid, Nout(I) = the columns holding an entry whose
+ *           row is in I, usable or not.  On the library's own r-disc graph (rows of a column = its out-neighbours) the finite rows of
+ *           the columns of I are marked ("togo_seed_form" 0); on every other graph each finite, unmarked column scans its rows
+ *           against the bitmap of I (form 1: one pass over rowval).
+ *        4. Push.  The rounds of mpfmt_graph_sssp_to from P0 to a fixed point: fl(G[x] + w) offered to the rows of the columns whose
+ *           label changed, a plain load then a 64-bit atomic minimum on the label bits, F applied to the pushing x.
+ *        5. Successors from the final G alone, by the rule above: two whole passes over the reached columns.
+ *      With D and I both empty nothing runs: no rounds, no successor pass, the same bytes.
+ *      The result is byte-identical to a fresh mpfmt_graph_sssp_to over the edited mask (DESIGN.md 7j has the argument).
+ * mpfmt_togo_begin  : computes the field of the target set (1-based, duplicates allowed, ntgt = 0 legal) into the tracked buffers.
+ *      The refusals of mpfmt_graph_sssp_to; a refused call leaves an earlier tracked field as it was.  info->path = 0.
+ * mpfmt_togo_update : the repair, info->path = 1.  The delta history is valid while no graph build and no whole sweep (Euclidean or
+ *      steering) has happened since the field was last valid; otherwise, with a swept mask resident, the field is recomputed in full:
+ *      info->path = 0.  No swept mask for the resident graph and the current box set: MPFMT_ERR_STATE, the field stays tracked.
+ * mpfmt_togo_read   : host copies of G[N] and S[N] (S may be NULL, and so may G): the field as it was last valid.
+ * mpfmt_togo_drop   : forgets the field (always succeeds).
+ * The field is dropped by new samples, another graph (another radius, k, steering space or steering parameters; an import),
+ * mpfmt_upload_shapes2d, mpfmt_set_state_bounds, mpfmt_set_shard and by destroying the ctx: mpfmt_togo_update / _read then return
+ * MPFMT_ERR_STATE until mpfmt_togo_begin.  mpfmt_upload_boxes replaces the list whole: the labels lose their history but the targets
+ * stay, and after the whole sweep that such an upload needs mpfmt_togo_update recomputes (path = 0).  mpfmt_field_*,
+ * mpfmt_graph_sssp, mpfmt_graph_sssp_to and the roadmap queries keep buffers of their own and leave it alone; it and the tracked
+ * cost-to-come field may be live at once, each with its own dirty bitmap.
+ * mpfmt_get_stat: "togo_tracked", "togo_path" (1 repaired, 0 computed in full), "togo_seed_form", "togo_reached",
+ * "togo_invalidated" (|I|), "togo_dirty_columns" (|D|), "togo_columns_read" (distinct columns whose entries the push read, all
+ * rounds), "togo_column_visits" (the same counted once per round), "togo_entries_read", "togo_rounds", "togo_relaxations",
+ * "togo_atomics".  Timers: "togo_invalidate", "togo_seed", "togo_push", "togo_successors". */
+#define MPFMT_TOGO_EQUAL_HOPS 64
+typedef struct {
+    int64_t reached;           /* samples with G < +Inf, the targets included */
+    int64_t invalidated;       /* |I| */
+    int64_t dirty_columns;     /* |D| */
+    int64_t columns_read;      /* distinct columns whose entries the push read */
+    int64_t column_visits;     /* columns read, counted once per round */
+    int64_t entries_read;      /* entries of the columns read, counted once per round */
+    int64_t rounds;            /* push rounds that ran */
+    int64_t relaxations;       /* fl(G[x] + w) evaluated; scheduling-dependent */
+    int64_t atomics;           /* atomic minima issued; scheduling-dependent */
+    double  ms_device;         /* device time of the call */
+    int32_t path;              /* 1 repaired, 0 computed in full */
+    int32_t pad_;
+} mpfmt_togo_info;
+MPFMT_API int32_t mpfmt_togo_begin(mpfmt_ctx* ctx, const int64_t* targets, int64_t ntgt, int32_t checkpts, mpfmt_togo_info* info);
+MPFMT_API int32_t mpfmt_togo_update(mpfmt_ctx* ctx, mpfmt_togo_info* info);
+MPFMT_API int32_t mpfmt_togo_read(mpfmt_ctx* ctx, double* G, int64_t* S);
+MPFMT_API int32_t mpfmt_togo_drop(mpfmt_ctx* ctx);
+
 /* ---- roadmap queries for external states: start and goal states that are NOT samples (the robot's present pose, a batch of candidate
  *      goals) are attached to the resident roadmap instead of being appended to the sample set (which would rebuild graph and mask).
  *      The ctx holds an unsharded, swept r-disc graph of radius r = its graph radius (built or imported); the checker is the N-D AABB

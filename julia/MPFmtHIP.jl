@@ -323,6 +323,39 @@ function hip_replan!(P::MPProblem)
     P.status, P.solution.cost, P.solution.elapsed
 end
 
+# ---- a cost-to-go policy kept valid across box edits, on any resident swept graph (include/mpfmt.h; r-disc, k-nearest, double
+#      integrator, Dubins, Reeds-Shepp): hip_graph_sssp_to computes the policy and throws it away; hip_togo_begin! keeps it in the ctx,
+#      and after mpfmt_boxes_add / _remove hip_togo_update! repairs it -- the robot has left init: what it needs again after every edit
+#      is the policy towards the fixed goal from wherever it stands.  The C caller that executes these calls with the same widths is
+#      tests/abi_c/abi_caller11.c. ----
+const sym_togo_begin = :mpfmt_togo_begin
+const sym_togo_update = :mpfmt_togo_update
+const sym_togo_read = :mpfmt_togo_read
+const sym_togo_drop = :mpfmt_togo_drop
+immutable TogoInfo
+    reached::Int64; invalidated::Int64; dirty_columns::Int64; columns_read::Int64; column_visits::Int64; entries_read::Int64
+    rounds::Int64; relaxations::Int64; atomics::Int64; ms_device::Float64; path::Int32; pad::Int32
+end
+function hip_togo_begin!(DS::HIPDistanceDS, targets::Vector{Int}; checkpts = true)
+    info = Ref{TogoInfo}()
+    chk(DS.ctx, ccall((sym_togo_begin, libmpfmt), Int32, (Ptr{Void}, Ptr{Int64}, Int64, Int32, Ptr{TogoInfo}),
+                      DS.ctx, targets, length(targets), checkpts, info))
+    info[]
+end
+# after the box edits: repair (info.path == 1) or, where an edit could not be applied in place and the mask was swept whole, recompute (0)
+function hip_togo_update!(DS::HIPDistanceDS)
+    info = Ref{TogoInfo}()
+    chk(DS.ctx, ccall((sym_togo_update, libmpfmt), Int32, (Ptr{Void}, Ptr{TogoInfo}), DS.ctx, info))
+    info[]
+end
+# G[i] = Inf: no target reachable from sample i; S[i] = the next sample on the way, 0: target or unreached
+function hip_togo_read(DS::HIPDistanceDS, N::Int)
+    G = Vector{Float64}(N); S = Vector{Int}(N)
+    chk(DS.ctx, ccall((sym_togo_read, libmpfmt), Int32, (Ptr{Void}, Ptr{Float64}, Ptr{Int64}), DS.ctx, G, S))
+    G, S
+end
+hip_togo_drop!(DS::HIPDistanceDS) = chk(DS.ctx, ccall((sym_togo_drop, libmpfmt), Int32, (Ptr{Void},), DS.ctx))
+
 # ---- post-processing: adaptive_shortcut!(P, iterations) (src/postprocessors.jl:41-50) on the device; the checker of P.V.DS.ctx is the
 #      one the last upload bound (hip_bind! / the planner calls).  max_states bounds the working path (include/mpfmt.h).
 const sym_adaptive_shortcut = :mpfmt_adaptive_shortcut

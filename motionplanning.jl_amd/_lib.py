@@ -51,6 +51,12 @@ class FieldInfo(C.Structure):
                 ("ms_device", C.c_double), ("path", C.c_int32), ("pad_", C.c_int32)]
 
 
+class TogoInfo(C.Structure):
+    _fields_ = [("reached", C.c_int64), ("invalidated", C.c_int64), ("dirty_columns", C.c_int64), ("columns_read", C.c_int64),
+                ("column_visits", C.c_int64), ("entries_read", C.c_int64), ("rounds", C.c_int64), ("relaxations", C.c_int64),
+                ("atomics", C.c_int64), ("ms_device", C.c_double), ("path", C.c_int32), ("pad_", C.c_int32)]
+
+
 class ShortcutInfo(C.Structure):
     _fields_ = [("status", C.c_int32), ("iterations_done", C.c_int32), ("n_out", C.c_int64), ("max_working_len", C.c_int64),
                 ("max_halvings", C.c_int64), ("collision_checks", C.c_int64), ("tests_evaluated", C.c_int64)]
@@ -123,6 +129,10 @@ SYMBOLS = [
     ("mpfmt_field_read", C.c_int32, [C.c_void_p, c_d_p, c_i64_p]),
     ("mpfmt_field_goal", C.c_int32, [C.c_void_p, C.c_int32, c_d_p, c_i64_p, C.POINTER(FmtResult)]),
     ("mpfmt_field_drop", C.c_int32, [C.c_void_p]),
+    ("mpfmt_togo_begin", C.c_int32, [C.c_void_p, c_i64_p, C.c_int64, C.c_int32, C.POINTER(TogoInfo)]),
+    ("mpfmt_togo_update", C.c_int32, [C.c_void_p, C.POINTER(TogoInfo)]),
+    ("mpfmt_togo_read", C.c_int32, [C.c_void_p, c_d_p, c_i64_p]),
+    ("mpfmt_togo_drop", C.c_int32, [C.c_void_p]),
     ("mpfmt_host_field_repair", C.c_int32, [C.c_int64, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p, c_u64_p, C.c_int64, c_d_p, c_i64_p,
                                             c_i64_p]),
     ("mpfmt_prmstar", C.c_int32, [C.c_void_p, C.c_double, C.c_int64, C.c_int32, C.c_int32, c_d_p, c_i64_p, c_d_p, c_i64_p,
@@ -393,6 +403,10 @@ def host_field_repair(colptr0, rowval0, nzval, efree, F, dirty, C_old, A_old, so
 
 def _field_info(i):
     return {k: getattr(i, k) for k, _ in FieldInfo._fields_ if k != "pad_"}
+
+
+def _togo_info(i):
+    return {k: getattr(i, k) for k, _ in TogoInfo._fields_ if k != "pad_"}
 
 
 def _roadmap_info(i):
@@ -798,6 +812,34 @@ class Context:
     def host_field_repair(colptr0, rowval0, nzval, efree, F, dirty, C_old, A_old, source=1):
         """The module's host_field_repair (no device)."""
         return host_field_repair(colptr0, rowval0, nzval, efree, F, dirty, C_old, A_old, source=source)
+
+    # ---- a cost-to-go field kept valid across box edits, on any resident swept graph (include/mpfmt.h) -------------------------
+    def togo_begin(self, targets, checkpts=True):
+        """Compute the cost-to-go field of the 1-based `targets` over whatever swept graph is resident into buffers the context keeps
+        (mpfmt_togo_begin); returns the info dict (reached, invalidated, dirty_columns, columns_read, column_visits, entries_read,
+        rounds, relaxations, atomics, ms_device, path)."""
+        tg = np.ascontiguousarray(np.atleast_1d(np.asarray(targets, dtype=np.int64)))
+        info = TogoInfo()
+        self._chk(self._L.mpfmt_togo_begin(self._h, _ip(tg) if tg.size else None, int(tg.size), int(bool(checkpts)), C.byref(info)))
+        return _togo_info(info)
+
+    def togo_update(self):
+        """Repair the tracked cost-to-go field after boxes_add / boxes_remove (mpfmt_togo_update): info["path"] = 1 repaired,
+        0 recomputed."""
+        info = TogoInfo()
+        self._chk(self._L.mpfmt_togo_update(self._h, C.byref(info)))
+        return _togo_info(info)
+
+    def togo_read(self, want_successors=True):
+        """Host copies (G, S) of the tracked cost-to-go field: G = +Inf where no target is reachable, S 1-based successors, 0 for
+        targets and unreached samples (None without want_successors)."""
+        G = np.empty(max(self.N, 1), dtype=np.float64)
+        S = np.empty(max(self.N, 1), dtype=np.int64) if want_successors else None
+        self._chk(self._L.mpfmt_togo_read(self._h, _dp(G), _ip(S)))
+        return G[:self.N], (None if S is None else S[:self.N])
+
+    def togo_drop(self):
+        self._chk(self._L.mpfmt_togo_drop(self._h))
 
     # ---- roadmap queries for states that are not samples (include/mpfmt.h, "roadmap queries for external states") ----------
     def _states(self, Q):

@@ -746,7 +746,7 @@ int32_t mpfmt_car_build(mpfmt_ctx* ctx, mpfmt_steer kind, double rt, double sp, 
     ctx->pairs_tested = cnnz;
     ctx->car_rt = rt; ctx->car_sp = sp; ctx->steer_r = r;
     ctx->steer_kind = kind;
-    ctx->steer_counted = ctx->steer_filled = true; ctx->steer_swept = false;
+    ctx->steer_counted = ctx->steer_filled = true; ctx->steer_swept = false; ctx->steer_epoch += 1;
     ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
     return MPFMT_OK;
 }
@@ -776,7 +776,7 @@ int32_t mpfmt_car_sweep(mpfmt_ctx* ctx)
         HIPCHK(ctx, hipGetLastError());
     }
     tm2.end("car_sweep");
-    ctx->steer_swept = true;
+    ctx->steer_swept = true; ctx->steer_sweep_epoch += 1;
     return MPFMT_OK;
 }
 

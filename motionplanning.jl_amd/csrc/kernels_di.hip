@@ -617,7 +617,7 @@ int32_t mpfmt_di_fill(mpfmt_ctx* ctx)
         HIPCHK(ctx, hipGetLastError());
         tm2.end("di_fill");
     }
-    ctx->steer_filled = true;
+    ctx->steer_filled = true; ctx->steer_epoch += 1;
     return MPFMT_OK;
 }
 
@@ -648,7 +648,7 @@ int32_t mpfmt_di_sweep(mpfmt_ctx* ctx)
         HIPCHK(ctx, hipGetLastError());
         tm3.end("di_sweep");
     }
-    ctx->steer_swept = true;
+    ctx->steer_swept = true; ctx->steer_sweep_epoch += 1;
     return MPFMT_OK;
 }
 

@@ -236,13 +236,22 @@ int32_t mpfmt_field_compute(mpfmt_ctx* ctx, int64_t source0, int32_t checkpts, c
     return MPFMT_OK;
 }
 
-int32_t mpfmt_field_mark_dirty(mpfmt_ctx* ctx)
+// the flagged columns of the last delta call, ctx->bd_cols[0 .. bd_columns), ORed into the dirty bitmap D (N bits) on ctx->stream: each
+// tracked field passes its own
+int32_t mpfmt_dirty_columns_into(mpfmt_ctx* ctx, unsigned long long* D)
 {
     const int64_t n = ctx->bd_columns;
-    if (!ctx->fld_tracked || n <= 0 || !ctx->fld_bm || ctx->fld_N != ctx->N) return MPFMT_OK;
-    hipLaunchKernelGGL(k_field_dirty, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->bd_cols, n, ctx->N,
-                       (unsigned long long*)ctx->fld_bm.get());
+    if (n <= 0) return MPFMT_OK;
+    hipLaunchKernelGGL(k_field_dirty, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->bd_cols, n, ctx->N, D);
     HIPCHK(ctx, hipGetLastError());
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_field_mark_dirty(mpfmt_ctx* ctx)
+{
+    if (!ctx->fld_tracked || ctx->bd_columns <= 0 || !ctx->fld_bm || ctx->fld_N != ctx->N) return MPFMT_OK;
+    const int32_t rc = mpfmt_dirty_columns_into(ctx, (unsigned long long*)ctx->fld_bm.get());
+    if (rc) return rc;
     ctx->fld_dirty_any = true;
     return MPFMT_OK;
 }

@@ -106,6 +106,7 @@ int32_t mpfmt_upload_shapes2d(mpfmt_ctx* ctx, int32_t n_shapes, const int32_t* k
     if (ss_lo) for (int i = 0; i < 2; ++i) { ctx->ss.lo[i] = ss_lo[i]; ctx->ss.hi[i] = ss_hi[i]; }
     ctx->graph_swept = false;
     mpfmt_field_drop_internal(ctx);
+    mpfmt_togo_drop_internal(ctx);
     return MPFMT_OK;
 }
 

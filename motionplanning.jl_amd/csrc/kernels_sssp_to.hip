@@ -62,45 +62,7 @@ __global__ __launch_bounds__(256) void k_sssp_to_push(int64_t N, int64_t words, 
     const ring_idx r = ring_at(round);
     const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
-    const uint64_t* bin;
-    unsigned long long* bout;
-    if (!ring_round(st->slot, &st->rounds, bm, words, r, gtid, nthreads, bin, bout)) return;
-    unsigned long long* Gb = (unsigned long long*)G;
-    const int lane = threadIdx.x & 63;
-    const int64_t nwaves = nthreads >> 6;
-    unsigned long long nrel = 0, natom = 0, nchg = 0, nent = 0, ncol = 0;
-    for (int64_t u = gtid >> 6; u < 4 * words; u += nwaves) {
-        const int64_t w = u >> 2;
-        const int sh = (int)(u & 3) * 16;
-        uint64_t word = bin[w];
-        if (F) word &= F[w];
-        unsigned bits = __builtin_amdgcn_readfirstlane((unsigned)((word >> sh) & 0xffffull));        // (the same in every lane: say so)
-        while (bits) {
-            const int64_t x = w * 64 + sh + __builtin_ctz(bits);
-            bits &= bits - 1;
-            const double gx = G[x];
-            const int64_t b0 = colptr[x], b1 = colptr[x + 1];
-            if (lane == 0) { ++ncol; nent += (unsigned long long)(b1 - b0); }
-            for (int64_t b = b0 + lane; b < b1; b += 64) {
-                if (!bit_of(efree, b)) continue;
-                const int32_t y = rowval[b];
-                const double cand = gx + nzval[b];
-                ++nrel;
-                if (!(cand < G[y])) continue;
-                const unsigned long long cb = label_bits(cand);
-                const unsigned long long old = atomicMin(&Gb[y], cb);
-                ++natom;
-                if (old > cb) { atomicOr(&bout[y >> 6], 1ull << (y & 63)); ++nchg; }
-            }
-        }
-    }
-    nrel = wave_sum(nrel); natom = wave_sum(natom); nchg = wave_sum(nchg);
-    if (lane == 0) {
-        if (nrel) atomicAdd(&st->relax, nrel);
-        if (natom) atomicAdd(&st->atomics, natom);
-        if (nchg) atomicAdd(&st->slot[r.out].changed, nchg);
-        if (ncol) { atomicAdd(&st->columns, ncol); atomicAdd(&st->entries, nent); }
-    }
+    push_body(words, colptr, rowval, nzval, efree, F, G, bm, st->slot, &st->rounds, &st->relax, &st->atomics, &st->entries, &st->columns, r, gtid, nthreads);
 }
 
 __global__ __launch_bounds__(256) void k_sssp_to_succ_init(int64_t N, unsigned long long* __restrict__ best, unsigned long long* __restrict__ S)
@@ -147,6 +109,21 @@ __global__ __launch_bounds__(256) void k_sssp_to_finish(int64_t N, const double*
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&st->reached, (unsigned long long)__popcll(m));
 }
 
+// The successor passes over a finished G on ctx->stream, for the one-shot field and for the tracked one (kernels_togo.hip): bm is four
+// bitmaps of ceil(N / 64) words, the fourth the targets; best [N] is scratch; S [N] is left with ~0 where no successor was found.
+void mpfmt_sssp_to_launch_successors(mpfmt_ctx* ctx, const uint64_t* d_F, const double* G, const uint64_t* bm, unsigned long long* best,
+                                     unsigned long long* S)
+{
+    const int64_t N = ctx->N, words = (N + 63) / 64;
+    const unsigned nb_cols = relax_wave_blocks(ctx, N);                      // one wavefront per column
+    const unsigned nb_n = (unsigned)((std::max<int64_t>(N, 1) + 255) / 256);
+    hipLaunchKernelGGL(k_sssp_to_succ_init, dim3(nb_n), dim3(256), 0, ctx->stream, N, best, S);
+    hipLaunchKernelGGL(k_sssp_to_succ<1>, dim3(nb_cols), dim3(256), 0, ctx->stream, N, words, ctx->colptr, ctx->rowval, ctx->nzval,
+                       ctx->graph_free, d_F, G, bm, best, S);
+    hipLaunchKernelGGL(k_sssp_to_succ<2>, dim3(nb_cols), dim3(256), 0, ctx->stream, N, words, ctx->colptr, ctx->rowval, ctx->nzval,
+                       ctx->graph_free, d_F, G, bm, best, S);
+}
+
 // targets1: 1-based, on the host, validated by the caller; G_host [N]; S_host [N] or nullptr (then the successor passes do not run)
 int32_t mpfmt_sssp_to_device(mpfmt_ctx* ctx, const int64_t* targets1, int64_t ntgt, const uint64_t* d_F, double* G_host, int64_t* S_host,
                              mpfmt_sssp_info* info)
@@ -167,7 +144,6 @@ int32_t mpfmt_sssp_to_device(mpfmt_ctx* ctx, const int64_t* targets1, int64_t nt
     unsigned long long* S = (unsigned long long*)ctx->sssp_A.get();
     // one wavefront per quarter word of the changed-sample bitmap, grid-stride
     const unsigned nb = relax_wave_blocks(ctx, 4 * words);
-    const unsigned nb_cols = relax_wave_blocks(ctx, N);                      // the successor passes: one wavefront per column
     const unsigned nb_init = (unsigned)((std::max<int64_t>(N, 4 * words) + 255) / 256);
     const unsigned nb_n = (unsigned)((N + 255) / 256);
     if (ntgt > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->sssp_to_tgt, targets1, sizeof(int64_t) * (size_t)ntgt, hipMemcpyHostToDevice, ctx->stream));
@@ -187,13 +163,7 @@ int32_t mpfmt_sssp_to_device(mpfmt_ctx* ctx, const int64_t* targets1, int64_t nt
     }
     {
         mpfmt_timed tm(ctx);
-        if (S_host) {
-            hipLaunchKernelGGL(k_sssp_to_succ_init, dim3(nb_n), dim3(256), 0, ctx->stream, N, ctx->sssp_to_best.get(), S);
-            hipLaunchKernelGGL(k_sssp_to_succ<1>, dim3(nb_cols), dim3(256), 0, ctx->stream, N, words, ctx->colptr, ctx->rowval, ctx->nzval,
-                               ctx->graph_free, d_F, G, ctx->sssp_bm, ctx->sssp_to_best.get(), S);
-            hipLaunchKernelGGL(k_sssp_to_succ<2>, dim3(nb_cols), dim3(256), 0, ctx->stream, N, words, ctx->colptr, ctx->rowval, ctx->nzval,
-                               ctx->graph_free, d_F, G, ctx->sssp_bm, ctx->sssp_to_best.get(), S);
-        }
+        if (S_host) mpfmt_sssp_to_launch_successors(ctx, d_F, G, ctx->sssp_bm, ctx->sssp_to_best.get(), S);
         hipLaunchKernelGGL(k_sssp_to_finish, dim3(nb_n), dim3(256), 0, ctx->stream, N, G, S, S_host ? 1 : 0, st);
         tm.end("sssp_to_successors");
     }

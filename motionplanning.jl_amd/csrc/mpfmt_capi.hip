@@ -232,6 +232,7 @@ int32_t mpfmt_set_shard(mpfmt_ctx* ctx, int32_t rank, int32_t world)
     if (world < 1 || rank < 0 || rank >= world) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "bad shard %d of %d", rank, world);
     ctx->rank = rank; ctx->world = world;
     mpfmt_field_drop_internal(ctx);
+    mpfmt_togo_drop_internal(ctx);
     ctx->deg_zero_valid = false;
     ctx->grid_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0;      // (the cell order and the built part of the index belong to the shard)
     ctx->graph_r = -1.0; ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
@@ -323,6 +324,7 @@ static int32_t adopt_samples(mpfmt_ctx* ctx, const double* src, bool src_on_host
     ctx->Xo.swap(ctx->Xo_next);
     ctx->samples_epoch += 1;
     mpfmt_field_drop_internal(ctx);
+    mpfmt_togo_drop_internal(ctx);
     ctx->grid_r = -1.0; ctx->graph_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0;
     ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
     ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
@@ -365,6 +367,7 @@ int32_t mpfmt_set_state_bounds(mpfmt_ctx* ctx, const double* ss_lo, const double
     if (ss_lo) for (int i = 0; i < d_state; ++i) { ctx->ss.lo[i] = ss_lo[i]; ctx->ss.hi[i] = ss_hi[i]; }
     ctx->graph_swept = false; ctx->steer_swept = false; ctx->pend_valid = false;     // (a pending list belongs to the obstacle set it was made against)
     mpfmt_field_drop_internal(ctx);
+    mpfmt_togo_drop_internal(ctx);
     return MPFMT_OK;
 }
 
@@ -443,14 +446,16 @@ static int32_t boxes_delta_finish(mpfmt_ctx* ctx, const double* d_delta, int32_t
         ctx->graph_swept = false;
         const int32_t rc = steer_delta_apply(ctx, d_delta, nd, remove);
         if (rc) { ctx->steer_swept = false; ctx->bd_path = 0; return rc; }   // (the list stands, the mask is swept again)
-        return MPFMT_OK;
+        return mpfmt_togo_mark_dirty(ctx);                   // (a tracked cost-to-go field learns which columns the edit read)
     }
     ctx->steer_swept = false;
     ctx->bd_path = boxes_delta_in_place(ctx) ? 1 : 0;
     if (!ctx->bd_path) { ctx->graph_swept = false; return MPFMT_OK; }
     const int32_t rc = mpfmt_boxdelta_apply(ctx, d_delta, nd, remove);
     if (rc) { ctx->graph_swept = false; ctx->bd_path = 0; return rc; }   // (the list stands, the mask is swept again)
-    return mpfmt_field_mark_dirty(ctx);                      // (a tracked field learns which columns the edit read)
+    const int32_t rf = mpfmt_field_mark_dirty(ctx);          // (a tracked field learns which columns the edit read:
+    if (rf) return rf;                                       //  each of the two has a dirty bitmap of its own)
+    return mpfmt_togo_mark_dirty(ctx);
 }
 
 int32_t mpfmt_boxes_add(mpfmt_ctx* ctx, const double* lohi, int32_t M_add)
@@ -655,6 +660,7 @@ int32_t mpfmt_graph_import(mpfmt_ctx* ctx, double r, const int64_t* colptr, cons
     ctx->graph_counted = ctx->graph_filled = true; ctx->knn_k = 0;
     ctx->graph_epoch += 1; ctx->graph_imported = true;
     mpfmt_field_drop_internal(ctx);
+    mpfmt_togo_drop_internal(ctx);
     ctx->graph_swept = false; ctx->pend_valid = false;
     ctx->pool_valid = false;
     ctx->rowpos_valid = false;
@@ -1404,8 +1410,9 @@ static int32_t sssp_ready(mpfmt_ctx* ctx)
     return MPFMT_OK;
 }
 
-// what the tracked fields and the external-state queries ask: a Euclidean graph (the steering delta kernels flag no dirty columns for a
-// tracked field, and an external state would need a steer to a non-sample)
+// what the tracked cost-to-come field and the external-state queries ask: a Euclidean graph (the repair of kernels_field.hip rests on
+// the Euclidean graph state, and an external state would need a steer to a non-sample; the tracked cost-to-go field of kernels_togo.hip
+// asks sssp_ready alone)
 static int32_t sssp_ready_euclid(mpfmt_ctx* ctx)
 {
     if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "roadmap queries run on an unsharded ctx");
@@ -1575,6 +1582,63 @@ int32_t mpfmt_field_drop(mpfmt_ctx* ctx)
 {
     if (!ctx) return MPFMT_ERR_ARG;
     mpfmt_field_drop_internal(ctx);
+    return MPFMT_OK;
+}
+
+// ---- a tracked cost-to-go field: kept valid across in-place box edits on any resident swept graph (kernels_togo.hip) -----------------------
+
+int32_t mpfmt_togo_begin(mpfmt_ctx* ctx, const int64_t* targets, int64_t ntgt, int32_t checkpts, mpfmt_togo_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (ntgt < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "ntgt < 0");
+    if (ntgt > 0 && !targets) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "targets is NULL");
+    int32_t rc;
+    const uint64_t* d_F;
+    if ((rc = field_prelude(ctx, targets, ntgt, "targets", false, checkpts, &d_F))) return rc;
+    return mpfmt_togo_compute(ctx, targets, ntgt, checkpts ? 1 : 0, d_F, info);
+}
+
+int32_t mpfmt_togo_update(mpfmt_ctx* ctx, mpfmt_togo_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!mpfmt_togo_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked cost-to-go field (mpfmt_togo_begin)");
+    int32_t rc;
+    const bool history = mpfmt_togo_history(ctx);                        // no build and no whole sweep since the field was last valid
+    const bool stands = history && !ctx->tg_dirty_any;                    // nothing was flagged: the field stands, and no bitmap is needed
+    const int32_t checkpts = ctx->tg_checkpts;                            // (begun over an obstacle set, and a ctx never loses its set)
+    const uint64_t* d_F = nullptr;
+    if ((rc = field_prelude(ctx, nullptr, 0, nullptr, false, checkpts, stands ? nullptr : &d_F))) return rc;
+    if (stands) {
+        ctx->tg_path = 1;
+        ctx->tg_invalidated = ctx->tg_dirty_columns = ctx->tg_columns_read = ctx->tg_column_visits = ctx->tg_entries_read = 0;
+        ctx->tg_rounds = ctx->tg_relax = ctx->tg_atomics = 0;
+        if (info) {
+            memset(info, 0, sizeof *info);
+            info->reached = ctx->tg_reached; info->path = 1;
+        }
+        return MPFMT_OK;
+    }
+    if (!history) return mpfmt_togo_compute(ctx, ctx->tg_targets.data(), (int64_t)ctx->tg_targets.size(), checkpts, d_F, info);
+    if ((rc = mpfmt_togo_repair(ctx, d_F, info))) { mpfmt_togo_drop_internal(ctx); return rc; }      // (a repair cut short leaves no field)
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_togo_read(mpfmt_ctx* ctx, double* G, int64_t* S)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!mpfmt_togo_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked cost-to-go field (mpfmt_togo_begin)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t N = (size_t)ctx->N;
+    if (G) HIPCHK(ctx, hipMemcpyAsync(G, ctx->tg_G, sizeof(double) * N, hipMemcpyDeviceToHost, ctx->stream));
+    if (S) HIPCHK(ctx, hipMemcpyAsync(S, ctx->tg_S, sizeof(int64_t) * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_togo_drop(mpfmt_ctx* ctx)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    mpfmt_togo_drop_internal(ctx);
     return MPFMT_OK;
 }
 
@@ -2538,6 +2602,18 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "boxes_delta_path") == 0) { *value = ctx->bd_path; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_columns") == 0) { *value = ctx->bd_columns; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_entries") == 0) { *value = ctx->bd_entries; return MPFMT_OK; }
+    if (strcmp(name, "togo_tracked") == 0) { *value = mpfmt_togo_live(ctx) ? 1 : 0; return MPFMT_OK; }
+    if (strcmp(name, "togo_path") == 0) { *value = ctx->tg_path; return MPFMT_OK; }
+    if (strcmp(name, "togo_seed_form") == 0) { *value = ctx->tg_seed_form; return MPFMT_OK; }
+    if (strcmp(name, "togo_reached") == 0) { *value = ctx->tg_reached; return MPFMT_OK; }
+    if (strcmp(name, "togo_invalidated") == 0) { *value = ctx->tg_invalidated; return MPFMT_OK; }
+    if (strcmp(name, "togo_dirty_columns") == 0) { *value = ctx->tg_dirty_columns; return MPFMT_OK; }
+    if (strcmp(name, "togo_columns_read") == 0) { *value = ctx->tg_columns_read; return MPFMT_OK; }
+    if (strcmp(name, "togo_column_visits") == 0) { *value = ctx->tg_column_visits; return MPFMT_OK; }
+    if (strcmp(name, "togo_entries_read") == 0) { *value = ctx->tg_entries_read; return MPFMT_OK; }
+    if (strcmp(name, "togo_rounds") == 0) { *value = ctx->tg_rounds; return MPFMT_OK; }
+    if (strcmp(name, "togo_relaxations") == 0) { *value = ctx->tg_relax; return MPFMT_OK; }
+    if (strcmp(name, "togo_atomics") == 0) { *value = ctx->tg_atomics; return MPFMT_OK; }
     if (strcmp(name, "field_tracked") == 0) { *value = mpfmt_field_live(ctx) ? 1 : 0; return MPFMT_OK; }
     if (strcmp(name, "field_update_path") == 0) { *value = ctx->fld_path; return MPFMT_OK; }
     if (strcmp(name, "field_invalidated") == 0) { *value = ctx->fld_invalidated; return MPFMT_OK; }

@@ -451,6 +451,29 @@ struct mpfmt_ctx {
     int32_t fld_path = 0;
     int64_t fld_invalidated = 0, fld_dirty_columns = 0, fld_columns_read = 0, fld_column_visits = 0, fld_entries_read = 0, fld_rounds = 0,
             fld_relax = 0, fld_reached = 0;
+
+    // ---- tracked cost-to-go field (kernels_togo.hip): buffers of its own that no other call writes, on any resident swept graph ----
+    // steer_epoch counts the builds of a steering graph (bumped wherever steer_filled becomes true), steer_sweep_epoch its whole sweeps
+    // (wherever steer_swept becomes true): what graph_epoch / sweep_epoch are to the Euclidean graph state
+    int64_t steer_epoch = 0, steer_sweep_epoch = 0;
+    mpfmt_dbuf<double> tg_G;              // [N] labels
+    mpfmt_dbuf<unsigned long long> tg_S;  // [N] 1-based successors (0: targets, unreached samples)
+    mpfmt_dbuf<unsigned long long> tg_best;      // [N] successor pass 1
+    mpfmt_dbuf<uint64_t> tg_bm;           // [7][ceil(N/64)]: the ring of three | targets | dirty columns | invalidated | columns read
+    mpfmt_dbuf<int64_t> tg_tgt;           // [ntgt] 1-based targets
+    mpfmt_dbuf<void> tg_state;            // togo_state (device) and its pinned host mirror
+    mpfmt_hbuf<void> tg_state_host;
+    std::vector<int64_t> tg_targets;     // the targets on the host (a recomputation starts from them)
+    bool tg_tracked = false, tg_steer = false;
+    int32_t tg_checkpts = 0;
+    int64_t tg_samples_epoch = -1, tg_build_epoch = -1, tg_sweep_epoch = -1, tg_N = 0, tg_knn_k = 0;
+    double tg_graph_r = -1.0, tg_steer_a = 0.0, tg_steer_b = 0.0;      // the graph's identity: radius (or k), steering parameters
+    mpfmt_steer tg_steer_kind = MPFMT_STEER_DI;
+    bool tg_dirty_any = false;           // a delta call has flagged columns since the field was last valid
+    // stats of the last mpfmt_togo_begin / _update
+    int32_t tg_path = 0, tg_seed_form = 0;
+    int64_t tg_invalidated = 0, tg_dirty_columns = 0, tg_columns_read = 0, tg_column_visits = 0, tg_entries_read = 0, tg_rounds = 0,
+            tg_relax = 0, tg_atomics = 0, tg_reached = 0;
 };
 
 // error helpers ---------------------------------------------------------------------------------
@@ -597,15 +620,25 @@ int32_t mpfmt_sssp_device(mpfmt_ctx* ctx, int64_t source0, const uint64_t* d_F, 
 void mpfmt_sssp_free(mpfmt_ctx* ctx);
 // kernels_sssp_to.hip: the cost-to-go field of a target set (1-based, on the host, validated) over the resident graph and mask; G_host [N],
 // S_host [N] or nullptr (no successor passes); labels and successors also stay in ctx->sssp_C / sssp_A
+void mpfmt_sssp_to_launch_successors(mpfmt_ctx* ctx, const uint64_t* d_F, const double* G, const uint64_t* bm, unsigned long long* best,
+                                     unsigned long long* S);      // the successor passes of the cost-to-go, on ctx->stream
 int32_t mpfmt_sssp_to_device(mpfmt_ctx* ctx, const int64_t* targets1, int64_t ntgt, const uint64_t* d_F, double* G_host, int64_t* S_host,
                              mpfmt_sssp_info* info);
 // kernels_field.hip: the tracked field.  d_F: the point bitmap of the current obstacle set or nullptr (checkpts = false)
 int32_t mpfmt_field_compute(mpfmt_ctx* ctx, int64_t source0, int32_t checkpts, const uint64_t* d_F, mpfmt_field_info* info);   // whole field into the tracked buffers
 int32_t mpfmt_field_repair(mpfmt_ctx* ctx, const uint64_t* d_F, mpfmt_field_info* info);                                       // steps 2-4 on the tracked buffers
+int32_t mpfmt_dirty_columns_into(mpfmt_ctx* ctx, unsigned long long* D);      // k_field_dirty: bd_cols[0 .. bd_columns) ORed into D, on ctx->stream
 int32_t mpfmt_field_mark_dirty(mpfmt_ctx* ctx);          // ORs ctx->bd_cols[0 .. bd_columns) into the dirty bitmap, on ctx->stream
 void mpfmt_field_drop_internal(mpfmt_ctx* ctx);
 bool mpfmt_field_live(mpfmt_ctx* ctx);                   // a tracked field of the resident samples and graph (drops one of another graph)
 bool mpfmt_field_history(const mpfmt_ctx* ctx);          // no graph build and no whole sweep since the field was last valid
+// the tracked cost-to-go field (kernels_togo.hip)
+int32_t mpfmt_togo_compute(mpfmt_ctx* ctx, const int64_t* targets1, int64_t ntgt, int32_t checkpts, const uint64_t* d_F, mpfmt_togo_info* info);
+int32_t mpfmt_togo_repair(mpfmt_ctx* ctx, const uint64_t* d_F, mpfmt_togo_info* info);      // steps 2-5 on the tracked buffers
+int32_t mpfmt_togo_mark_dirty(mpfmt_ctx* ctx);           // ORs ctx->bd_cols[0 .. bd_columns) into its own dirty bitmap, on ctx->stream
+void mpfmt_togo_drop_internal(mpfmt_ctx* ctx);
+bool mpfmt_togo_live(mpfmt_ctx* ctx);                    // a tracked field of the resident samples and graph (drops one of another graph)
+bool mpfmt_togo_history(const mpfmt_ctx* ctx);           // no graph build and no whole sweep since the field was last valid
 // the field of the usable seeds of one external start: entries [n] of a near list (1-based samples, distances, bits: 2 = usable) become
 // C[y] = seed[y] = fl(0 + dist); labels stay in ctx->sssp_C, parents in ctx->sssp_A (1-based, -1 = the start, 0 = none)
 int32_t mpfmt_sssp_seeded_device(mpfmt_ctx* ctx, const int64_t* d_idx1, const double* d_dist, const uint8_t* d_bits, int64_t n, const uint64_t* d_F,

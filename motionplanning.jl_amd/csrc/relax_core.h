@@ -1,7 +1,7 @@
-// The relaxation core of the roadmap fields: what kernels_sssp.hip, kernels_sssp_multi.hip, kernels_field.hip and
-// kernels_sssp_to.hip share -- the ring of three changed-sample bitmaps with its round state, the column fold of the pull, the parent
-// rule, and the host loop that issues the rounds.  Everything here is __forceinline__ or a host template: each kernel stays a kernel of
-// its own and inlines the blocks it uses.
+// The relaxation core of the roadmap fields: what kernels_sssp.hip, kernels_sssp_multi.hip, kernels_field.hip,
+// kernels_sssp_to.hip and kernels_togo.hip share -- the ring of three changed-sample bitmaps with its round state, the column fold of
+// the pull, the parent rule, the push of the cost-to-go, and the host loop that issues the rounds.  Everything here is __forceinline__
+// or a host template: each kernel stays a kernel of its own and inlines the blocks it uses.
 //
 // * three sample bitmaps in rotation: round t reads B[t % 3], marks B[(t+1) % 3] and clears B[(t+2) % 3] (last read by round t-1),
 //   so no round needs a memset of its own;
@@ -178,6 +178,60 @@ __device__ __forceinline__ void parents_body(int64_t N, int64_t src, const int64
         if (lane == 0) { A[x] = a; if (WITH_ENTRY) Ab[x] = e; }
     }
     if (lane == 0 && nreach) atomicAdd(reached, nreach);
+}
+
+// ---- the push of the cost-to-go ---------------------------------------------------------------------------------------
+
+// The body of a push round, shared by k_sssp_to_push (the one-shot field) and k_togo_push (the tracked one): the ring header, then one
+// wavefront per quarter word of the round's bitmap (& F with checkpts).  A column x of it loads G[x] once and offers fl(G[x] + w) to
+// every row y of a free entry: a plain load of G[y] first, then a 64-bit atomicMin on the label bits; a returned old value above the
+// candidate marks y for the next round.  The counters are those of the caller's state.  r = ring_at(round), gtid and nthreads (the
+// global thread index and the grid size) come from the kernel, which computes them in this order.
+__device__ __forceinline__ void push_body(int64_t words, const int64_t* __restrict__ colptr, const int32_t* __restrict__ rowval,
+                                          const double* __restrict__ nzval, const uint64_t* __restrict__ efree, const uint64_t* __restrict__ F,
+                                          double* G, uint64_t* bm, count_slot* slot, unsigned long long* rounds, unsigned long long* relax,
+                                          unsigned long long* atomics, unsigned long long* entries, unsigned long long* columns,
+                                          const ring_idx& r, int64_t gtid, int64_t nthreads)
+{
+    const uint64_t* bin;
+    unsigned long long* bout;
+    if (!ring_round(slot, rounds, bm, words, r, gtid, nthreads, bin, bout)) return;
+    unsigned long long* Gb = (unsigned long long*)G;
+    const int lane = threadIdx.x & 63;
+    const int64_t nwaves = nthreads >> 6;
+    unsigned long long nrel = 0, natom = 0, nchg = 0, nent = 0, ncol = 0;
+    for (int64_t u = gtid >> 6; u < 4 * words; u += nwaves) {
+        const int64_t w = u >> 2;
+        const int sh = (int)(u & 3) * 16;
+        uint64_t word = bin[w];
+        if (F) word &= F[w];
+        unsigned bits = __builtin_amdgcn_readfirstlane((unsigned)((word >> sh) & 0xffffull));        // (the same in every lane: say so)
+        while (bits) {
+            const int64_t x = w * 64 + sh + __builtin_ctz(bits);
+            bits &= bits - 1;
+            const double gx = G[x];
+            const int64_t b0 = colptr[x], b1 = colptr[x + 1];
+            if (lane == 0) { ++ncol; nent += (unsigned long long)(b1 - b0); }
+            for (int64_t b = b0 + lane; b < b1; b += 64) {
+                if (!bit_of(efree, b)) continue;
+                const int32_t y = rowval[b];
+                const double cand = gx + nzval[b];
+                ++nrel;
+                if (!(cand < G[y])) continue;
+                const unsigned long long cb = label_bits(cand);
+                const unsigned long long old = atomicMin(&Gb[y], cb);
+                ++natom;
+                if (old > cb) { atomicOr(&bout[y >> 6], 1ull << (y & 63)); ++nchg; }
+            }
+        }
+    }
+    nrel = wave_sum(nrel); natom = wave_sum(natom); nchg = wave_sum(nchg);
+    if (lane == 0) {
+        if (nrel) atomicAdd(relax, nrel);
+        if (natom) atomicAdd(atomics, natom);
+        if (nchg) atomicAdd(&slot[r.out].changed, nchg);
+        if (ncol) { atomicAdd(columns, ncol); atomicAdd(entries, nent); }
+    }
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------

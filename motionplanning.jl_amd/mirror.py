@@ -757,20 +757,55 @@ def _goal_members(P):
     return np.flatnonzero(inside).astype(np.int64) + 1
 
 
-def cost_to_go_(P, checkpts=True):
+def cost_to_go_(P, checkpts=True, keep_field=False):
     """The feedback policy over the roadmap a prmstar_ / fmtstar_(band = ...) call left resident in P.ctx, in any space: from every
     sample the optimal cost to the samples inside P.goal and the next sample on the way (mpfmt_graph_sssp_to).  On the directed
     graphs (double integrator, Dubins, k-nearest) this is not the cost-to-come of a goal sample.  Returns (G, S): G = inf where the goal
     cannot be reached, 0 on the goal samples; S 1-based successors (0 = goal sample or unreached).  Stores metadata["cost_to_go"] and
-    metadata["successor"]."""
+    metadata["successor"].
+    keep_field = True: the context keeps the policy (Context.togo_begin), in any space, so that after addobstacle_ / addblocker_ /
+    removeobstacle_ a repolicy_(P) repairs it instead of computing it again."""
     if P.solution is None or P.ctx is None:
         raise RuntimeError("cost_to_go_ needs the roadmap of a prmstar_ / fmtstar_ call")
     P.CC._bind(P.ctx, P.SS)
-    out = P.ctx.graph_sssp_to(_goal_members(P), checkpts=checkpts)
-    P.solution.metadata["cost_to_go"] = out["G"]
-    P.solution.metadata["successor"] = out["S"]
-    P.solution.metadata["cost_to_go_info"] = out["info"]
-    return out["G"], out["S"]
+    if keep_field:
+        info = P.ctx.togo_begin(_goal_members(P), checkpts=checkpts)
+        G, S = P.ctx.togo_read()
+    else:
+        out = P.ctx.graph_sssp_to(_goal_members(P), checkpts=checkpts)
+        G, S, info = out["G"], out["S"], out["info"]
+    P.solution.metadata["cost_to_go"] = G
+    P.solution.metadata["successor"] = S
+    P.solution.metadata["cost_to_go_info"] = info
+    return G, S
+
+
+def repolicy_(P):
+    """After addobstacle_ / addblocker_ / removeobstacle_ on a problem whose policy cost_to_go_(P, keep_field=True) left in the context:
+    repair it (Context.togo_update: work that follows the edit; a whole recomputation only where the edit could not be applied in place)
+    and refresh metadata["cost_to_go"] / ["successor"]; metadata["cost_to_go_info"] = the repair's counters.  successor_paths then
+    serves any current state.  Returns (G, S).  Raises (MPFMTError, ERR_STATE) without a tracked policy."""
+    if P.solution is None or P.ctx is None:
+        raise RuntimeError("repolicy_ needs the policy of a cost_to_go_(P, keep_field=True) call")
+    ctx = P.ctx
+    if ctx.stat("togo_tracked") != 1:
+        raise _lib.MPFMTError(_lib.ERR_STATE, "repolicy_: the context tracks no policy (cost_to_go_(P, keep_field=True))")
+    P.CC._bind(ctx, P.SS)
+    # (an edit that could not be applied in place: the mask is swept whole, and the update recomputes)
+    if isinstance(P.SS.dist, LinearQuadratic):
+        if ctx.stat("steer_swept") != 1:
+            ctx.di_graph_edges_free()
+    elif isinstance(P.SS.dist, (DubinsExact, ReedsSheppExact)):
+        if ctx.stat("steer_swept") != 1:
+            ctx.dubins_graph_edges_free() if isinstance(P.SS.dist, DubinsExact) else ctx.reedsshepp_graph_edges_free()
+    elif ctx.stat("graph_swept") != 1:
+        ctx.knn_graph_edges_free() if "k" in P.solution.metadata else ctx.graph_sweep_device()
+    info = ctx.togo_update()
+    G, S = ctx.togo_read()
+    P.solution.metadata["cost_to_go"] = G
+    P.solution.metadata["successor"] = S
+    P.solution.metadata["cost_to_go_info"] = info
+    return G, S
 
 
 def successor_paths(S, nodes):
