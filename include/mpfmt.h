@@ -325,8 +325,9 @@ MPFMT_API int32_t mpfmt_knn_prmstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx,
  *      cost-to-come field from init_idx and the goal extraction of mpfmt_prmstar: the reached sample in the region of lowest
  *      (C, index).  The goal predicate is that of the steering FMT* planners: POINT = the exact state, RECT / BALL on the first dw
  *      coordinates.  res as in mpfmt_prmstar; collision_checks = 0.
- * Tracked fields (mpfmt_field_*) and external states (mpfmt_roadmap_*) stay refused on a steering graph: MPFMT_ERR_STATE,
- *      "Euclidean graphs only". */
+ * Tracked fields (mpfmt_field_*) and the Euclidean calls on external states (mpfmt_roadmap_*) stay refused on a steering graph:
+ *      MPFMT_ERR_STATE, "Euclidean graphs only".  External states on a steering graph have entry points of their own:
+ *      mpfmt_steer_roadmap_* ("roadmap queries for external states, steering spaces", below). */
 MPFMT_API int32_t mpfmt_host_graph_sssp_to(int64_t N, const int64_t* colptr, const int32_t* rowval, const double* nzval,
                                            const uint64_t* efree, const uint64_t* F, const int64_t* targets, int64_t ntgt,
                                            double* G, int64_t* S);
@@ -509,8 +510,9 @@ MPFMT_API int32_t mpfmt_togo_drop(mpfmt_ctx* ctx);
  *      sharded ctx, the 2-D SAT world, a non-identity workspace; MPFMT_ERR_ARG: NULL arrays, a non-finite query coordinate.  nq == 0
  *      succeeds and does nothing.  Timers "roadmap_near", "roadmap_attach"; stats "roadmap_candidates" (distances evaluated by the last
  *      call), "roadmap_near_total" (near-set entries it found).
- * Out of scope: k-nearest graphs (an external state has no radius there), steering spaces, the SAT world, sharded contexts, and repairing
- *      a field after mpfmt_boxes_add / _remove (the mask stays current: ask again). */
+ * Out of scope: k-nearest graphs (an external state has no radius there), the SAT world, sharded contexts, and repairing
+ *      a field after mpfmt_boxes_add / _remove (the mask stays current: ask again).  A resident steering graph is refused here and
+ *      served by mpfmt_steer_roadmap_* (after the cost matrices below). */
 typedef struct {
     int32_t status;            /* 0 solved, 1 no usable path, 2 s not a free state, 3 g not a free state */
     int32_t pad_;
@@ -568,6 +570,50 @@ MPFMT_API int32_t mpfmt_graph_sssp_multi(mpfmt_ctx* ctx, const int64_t* sources,
                                mpfmt_sssp_info* info);
 MPFMT_API int32_t mpfmt_roadmap_matrix(mpfmt_ctx* ctx, const double* S, int64_t ns, const double* G, int64_t ng, int32_t checkpts, double* cost,
                              int32_t* status, mpfmt_roadmap_matrix_info* info);
+
+/* ---- roadmap queries for external states, steering spaces: the calls of "roadmap queries for external states" on a
+ *      resident double-integrator, Dubins or Reeds-Shepp graph.  The ctx holds an unsharded, filled and swept steering graph and an
+ *      N-D box set; callers pass no space parameters: the resident graph's (rho or turning radius and speed, the cost radius r) are used.
+ *      GOVERNING RULE.  An external state q (d finite doubles) gets the entries it would have had, had it been a sample when the graph
+ *      was built and swept: the same arithmetic, the same direction convention (entry of column x with row y = the edge y -> x), and
+ *      no self-exclusion, because q has no index.
+ *      Head list of q (direction 1, edges y -> q, q in the role of a column); cost <= r is required in every space:
+ *        double integrator : member iff dcost(V[y], q; r) > 0 (the build's candidate test) and cost <= r from steer(V[y], q);
+ *                            weight = that cost; free bit = the sweep's 5-waypoint motion test V[y] -> q with the t* of that steer.
+ *        Dubins            : member iff the positions are within r (the canonical 2-D fold d2 <= r * r of the candidate graph) and
+ *                            cost <= r from dubins(V[y], q); weight = that cost; free bit = the sweep's motion test V[y] -> q.
+ *        Reeds-Shepp       : member iff positions within r and reedsshepp cost (q, V[y]) <= r -- the cost-only evaluation in the
+ *                            direction the build stores for column q, row y; weight = that cost; free bit = motion test V[y] -> q.
+ *      Tail list of q (direction 0, edges q -> y, q as a row of column y): the mirror image.  Double integrator and Dubins: steer
+ *        and motion q -> V[y].  Reeds-Shepp: weight = cost (V[y], q), motion test q -> V[y].
+ *      Consequences: indices ascend.  A sample bit-equal to q is a member like any duplicate sample is today (cost 0, t* = 0, and
+ *        whatever bit the motion test returns at t = 0).  For q bit-equal to sample v the head list is column v of the resident graph
+ *        plus v itself, the tail list every entry with row v plus v; weights and bits are the resident ones, bit for bit.
+ *      A pair query (s, g) reads as mpfmt_roadmap_query with these lists substituted: seeds fl(0 + w(s, y)) on tail entries that are
+ *        free and, with checkpts, have F[y] set (F = the bitmap of the steering planners: bounds on all d coordinates, the point test
+ *        on the first dw); the direct edge exists iff g passes the tail-list membership of s (g treated as a sample) and the motion
+ *        s -> g is free, its weight is that entry's weight; C = the least fixed point of C[x] = min(seed[x], min_y fl(C[y] + w_yx));
+ *        cost = min(direct, min_y fl(C[y] + w(y, g))) over free head entries; parents by the rule above with s as index 0 and
+ *        label 0, the direct edge wins ties.  The uniqueness argument needs only w >= 0 and monotone fl(a + w): it holds for these
+ *        quasi-metric weights.  Status 0 solved, 1 no usable path, 2 s not a free state, 3 g not a free state (the steering planners'
+ *        predicate: bounds on all d coordinates, point test on the first dw; s is looked at first).  near_* and usable_* are filled for
+ *        every status; info is mpfmt_roadmap_info.
+ * mpfmt_steer_roadmap_near / _attach / _query : arguments, CSR layout, the cap == 0 size query and MPFMT_ERR_CAPACITY exactly as
+ *      mpfmt_roadmap_near / _attach / _query.  Lists leave the kernel in ascending order (no ordering pass).
+ * Refusals leave the ctx as it was.  MPFMT_ERR_STATE: no resident steering graph (a Euclidean or k-nearest graph: use
+ *      mpfmt_roadmap_*), an unswept graph or no mask, a sharded ctx, the 2-D SAT world, no box set.  MPFMT_ERR_ARG: NULL arrays, a
+ *      bad direction, negative counts, a non-finite coordinate.  nq == 0 succeeds and does nothing.  The calls touch neither graph,
+ *      mask, segment counts, a tracked cost-to-go field nor the samples.
+ *      Timers "steer_roadmap_near", "steer_roadmap_attach"; stats "roadmap_candidates" (pairs pre-tested by the last call),
+ *      "roadmap_near_total" (entries found), "steer_roadmap_steered" (exact steers run).
+ * Out of scope: a matrix form and a host twin (the product has no host restatement of the steering sweeps), k-nearest graphs, the
+ *      SAT world, sharded contexts, the controls of the attachment edges (mpfmt_di_steer / _dubins_steer / _reedsshepp_steer give
+ *      them for any state pair). */
+MPFMT_API int32_t mpfmt_steer_roadmap_near(mpfmt_ctx* ctx, const double* Q, int64_t nq, int32_t direction, int64_t* ptr, int64_t cap,
+                                           int64_t* idx, double* dist, uint64_t* free_mask, int64_t* total);
+MPFMT_API int32_t mpfmt_steer_roadmap_attach(mpfmt_ctx* ctx, const double* Q, int64_t nq, const double* C, int64_t* parent, double* cost);
+MPFMT_API int32_t mpfmt_steer_roadmap_query(mpfmt_ctx* ctx, const double* S, const double* G, int64_t nq, int32_t checkpts, double* cost,
+                                            int64_t* path_ptr, int64_t* path, int64_t path_cap, mpfmt_roadmap_info* info);
 
 /* ---- adaptive shortcutting of solution paths (Hsu 2000): shortcut / cut_corner / adaptive_shortcut(!) of src/postprocessors.jl:6-50,
  *      statement for statement, for ONE path on the host and for a BATCH of paths on the device (one wavefront per path; the tree paths

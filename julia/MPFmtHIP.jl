@@ -288,6 +288,42 @@ function hip_roadmap_attach(DS::HIPDistanceDS, Q::Matrix{Float64}, C::Vector{Flo
     cost, parent
 end
 
+# the same on a resident steering graph (double integrator, Dubins, Reeds-Shepp; include/mpfmt.h, "roadmap queries for external
+# states, steering spaces"): the states attach by the space's own steer, with the resident graph's parameters.  hip_steer_roadmap_near
+# -> (ptr[n + 1] 0-based, idx 1-based ascending, cost, free) of the tail (direction 0) or head (1) lists.  The C caller that executes
+# these calls with the same widths is tests/abi_c/abi_caller12.c.
+const sym_steer_roadmap_query = :mpfmt_steer_roadmap_query
+const sym_steer_roadmap_near = :mpfmt_steer_roadmap_near
+const sym_steer_roadmap_attach = :mpfmt_steer_roadmap_attach
+function hip_steer_roadmap_query(DS::HIPDistanceDS, S::Matrix{Float64}, G::Matrix{Float64}; checkpts = true, path_cap = 64 * size(S, 2))
+    n = size(S, 2)
+    cost = Vector{Float64}(n); pptr = Vector{Int}(n + 1); path = Vector{Int}(max(path_cap, 1)); info = Vector{RoadmapInfo}(n)
+    rc = ccall((sym_steer_roadmap_query, libmpfmt), Int32,
+               (Ptr{Void}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{RoadmapInfo}),
+               DS.ctx, S, G, n, checkpts, cost, pptr, path, path_cap, info)
+    rc == -5 && return hip_steer_roadmap_query(DS, S, G; checkpts = checkpts, path_cap = pptr[n + 1])
+    chk(DS.ctx, rc)
+    cost, pptr, path[1:pptr[n + 1]], info
+end
+function hip_steer_roadmap_near(DS::HIPDistanceDS, Q::Matrix{Float64}, direction::Int; cap = 0)
+    n = size(Q, 2)
+    ptr = Vector{Int}(n + 1); total = Ref{Int64}(0)
+    idx = Vector{Int}(max(cap, 1)); dist = Vector{Float64}(max(cap, 1)); free = falses(max(cap, 1))
+    rc = ccall((sym_steer_roadmap_near, libmpfmt), Int32,
+               (Ptr{Void}, Ptr{Float64}, Int64, Int32, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{UInt64}, Ptr{Int64}),
+               DS.ctx, Q, n, direction, ptr, cap, idx, dist, free.chunks, total)
+    rc == -5 && return hip_steer_roadmap_near(DS, Q, direction; cap = total[])
+    chk(DS.ctx, rc)
+    ptr, idx[1:total[]], dist[1:total[]], free[1:total[]]
+end
+function hip_steer_roadmap_attach(DS::HIPDistanceDS, Q::Matrix{Float64}, C::Vector{Float64})
+    n = size(Q, 2)
+    cost = Vector{Float64}(n); parent = Vector{Int}(n)
+    chk(DS.ctx, ccall((sym_steer_roadmap_attach, libmpfmt), Int32, (Ptr{Void}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
+                      DS.ctx, Q, n, C, parent, cost))
+    cost, parent
+end
+
 # ---- a cost-to-come field kept valid across box edits (include/mpfmt.h): hip_prmstar!(P, r) computes a field and throws it away;
 #      hip_field_begin! keeps the field of init_idx in the ctx, and after mpfmt_boxes_add / _remove (INTEGRATION.md, "obstacles that
 #      change") hip_replan! repairs it -- work that follows the edit -- and extracts goal and path again.  The C caller that executes

@@ -142,6 +142,10 @@ SYMBOLS = [
     ("mpfmt_roadmap_near", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, C.c_int32, c_i64_p, C.c_int64, c_i64_p, c_d_p, c_u64_p, c_i64_p]),
     ("mpfmt_roadmap_attach", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, c_d_p, c_i64_p, c_d_p]),
     ("mpfmt_roadmap_query", C.c_int32, [C.c_void_p, c_d_p, c_d_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, c_i64_p, C.c_int64, C.POINTER(RoadmapInfo)]),
+    ("mpfmt_steer_roadmap_near", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, C.c_int32, c_i64_p, C.c_int64, c_i64_p, c_d_p, c_u64_p, c_i64_p]),
+    ("mpfmt_steer_roadmap_attach", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, c_d_p, c_i64_p, c_d_p]),
+    ("mpfmt_steer_roadmap_query", C.c_int32, [C.c_void_p, c_d_p, c_d_p, C.c_int64, C.c_int32, c_d_p, c_i64_p, c_i64_p, C.c_int64,
+                                              C.POINTER(RoadmapInfo)]),
     ("mpfmt_roadmap_matrix", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, c_d_p, C.c_int64, C.c_int32, c_d_p, C.POINTER(C.c_int32),
                                          C.POINTER(RoadmapMatrixInfo)]),
     ("mpfmt_host_roadmap_query", C.c_int32, [C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p, c_d_p, C.c_int32,
@@ -853,6 +857,9 @@ class Context:
         """Near lists of the external states Q (n, d) over the resident r-disc graph's radius: (ptr (n + 1,) 0-based, idx 1-based
         ascending, dist, free bits (bool)); direction 0 = tail (q -> sample), 1 = head (sample -> q).  cap: capacity in entries (None:
         ask, then fetch); too small raises MPFMTError(ERR_CAPACITY) whose .total holds the size needed."""
+        return self._near(self._L.mpfmt_roadmap_near, Q, direction, cap)
+
+    def _near(self, fn, Q, direction, cap):
         Q = self._states(Q)
         n = Q.shape[0]
         ptr = np.zeros(n + 1, dtype=np.int64)
@@ -862,7 +869,7 @@ class Context:
         while True:
             idx = np.empty(max(cap, 1), dtype=np.int64); dist = np.empty(max(cap, 1), dtype=np.float64)
             mask = np.zeros(max(nwords(cap), 1), dtype=np.uint64)
-            rc = self._L.mpfmt_roadmap_near(self._h, _dp(Q), n, int(direction), _ip(ptr), cap, _ip(idx), _dp(dist), _up(mask), C.byref(total))
+            rc = fn(self._h, _dp(Q), n, int(direction), _ip(ptr), cap, _ip(idx), _dp(dist), _up(mask), C.byref(total))
             if rc == ERR_CAPACITY and ask:
                 cap, ask = int(total.value), False
                 continue
@@ -877,19 +884,25 @@ class Context:
     def roadmap_attach(self, Q, Cfield):
         """The goal half for many goals over ONE field (a row of graph_sssp): per state of Q (n, d) the head-direction minimum
         fl(C[y] + d(y, q)) over the free near samples -> (cost (n,), +Inf = none; parent (n,) 1-based, 0 = none)."""
+        return self._attach(self._L.mpfmt_roadmap_attach, Q, Cfield)
+
+    def _attach(self, fn, Q, Cfield):
         Q = self._states(Q)
         n = Q.shape[0]
         Cf = np.ascontiguousarray(Cfield, dtype=np.float64)
         if Cf.shape != (self.N,):
             raise ValueError("C must have N entries")
         cost = np.empty(max(n, 1), dtype=np.float64); par = np.empty(max(n, 1), dtype=np.int64)
-        self._chk(self._L.mpfmt_roadmap_attach(self._h, _dp(Q), n, _dp(Cf), _ip(par), _dp(cost)))
+        self._chk(fn(self._h, _dp(Q), n, _dp(Cf), _ip(par), _dp(cost)))
         return cost[:n], par[:n]
 
     def roadmap_query(self, S, G, checkpts=True):
         """Pair queries between external states S[i] -> G[i] ((n, d) each) over the resident roadmap: (cost (n,), paths = list of 1-based
         sample index arrays between s and g, info = list of dicts: status 0 solved / 1 no path / 2 start blocked / 3 goal blocked,
         near_s, usable_s, near_g, usable_g, rounds, path_len, ms_device)."""
+        return self._query(self._L.mpfmt_roadmap_query, S, G, checkpts)
+
+    def _query(self, fn, S, G, checkpts):
         S = self._states(S); G = self._states(G)
         if S.shape != G.shape:
             raise ValueError("S and G must have the same shape")
@@ -900,13 +913,28 @@ class Context:
         cap = max(64 * n, 1)
         while True:
             path = np.empty(cap, dtype=np.int64)
-            rc = self._L.mpfmt_roadmap_query(self._h, _dp(S), _dp(G), n, int(bool(checkpts)), _dp(cost), _ip(pptr), _ip(path), cap, info)
+            rc = fn(self._h, _dp(S), _dp(G), n, int(bool(checkpts)), _dp(cost), _ip(pptr), _ip(path), cap, info)
             if rc == ERR_CAPACITY and int(pptr[n]) > cap:
                 cap = int(pptr[n])
                 continue
             self._chk(rc)
             break
         return (cost[:n], [path[pptr[i]:pptr[i + 1]].copy() for i in range(n)], [_roadmap_info(info[i]) for i in range(n)])
+
+    # the same three calls on a resident steering graph (include/mpfmt.h, "roadmap queries for external states, steering spaces"): the
+    # resident graph's own space parameters are used; shapes and return values are those of the Euclidean namesakes
+    def steer_roadmap_near(self, Q, direction=0, cap=None):
+        """roadmap_near over the resident double-integrator / Dubins / Reeds-Shepp graph: the entries q would have had as a sample (dist =
+        the steering cost in the build's direction, free bits = the sweep's motion test)."""
+        return self._near(self._L.mpfmt_steer_roadmap_near, Q, direction, cap)
+
+    def steer_roadmap_attach(self, Q, Cfield):
+        """roadmap_attach over the resident steering graph: per state the head-direction minimum fl(C[y] + w(y, q)) over its free entries."""
+        return self._attach(self._L.mpfmt_steer_roadmap_attach, Q, Cfield)
+
+    def steer_roadmap_query(self, S, G, checkpts=True):
+        """roadmap_query over the resident steering graph: (cost, paths, info) for the pairs S[i] -> G[i], states that are not samples."""
+        return self._query(self._L.mpfmt_steer_roadmap_query, S, G, checkpts)
 
     def roadmap_matrix(self, S, G, checkpts=True):
         """The cost matrix between external starts S (ns, d) and goals G (ng, d) at the price of ns fields, 64 per pass over the graph

@@ -14,6 +14,7 @@
 #include "mp_math.h"
 #include "sat2d_predicates.h"
 #include "steer_delta.h"
+#include "steer_roadmap.h"
 
 #define CAR_TWOPI (2 * 3.141592653589793)
 
@@ -666,6 +667,49 @@ __global__ __launch_bounds__(SD_THREADS) void k_car_delta(const double* __restri
     if (lane == 0 && tested_n) atomicAdd(ctr + 1, tested_n);
 }
 
+// ---- external states on the resident graph (steer_roadmap.h) ---------------------------------------------------------
+// One wavefront per query state q: the entries q would have had as a sample.  Dense loop: the positions fold of the candidate graph
+// (d2 <= r * r, the canonical 2-D fold -- exact, so it is also the first membership test).  Survivors, 64 at a time: the cost of
+// k_car_cost in the build's direction -- head (dir 1): Dubins steer(V[y] -> q), Reeds-Shepp rs_cost(q, V[y]); tail: Dubins
+// steer(q -> V[y]), Reeds-Shepp rs_cost(V[y], q) --, cost <= r, and in modes 1 and 2 the whole sweep's car_motion_free from the row
+// to the column (head: V[y] -> q, tail: q -> V[y]).  Boxes are read through mpfmt_ws2d as k_car_sweep reads them.
+template <int KIND>
+__global__ __launch_bounds__(SRM_WAVES * 64) void k_car_roadmap(srm_args a, mpfmt_ws2d cc, mpfmt_ss ss)
+{
+    __shared__ int32_t s_q[SRM_WAVES][SRM_QCAP];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t qi = (int64_t)blockIdx.x * SRM_WAVES + wv;
+    if (qi >= a.nq) return;
+    const double q[3] = {a.Q[3 * qi], a.Q[3 * qi + 1], a.Q[3 * qi + 2]};
+    const double r2 = a.r * a.r;
+    auto pre = [&](int64_t y) -> bool {
+        const double t0 = q[0] - a.X[3 * y], t1 = q[1] - a.X[3 * y + 1];
+        const double tt0 = t0 * t0, tt1 = t1 * t1;
+        return tt0 + tt1 <= r2;
+    };
+    auto exact = [&](int64_t y, bool motion, double& w, bool& fr, int& st) -> bool {
+        const double v[3] = {a.X[3 * y], a.X[3 * y + 1], a.X[3 * y + 2]};
+        const double* from = a.dir ? v : q;
+        const double* to = a.dir ? q : v;
+        double c;
+        if constexpr (KIND == 2) c = a.dir ? rs_cost(q, v, a.rt) : rs_cost(v, q, a.rt);
+        else {
+            car_step path[5];
+            int L;
+            c = car_steer<KIND>(from, to, a.rt, a.sp, path, L);
+        }
+        st = 1;
+        if (!(c <= a.r)) return false;
+        w = c;
+        if (motion) {
+            int ns = 0;
+            fr = car_motion_free<KIND>(from, to, a.rt, a.sp, cc, ss, &ns);
+        }
+        return true;
+    };
+    srm_wave(a, qi, lane, s_q[wv], pre, exact);
+}
+
 // controls: [n][5][3] = (duration, speed, signed curvature), unused segments zero; nseg[i] = segments used
 template <int KIND>
 __global__ __launch_bounds__(256) void k_car_steer(const double* __restrict__ X0, const double* __restrict__ X1, int64_t n, double rt,
@@ -801,6 +845,21 @@ int32_t mpfmt_car_delta_launch(mpfmt_ctx* ctx, const double* d_delta, int32_t nd
     if (ctx->steer_kind == MPFMT_STEER_REEDSSHEPP) { if (remove) CAR_DELTA_GO(2, true); else CAR_DELTA_GO(2, false); }
     else { if (remove) CAR_DELTA_GO(1, true); else CAR_DELTA_GO(1, false); }
 #undef CAR_DELTA_GO
+    HIPCHK(ctx, hipGetLastError());
+    return MPFMT_OK;
+}
+
+// external states on the resident car graph: a.Q / nq / dir / mode / X / N / pair and the outputs are the caller's
+int32_t mpfmt_car_roadmap_launch(mpfmt_ctx* ctx, srm_args& a)
+{
+    a.r = ctx->steer_r; a.rt = ctx->car_rt; a.sp = ctx->car_sp;
+    a.rho = a.i2 = a.i3 = a.i4 = a.r2 = 0.0;
+    a.boxes = ctx->boxes; a.M = ctx->M; a.stage = 0;
+    mpfmt_ws2d cc;
+    cc.kind = 0; cc.boxes = ctx->boxes; cc.M = ctx->M; cc.shapes = nullptr; cc.ns = 0; cc.aabb = ctx->aabb2d;
+    const unsigned nb = (unsigned)((a.nq + SRM_WAVES - 1) / SRM_WAVES);
+    if (ctx->steer_kind == MPFMT_STEER_REEDSSHEPP) hipLaunchKernelGGL(k_car_roadmap<2>, dim3(nb), dim3(SRM_WAVES * 64), 0, ctx->stream, a, cc, ctx->ss);
+    else hipLaunchKernelGGL(k_car_roadmap<1>, dim3(nb), dim3(SRM_WAVES * 64), 0, ctx->stream, a, cc, ctx->ss);
     HIPCHK(ctx, hipGetLastError());
     return MPFMT_OK;
 }

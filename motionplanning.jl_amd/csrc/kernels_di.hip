@@ -21,6 +21,7 @@
 
 #include "di_steer.h"
 #include "steer_delta.h"
+#include "steer_roadmap.h"
 
 // MODE 0: count   1: fill the staging CSC from the counts   2: count AND keep the accepted hits in slot lists (single pass)
 template <int M, int MODE>
@@ -457,6 +458,73 @@ __global__ void k_di_steer(const double* __restrict__ X0, const double* __restri
     cost[p] = c; topt[p] = t;
 }
 
+// ---- external states on the resident graph (steer_roadmap.h) ---------------------------------------------------------
+// One wavefront per query state q: the entries q would have had as a sample.  Head direction (dir 1): the pair is (V[y], q), q in the
+// role of a column; tail direction: (q, V[y]).  Dense loop: the two multiply-only conservative tests of k_di_pairs on that pair.
+// Survivors, 64 at a time: the build's exact candidate test dcost(r) > 0, its steer and cost <= r, and -- modes 1 and 2 -- the whole
+// sweep's di_motion_free with the t* of that steer.  No self-exclusion: q has no index.  LDS: the box set [M][2 M] when a.stage.
+template <int M>
+__global__ __launch_bounds__(SRM_WAVES * 64) void k_di_roadmap(srm_args a, mpfmt_ss ss)
+{
+    constexpr int NS = 2 * M;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int32_t s_q[SRM_WAVES][SRM_QCAP];
+    double* sbox = (double*)smem;
+    const bool staged = a.stage && a.mode != 0;
+    if (staged) for (int t = threadIdx.x; t < a.M * 2 * M; t += blockDim.x) sbox[t] = a.boxes[t];
+    __syncthreads();                                         // (the only workgroup barrier: the wavefronts are on their own from here)
+    const double* bx = staged ? (const double*)sbox : a.boxes;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t qi = (int64_t)blockIdx.x * SRM_WAVES + wv;
+    if (qi >= a.nq) return;
+    mpfmt_ws2d cc;
+    cc.kind = 0; cc.boxes = nullptr; cc.M = 0; cc.shapes = nullptr; cc.ns = 0;
+    cc.aabb = mpfmt_aabb2d();
+    double q[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) q[i] = a.Q[qi * NS + i];
+    auto pre = [&](int64_t y) -> bool {
+        double ca = 0.0, cb = 0.0, cc2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+            const double py = a.X[y * NS + i], vy = a.X[y * NS + M + i];
+            const double p = a.dir ? q[i] - py : py - q[i];
+            const double v0 = a.dir ? vy : q[M + i], v1 = a.dir ? q[M + i] : vy;
+            ca += p * p;
+            cb += p * (v0 + v1);
+            cc2 += (v0 * v0 + v0 * v1) + v1 * v1;
+        }
+        const double ta = 36.0 * ca * a.i4, tb = 24.0 * cb * a.i3, tc = 4.0 * cc2 * a.i2;
+        const double cd = 1.0 - a.rho * ((ta - tb) + tc);
+        const double slack = 1e-9 * (1.0 + a.rho * ((ta + fabs(tb)) + tc));
+        const double l1 = 4.0 * ca * cc2, l2 = 3.0 * cb * cb;
+        const bool far = 4.0 * a.rho * (l1 - l2) > (ca * a.r2) * (1.0 + 1e-9) + 4e-9 * a.rho * (l1 + l2);
+        return (cd > -slack) && !far;
+    };
+    auto exact = [&](int64_t y, bool motion, double& w, bool& fr, int& st) -> bool {
+        double p0[NS], p1[NS];
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            const double c = a.X[y * NS + i];
+            p0[i] = a.dir ? c : q[i];
+            p1[i] = a.dir ? q[i] : c;
+        }
+        const di_coef k = di_coefs<M>(p0, p1);
+        if (!(di_dcost(k, a.rho, a.r) > 0)) return false;
+        double cost, t;
+        di_steer<M>(p0, p1, a.rho, a.r, cost, t);
+        st = 1;
+        if (!(cost <= a.r)) return false;
+        w = cost;
+        if (motion) {
+            int segs = 0;
+            fr = di_motion_free<M>(p0, p1, t, bx, a.M, ss, cc, segs);
+        }
+        return true;
+    };
+    srm_wave(a, qi, lane, s_q[wv], pre, exact);
+}
+
 // ---- host launchers ---------------------------------------------------------------------------------------------------
 #define DISPATCH_M(MM, EXPR)                                                                      \
     switch (MM) {                                                                                 \
@@ -654,6 +722,22 @@ int32_t mpfmt_di_sweep(mpfmt_ctx* ctx)
 
 // the list the whole sweep stages in LDS: M boxes of an m-dimensional workspace are within its limit
 bool mpfmt_di_sweep_fits(int64_t M, int m) { return (size_t)M * 2 * m * sizeof(double) + 16 <= 60 * 1024; }
+
+// external states on the resident double-integrator graph: a.Q / nq / dir / mode / X / N / pair and the outputs are the caller's
+int32_t mpfmt_di_roadmap_launch(mpfmt_ctx* ctx, srm_args& a)
+{
+    const int m = ctx->d / 2;
+    a.r = ctx->steer_r; a.rho = ctx->di_rho;
+    a.i2 = 1.0 / (a.r * a.r); a.i3 = a.i2 / a.r; a.i4 = a.i2 * a.i2; a.r2 = a.r * a.r;
+    a.rt = a.sp = 0.0;
+    a.boxes = ctx->boxes; a.M = ctx->M;
+    a.stage = (ctx->M > 0 && mpfmt_di_sweep_fits(ctx->M, m)) ? 1 : 0;
+    const size_t lds = (a.stage && a.mode != 0) ? (size_t)ctx->M * 2 * m * sizeof(double) + 16 : 0;
+    const unsigned nb = (unsigned)((a.nq + SRM_WAVES - 1) / SRM_WAVES);
+    DISPATCH_M(m, hipLaunchKernelGGL((k_di_roadmap<DM>), dim3(nb), dim3(SRM_WAVES * 64), lds, ctx->stream, a, ctx->ss));
+    HIPCHK(ctx, hipGetLastError());
+    return MPFMT_OK;
+}
 
 // flag + update on ctx->stream for a resident, swept double-integrator graph: d_delta = the nd boxes added (already at the end of
 // ctx->boxes) or a copy of the nd boxes removed (ctx->boxes / ctx->M: the remaining list).  The caller owns bd_cols / bd_ctr.

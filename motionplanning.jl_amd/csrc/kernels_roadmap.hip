@@ -14,6 +14,7 @@
 //   k_roadmap_goal : the last hop and the path of ONE pair query from its goal's list, the finished field and its parents.
 #include "mpfmt_internal.h"
 #include "sweep_predicates.h"
+#include "steer_roadmap.h"
 #include <cmath>
 #include <algorithm>
 
@@ -368,4 +369,87 @@ int32_t mpfmt_roadmap_goal(mpfmt_ctx* ctx, const mpfmt_rm_list& L, int64_t q, co
                        (const double*)L.dist, (const uint8_t*)L.bits, d_C, d_A, ctx->N, d_res);
     HIPCHK(ctx, hipGetLastError());
     return MPFMT_OK;
+}
+
+// ---- the same lists for a resident steering graph (steer_roadmap.h; k_di_roadmap in kernels_di.hip, k_car_roadmap in kernels_car.hip) ------
+// d_X / nx: the samples the queries meet -- ctx->Xo / N, or with pair the goals of a pair query (query i meets d_X[i] alone: the direct
+// edge).  Lists come out of the fill in ascending order: no ordering pass.
+
+static int32_t srm_launch(mpfmt_ctx* ctx, srm_args& a)
+{
+    return ctx->steer_kind == MPFMT_STEER_DI ? mpfmt_di_roadmap_launch(ctx, a) : mpfmt_car_roadmap_launch(ctx, a);
+}
+
+static int32_t srm_stats(mpfmt_ctx* ctx, const unsigned long long* d_ctr, int64_t near_total)
+{
+    unsigned long long c[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(c, d_ctr, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->roadmap_candidates = (int64_t)c[0]; ctx->steer_roadmap_steered = (int64_t)c[1]; ctx->roadmap_near_total = near_total;
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_steer_roadmap_lists(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, int dir, const uint64_t* d_F, mpfmt_rm_list* out,
+                                  bool count_only, const double* d_X, int64_t nx, bool pair)
+{
+    int32_t rc;
+    int64_t *d_cnt = nullptr, *d_us = nullptr, *d_ptr = nullptr;
+    unsigned long long* d_ctr = nullptr;
+    HIPCHK(ctx, tmp.get(&d_cnt, sizeof(int64_t) * (size_t)nq));
+    HIPCHK(ctx, tmp.get(&d_us, sizeof(int64_t) * (size_t)nq));
+    HIPCHK(ctx, tmp.get(&d_ptr, sizeof(int64_t) * (size_t)(nq + 1)));
+    HIPCHK(ctx, tmp.get(&d_ctr, 2 * sizeof(unsigned long long)));
+    HIPCHK(ctx, hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    mpfmt_timed tm(ctx);
+    srm_args a{};
+    a.Q = d_Q; a.nq = nq; a.dir = dir; a.mode = 0; a.X = d_X; a.N = nx; a.pair = pair ? 1 : 0; a.F = d_F;
+    a.near_cnt = d_cnt; a.usable_cnt = d_us; a.ctr = d_ctr;
+    if ((rc = srm_launch(ctx, a))) return rc;
+    out->ptr_host.assign((size_t)nq + 1, 0);
+    HIPCHK(ctx, hipMemcpyAsync(out->ptr_host.data() + 1, d_cnt, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < nq; ++i) out->ptr_host[(size_t)i + 1] += out->ptr_host[(size_t)i];
+    const int64_t total = out->ptr_host[(size_t)nq];
+    if (count_only) {
+        tm.end("steer_roadmap_near");
+        out->total = total;
+        return srm_stats(ctx, d_ctr, total);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d_ptr, out->ptr_host.data(), sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice, ctx->stream));
+    int64_t* d_idx1 = nullptr; double* d_dist = nullptr; uint8_t* d_bits = nullptr;
+    HIPCHK(ctx, tmp.get(&d_idx1, sizeof(int64_t) * (size_t)total));
+    HIPCHK(ctx, tmp.get(&d_dist, sizeof(double) * (size_t)total));
+    HIPCHK(ctx, tmp.get(&d_bits, (size_t)total));
+    HIPCHK(ctx, hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    a.mode = 1; a.ptr = d_ptr; a.idx1 = d_idx1; a.dist = d_dist; a.bits = d_bits;
+    if ((rc = srm_launch(ctx, a))) return rc;
+    tm.end("steer_roadmap_near");
+    out->usable_host.assign((size_t)nq, 0);
+    HIPCHK(ctx, hipMemcpyAsync(out->usable_host.data(), d_us, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = srm_stats(ctx, d_ctr, total))) return rc;
+    out->ptr = d_ptr; out->idx1 = d_idx1; out->dist = d_dist; out->bits = d_bits; out->total = total;
+    return MPFMT_OK;
+}
+
+// the reduce form over a device field d_C [N]: head direction, one launch, no list
+int32_t mpfmt_steer_roadmap_reduce(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, const double* d_C, double* d_cost, int64_t* d_parent)
+{
+    int32_t rc;
+    int64_t* d_cnt = nullptr;
+    unsigned long long* d_ctr = nullptr;
+    HIPCHK(ctx, tmp.get(&d_cnt, sizeof(int64_t) * (size_t)nq));
+    HIPCHK(ctx, tmp.get(&d_ctr, 2 * sizeof(unsigned long long)));
+    HIPCHK(ctx, hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    mpfmt_timed tm(ctx);
+    srm_args a{};
+    a.Q = d_Q; a.nq = nq; a.dir = 1; a.mode = 2; a.X = ctx->Xo; a.N = ctx->N; a.near_cnt = d_cnt; a.C = d_C; a.best_cost = d_cost;
+    a.best_parent = d_parent; a.ctr = d_ctr;
+    if ((rc = srm_launch(ctx, a))) return rc;
+    tm.end("steer_roadmap_attach");
+    std::vector<int64_t> cnt((size_t)nq);
+    HIPCHK(ctx, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    int64_t total = 0;
+    for (int64_t c : cnt) total += c;
+    return srm_stats(ctx, d_ctr, total);
 }

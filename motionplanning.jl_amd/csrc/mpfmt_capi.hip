@@ -1410,9 +1410,9 @@ static int32_t sssp_ready(mpfmt_ctx* ctx)
     return MPFMT_OK;
 }
 
-// what the tracked cost-to-come field and the external-state queries ask: a Euclidean graph (the repair of kernels_field.hip rests on
-// the Euclidean graph state, and an external state would need a steer to a non-sample; the tracked cost-to-go field of kernels_togo.hip
-// asks sssp_ready alone)
+// what the tracked cost-to-come field and the Euclidean external-state queries ask: a Euclidean graph (the repair of kernels_field.hip
+// rests on the Euclidean graph state, and mpfmt_roadmap_* attach by the Euclidean distance and segment test -- a steering graph has
+// mpfmt_steer_roadmap_*, below; the tracked cost-to-go field of kernels_togo.hip asks sssp_ready alone)
 static int32_t sssp_ready_euclid(mpfmt_ctx* ctx)
 {
     if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "roadmap queries run on an unsharded ctx");
@@ -2048,6 +2048,198 @@ static int32_t steer_point_bitmap(mpfmt_ctx* ctx)
     return steer_upload_bitmap(ctx, F);
 }
 
+// ---- roadmap queries for external states on a resident steering graph (steer_roadmap.h) -------------------------------------
+
+// what every such call asks of the ctx; nothing has been touched when it refuses
+static int32_t steer_roadmap_ready(mpfmt_ctx* ctx)
+{
+    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "roadmap queries run on an unsharded ctx");
+    if (!(ctx->Xo && ctx->steer_filled)) {
+        if (ctx->Xo && ctx->graph_filled)
+            return mpfmt_fail(ctx, MPFMT_ERR_STATE, "steering graphs only: the resident graph is a Euclidean %s graph (mpfmt_roadmap_near / _attach / _query)",
+                              ctx->knn_k > 0 ? "k-nearest" : "r-disc");
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no resident steering graph (mpfmt_di_graph, mpfmt_dubins_graph, mpfmt_reedsshepp_graph, or a steering PRM* planner)");
+    }
+    if (ctx->cc_kind != 0) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "external states need the N-D box checker (the 2-D SAT world is resident)");
+    int32_t rc;
+    if ((rc = sssp_ready(ctx))) return rc;                                  // (swept, and a mask)
+    if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
+    const steer_space s = steer_space_of(ctx, ctx->steer_kind);
+    if (ctx->dw != s.dw || ctx->d != s.d)
+        return mpfmt_fail(ctx, MPFMT_ERR_STATE, "workspace dim %d / state dim %d do not fit the resident steering graph (%d / %d)", ctx->dw, ctx->d, s.dw, s.d);
+    if (ctx->ss.has && ctx->ss.d != ctx->d) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "state-space bounds have %d dims, states %d", ctx->ss.d, ctx->d);
+    return MPFMT_OK;
+}
+
+// is_free_state of nq external states Q [nq][d] (host): the steering planners' predicate, as steer_state_bitmap applies it to the samples
+static int32_t steer_query_states_free(mpfmt_ctx* ctx, const double* Q, int64_t nq, std::vector<uint64_t>& F)
+{
+    const steer_space s = steer_space_of(ctx, ctx->steer_kind);
+    std::vector<double> P((size_t)nq * s.dw);
+    for (int64_t i = 0; i < nq; ++i)
+        for (int q = 0; q < s.dw; ++q) P[(size_t)i * s.dw + q] = Q[(size_t)i * s.d + q];
+    F.assign((size_t)(nq + 63) / 64, 0);
+    const mpfmt_ss keep = ctx->ss;
+    ctx->ss.has = 0;
+    const int32_t rc = mpfmt_states_free(ctx, P.data(), nq, F.data());
+    ctx->ss = keep;
+    if (rc) return rc;
+    if (keep.has)
+        for (int64_t i = 0; i < nq; ++i) {
+            const double* v = Q + (size_t)i * s.d;
+            bool ok = true;
+            for (int q = 0; q < s.d; ++q) ok = ok && (keep.lo[q] <= v[q]) && (v[q] <= keep.hi[q]);
+            if (!ok) F[(size_t)(i >> 6)] &= ~(1ull << (i & 63));
+        }
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_steer_roadmap_near(mpfmt_ctx* ctx, const double* Q, int64_t nq, int32_t direction, int64_t* ptr, int64_t cap, int64_t* idx, double* dist,
+                                 uint64_t* free_mask, int64_t* total)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (nq < 0 || cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_near: nq / cap < 0");
+    if (direction != 0 && direction != 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_near: direction must be 0 (tail) or 1 (head)");
+    if (nq > 0 && (!Q || !ptr || !total)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_near: Q / ptr / total is NULL");
+    if (nq > 0 && cap > 0 && (!idx || !dist || !free_mask)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_near: idx / dist / free_mask is NULL");
+    int32_t rc;
+    if ((rc = steer_roadmap_ready(ctx))) return rc;
+    if (nq == 0) return MPFMT_OK;
+    if ((rc = roadmap_finite(ctx, Q, nq, "steer_roadmap_near"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    mpfmt_tmp tmp;
+    double* dQ = nullptr;
+    if ((rc = up_d(ctx, tmp, Q, (size_t)nq * ctx->d, &dQ))) return rc;
+    mpfmt_rm_list L;
+    if ((rc = mpfmt_steer_roadmap_lists(ctx, tmp, dQ, nq, direction, nullptr, &L, cap == 0, ctx->Xo, ctx->N, false))) return rc;
+    memcpy(ptr, L.ptr_host.data(), sizeof(int64_t) * (size_t)(nq + 1));
+    *total = L.total;
+    if (L.total > cap) return mpfmt_fail(ctx, MPFMT_ERR_CAPACITY, "steer_roadmap_near: %lld entries exceed capacity %lld", (long long)L.total, (long long)cap);
+    if (L.total == 0) return MPFMT_OK;
+    std::vector<uint8_t> bits((size_t)L.total);
+    HIPCHK(ctx, hipMemcpyAsync(idx, L.idx1, sizeof(int64_t) * (size_t)L.total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(dist, L.dist, sizeof(double) * (size_t)L.total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(bits.data(), L.bits, (size_t)L.total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t w = 0; w < (L.total + 63) / 64; ++w) free_mask[w] = 0;
+    for (int64_t e = 0; e < L.total; ++e) if (bits[(size_t)e] & 1) free_mask[e >> 6] |= 1ull << (e & 63);
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_steer_roadmap_attach(mpfmt_ctx* ctx, const double* Q, int64_t nq, const double* C, int64_t* parent, double* cost)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (nq < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_attach: nq < 0");
+    if (nq > 0 && (!Q || !C || !parent || !cost)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_attach: Q / C / parent / cost is NULL");
+    int32_t rc;
+    if ((rc = steer_roadmap_ready(ctx))) return rc;
+    if (nq == 0) return MPFMT_OK;
+    if ((rc = roadmap_finite(ctx, Q, nq, "steer_roadmap_attach"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    mpfmt_tmp tmp;
+    double *dQ = nullptr, *dC = nullptr, *d_cost = nullptr; int64_t* d_par = nullptr;
+    if ((rc = up_d(ctx, tmp, Q, (size_t)nq * ctx->d, &dQ))) return rc;
+    if ((rc = up_d(ctx, tmp, C, (size_t)ctx->N, &dC))) return rc;
+    HIPCHK(ctx, tmp.get(&d_cost, sizeof(double) * (size_t)nq));
+    HIPCHK(ctx, tmp.get(&d_par, sizeof(int64_t) * (size_t)nq));
+    if ((rc = mpfmt_steer_roadmap_reduce(ctx, tmp, dQ, nq, dC, d_cost, d_par))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(parent, d_par, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return MPFMT_OK;
+}
+
+// mpfmt_roadmap_query's loop with three changes: the steering state test, the resident steering bitmap, and the direct edge from a
+// 1 x 1 tail-list evaluation (query s_i against the single "sample" g_i)
+int32_t mpfmt_steer_roadmap_query(mpfmt_ctx* ctx, const double* S, const double* G, int64_t nq, int32_t checkpts, double* cost, int64_t* path_ptr,
+                                  int64_t* path, int64_t path_cap, mpfmt_roadmap_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (nq < 0 || path_cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_query: nq / path_cap < 0");
+    if (nq > 0 && (!S || !G || !cost || !path_ptr || (path_cap > 0 && !path)))
+        return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_query: S / G / cost / path_ptr / path is NULL");
+    int32_t rc;
+    if ((rc = steer_roadmap_ready(ctx))) return rc;
+    if (nq == 0) return MPFMT_OK;
+    if ((rc = roadmap_finite(ctx, S, nq, "steer_roadmap_query (S)"))) return rc;
+    if ((rc = roadmap_finite(ctx, G, nq, "steer_roadmap_query (G)"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int d = ctx->d;
+    const int64_t N = ctx->N;
+    std::vector<uint64_t> fs, fg;
+    if ((rc = steer_query_states_free(ctx, S, nq, fs))) return rc;
+    if ((rc = steer_query_states_free(ctx, G, nq, fg))) return rc;
+    mpfmt_tmp tmp;
+    double *dS = nullptr, *dG = nullptr;
+    if ((rc = up_d(ctx, tmp, S, (size_t)nq * d, &dS))) return rc;
+    if ((rc = up_d(ctx, tmp, G, (size_t)nq * d, &dG))) return rc;
+    if (checkpts && (rc = sssp_resident_bitmap(ctx))) return rc;
+    const uint64_t* d_F = checkpts ? ctx->sssp_F.get() : nullptr;
+    // the direct edges, then all attachments, one count and one fill launch each
+    mpfmt_rm_list Ld, Ls, Lg;
+    if ((rc = mpfmt_steer_roadmap_lists(ctx, tmp, dS, nq, 0, nullptr, &Ld, false, dG, nq, true))) return rc;
+    int64_t cand = ctx->roadmap_candidates, tot = 0, steered = ctx->steer_roadmap_steered;      // (the direct edges are no near-set entries)
+    std::vector<double> dw((size_t)std::max<int64_t>(Ld.total, 1));
+    std::vector<uint8_t> db((size_t)std::max<int64_t>(Ld.total, 1));
+    if (Ld.total > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(dw.data(), Ld.dist, sizeof(double) * (size_t)Ld.total, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(db.data(), Ld.bits, (size_t)Ld.total, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if ((rc = mpfmt_steer_roadmap_lists(ctx, tmp, dS, nq, 0, d_F, &Ls, false, ctx->Xo, N, false))) return rc;
+    cand += ctx->roadmap_candidates; tot += ctx->roadmap_near_total; steered += ctx->steer_roadmap_steered;
+    if ((rc = mpfmt_steer_roadmap_lists(ctx, tmp, dG, nq, 1, nullptr, &Lg, false, ctx->Xo, N, false))) return rc;
+    ctx->roadmap_candidates += cand; ctx->roadmap_near_total += tot; ctx->steer_roadmap_steered += steered;
+    int64_t* d_res = nullptr;
+    HIPCHK(ctx, tmp.get(&d_res, sizeof(int64_t) * (size_t)(N + 8)));
+    int64_t res[3];
+    std::vector<int64_t> hops;
+    int64_t used = 0;
+    bool over = false;
+    path_ptr[0] = 0;
+    for (int64_t q = 0; q < nq; ++q) {
+        mpfmt_roadmap_info inf;
+        memset(&inf, 0, sizeof inf);
+        inf.near_s = Ls.ptr_host[(size_t)q + 1] - Ls.ptr_host[(size_t)q]; inf.usable_s = Ls.usable_host[(size_t)q];
+        inf.near_g = Lg.ptr_host[(size_t)q + 1] - Lg.ptr_host[(size_t)q]; inf.usable_g = Lg.usable_host[(size_t)q];
+        cost[q] = INFINITY;
+        int64_t len = 0;
+        if (!((fs[(size_t)(q >> 6)] >> (q & 63)) & 1ull)) inf.status = 2;
+        else if (!((fg[(size_t)(q >> 6)] >> (q & 63)) & 1ull)) inf.status = 3;
+        else {
+            const int64_t s0 = Ls.ptr_host[(size_t)q];
+            mpfmt_sssp_info fi;
+            if ((rc = mpfmt_sssp_seeded_device(ctx, Ls.idx1 + s0, Ls.dist + s0, Ls.bits + s0, inf.near_s, d_F, &fi))) return rc;
+            inf.rounds = fi.rounds; inf.ms_device = fi.ms_device;
+            if ((rc = mpfmt_roadmap_goal(ctx, Lg, q, ctx->sssp_C, ctx->sssp_A, d_res))) return rc;
+            HIPCHK(ctx, hipMemcpyAsync(res, d_res, sizeof(int64_t) * 3, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            double best; memcpy(&best, &res[0], sizeof best);
+            const int64_t last = res[1];
+            const int64_t e = Ld.ptr_host[(size_t)q];
+            const bool direct = Ld.ptr_host[(size_t)q + 1] > e && (db[(size_t)e] & 1);
+            const double dsg = direct ? dw[(size_t)e] : INFINITY;
+            if (direct && (last == 0 || dsg <= best)) { cost[q] = dsg; inf.status = 0; }
+            else if (last == 0) inf.status = 1;
+            else {
+                cost[q] = best; inf.status = 0; len = res[2];
+                if (used + len <= path_cap) {
+                    hops.resize((size_t)len);
+                    HIPCHK(ctx, hipMemcpyAsync(hops.data(), d_res + 3, sizeof(int64_t) * (size_t)len, hipMemcpyDeviceToHost, ctx->stream));
+                    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+                    for (int64_t i = 0; i < len; ++i) path[used + i] = hops[(size_t)(len - 1 - i)];
+                } else over = true;
+            }
+        }
+        inf.path_len = len;
+        used += len;
+        path_ptr[q + 1] = used;
+        if (info) info[q] = inf;
+    }
+    if (over) return mpfmt_fail(ctx, MPFMT_ERR_CAPACITY, "steer_roadmap_query: %lld path samples exceed capacity %lld", (long long)used, (long long)path_cap);
+    return MPFMT_OK;
+}
+
 // The planners' common prelude: the checks of the ctx against the space, then the states on the host (X) and the checkpts bitmap F,
 // is_free_state(v, CC, SS) = in_state_space(v) && point-vs-obstacles on the workspace coordinates.  The point test runs on the
 // workspace points with the state-space bounds (which have the states' dimension) switched off; they are applied here.
@@ -2596,6 +2788,7 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "sssp_multi_bytes") == 0) { *value = ctx->ms_bytes; return MPFMT_OK; }
     if (strcmp(name, "roadmap_candidates") == 0) { *value = ctx->roadmap_candidates; return MPFMT_OK; }
     if (strcmp(name, "roadmap_near_total") == 0) { *value = ctx->roadmap_near_total; return MPFMT_OK; }
+    if (strcmp(name, "steer_roadmap_steered") == 0) { *value = ctx->steer_roadmap_steered; return MPFMT_OK; }
     if (strcmp(name, "shortcut_tests_evaluated") == 0) { *value = ctx->shortcut_tests; return MPFMT_OK; }
     if (strcmp(name, "shortcut_checks") == 0) { *value = ctx->shortcut_checks; return MPFMT_OK; }
     if (strcmp(name, "steer_swept") == 0) { *value = (ctx->steer_filled && ctx->steer_swept) ? 1 : 0; return MPFMT_OK; }

@@ -418,6 +418,7 @@ struct mpfmt_ctx {
     // ---- roadmap queries for external states (kernels_roadmap.hip, the seeded field of kernels_sssp.hip) ----
     mpfmt_dbuf<double> sssp_seed;         // [N] seed labels of the running pair query (+Inf: no usable edge from the start)
     int64_t roadmap_candidates = 0, roadmap_near_total = 0;      // stats of the last call
+    int64_t steer_roadmap_steered = 0;    // exact steers run by the last call on a steering graph (steer_roadmap.h)
 
     // ---- many-source fields and cost matrices (kernels_sssp_multi.hip): buffers of their own, grow-only ----
     mpfmt_dbuf<double> ms_L;              // [N][64] labels, lane = source
@@ -656,6 +657,11 @@ int32_t mpfmt_roadmap_lists(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, i
                             bool count_only = false);
 int32_t mpfmt_roadmap_reduce(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, const double* d_C, double* d_cost, int64_t* d_parent);
 int32_t mpfmt_roadmap_goal(mpfmt_ctx* ctx, const mpfmt_rm_list& L, int64_t q, const double* d_C, const int64_t* d_A, int64_t* d_res);
+// the same lists and reduction for a resident steering graph (steer_roadmap.h).  d_X / nx: the samples the queries meet (ctx->Xo / N);
+// pair: query i meets d_X[i] alone (the direct edge of pair i, d_X = the goals)
+int32_t mpfmt_steer_roadmap_lists(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, int dir, const uint64_t* d_F, mpfmt_rm_list* out,
+                                  bool count_only, const double* d_X, int64_t nx, bool pair);
+int32_t mpfmt_steer_roadmap_reduce(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, const double* d_C, double* d_cost, int64_t* d_parent);
 
 // kernels_sssp_multi.hip ----------------------------------------------------------------------------
 // nsrc fields (sources 1-based, on the host) in groups of 64 over the resident graph and mask; C_host [nsrc][N], A_host [nsrc][N] or nullptr

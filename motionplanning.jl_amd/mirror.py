@@ -708,15 +708,16 @@ def roadmap_query_(P, starts, goals, checkpts=True):
     """Multi-query use of the roadmap a prmstar_ / fmtstar_ call (connections = "R") left resident in P.ctx: pair queries between states
     that are NOT samples (the robot's present pose, candidate goals) without touching samples, graph or mask (mpfmt_roadmap_query).
     starts / goals: (n, d).  Returns (costs (n,), paths): paths[i] = the states [s, V[path...], g] as an (m, d) array -- it goes straight
-    into P.ctx.adaptive_shortcut -- or None when query i has no solution; metadata["roadmap_info"] holds the per-query info dicts."""
+    into P.ctx.adaptive_shortcut -- or None when query i has no solution; metadata["roadmap_info"] holds the per-query info dicts.
+    In a steering space (DoubleIntegrator, Dubins, Reeds-Shepp) the states attach by the space's own steer (mpfmt_steer_roadmap_query);
+    the paths have the same form and are not Euclidean polylines."""
     if P.solution is None or P.ctx is None:
         raise RuntimeError("roadmap_query_ needs the roadmap of a prmstar_ / fmtstar_ call")
-    if not isinstance(P.SS.dist, Euclidean):
-        raise RuntimeError("roadmap_query_ requires Euclidean SS")
     S = np.ascontiguousarray(np.atleast_2d(np.asarray(starts, dtype=np.float64)))
     G = np.ascontiguousarray(np.atleast_2d(np.asarray(goals, dtype=np.float64)))
     P.CC._bind(P.ctx, P.SS)
-    cost, idx, info = P.ctx.roadmap_query(S, G, checkpts=checkpts)
+    query = P.ctx.roadmap_query if isinstance(P.SS.dist, Euclidean) else P.ctx.steer_roadmap_query
+    cost, idx, info = query(S, G, checkpts=checkpts)
     paths = [np.vstack([S[i:i + 1], P.V.V[idx[i] - 1], G[i:i + 1]]) if info[i]["status"] == 0 else None for i in range(len(idx))]
     P.solution.metadata["roadmap_info"] = info
     return cost, paths
