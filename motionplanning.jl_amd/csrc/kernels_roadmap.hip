@@ -283,84 +283,125 @@ static int32_t rm_launch(mpfmt_ctx* ctx, rm_args& a)
     return MPFMT_OK;
 }
 
-static int32_t rm_stats(mpfmt_ctx* ctx, const unsigned long long* d_ncand, int64_t near_total)
+// ---- the host driver of both spaces ---------------------------------------------------------------------------------------------------------
+// DESIGN.md 7f, "The host driver".  A space supplies its timer name, the number of counters its kernel keeps ([0] pairs (pre-)tested,
+// [1] exact steers run), whether its fill needs the ordering pass, and a callable that copies the driver's slots into its own argument
+// struct -- rm_args, srm_args -- next to the query's own fields, and launches its kernel.  A list or reduce call is ONE timed interval.
+
+struct rm_slots {                        // what the driver owns of a launch
+    int mode;
+    int64_t* near_cnt; int64_t* usable_cnt; unsigned long long* ctr;
+    const int64_t* ptr; double* dist; uint8_t* bits;      // mode 1: the offsets and where the fill writes ...
+    int32_t* idx; int64_t* idx1;                           // ... 0-based in cell order ahead of the ordering pass, else 1-based and final
+};
+typedef std::function<int32_t(const rm_slots&)> rm_launcher;
+
+// the stats of one list or reduce call, left in the ctx (a public call of several sums them: mpfmt_capi.hip)
+static int32_t rm_stats(mpfmt_ctx* ctx, const unsigned long long* d_ctr, int nctr, int64_t near_total)
 {
-    unsigned long long nc = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&nc, d_ncand, sizeof nc, hipMemcpyDeviceToHost, ctx->stream));
+    unsigned long long c[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(c, d_ctr, sizeof(unsigned long long) * (size_t)nctr, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->roadmap_candidates = (int64_t)nc; ctx->roadmap_near_total = near_total;
+    ctx->roadmap_candidates = (int64_t)c[0]; ctx->roadmap_near_total = near_total;
+    if (nctr > 1) ctx->steer_roadmap_steered = (int64_t)c[1];
     return MPFMT_OK;
 }
 
-// the list form: count, offsets (scanned on the host: nq counters), fill, order.  Arrays live in tmp.
+// the list form.  Arrays live in tmp.  count_only: ptr_host / total alone (no list is filled)
+static int32_t rm_drive_lists(mpfmt_ctx* ctx, mpfmt_tmp& tmp, int64_t nq, mpfmt_rm_list* out, bool count_only, const char* timer, int nctr, bool sort,
+                              const rm_launcher& launch)
+{
+    int32_t rc;
+    rm_slots s{};
+    int64_t* d_ptr = nullptr;
+    HIPCHK(ctx, tmp.get(&s.near_cnt, sizeof(int64_t) * (size_t)nq));
+    HIPCHK(ctx, tmp.get(&s.usable_cnt, sizeof(int64_t) * (size_t)nq));
+    HIPCHK(ctx, tmp.get(&d_ptr, sizeof(int64_t) * (size_t)(nq + 1)));
+    HIPCHK(ctx, tmp.get(&s.ctr, sizeof(unsigned long long) * (size_t)nctr));
+    HIPCHK(ctx, hipMemsetAsync(s.ctr, 0, sizeof(unsigned long long) * (size_t)nctr, ctx->stream));
+    mpfmt_timed tm(ctx);
+    s.mode = 0;
+    if ((rc = launch(s))) return rc;
+    out->ptr_host.assign((size_t)nq + 1, 0);
+    HIPCHK(ctx, hipMemcpyAsync(out->ptr_host.data() + 1, s.near_cnt, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < nq; ++i) out->ptr_host[(size_t)i + 1] += out->ptr_host[(size_t)i];
+    const int64_t total = out->ptr_host[(size_t)nq];
+    out->total = total;
+    if (count_only) {
+        tm.end(timer);
+        return rm_stats(ctx, s.ctr, nctr, total);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d_ptr, out->ptr_host.data(), sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice, ctx->stream));
+    double* d_dist2 = nullptr; uint8_t* d_bits2 = nullptr;
+    if (sort) HIPCHK(ctx, tmp.get(&s.idx, sizeof(int32_t) * (size_t)total));
+    HIPCHK(ctx, tmp.get(&s.dist, sizeof(double) * (size_t)total));
+    HIPCHK(ctx, tmp.get(&s.bits, (size_t)total));
+    HIPCHK(ctx, tmp.get(&s.idx1, sizeof(int64_t) * (size_t)total));
+    if (sort) {
+        HIPCHK(ctx, tmp.get(&d_dist2, sizeof(double) * (size_t)total));
+        HIPCHK(ctx, tmp.get(&d_bits2, (size_t)total));
+    }
+    HIPCHK(ctx, hipMemsetAsync(s.ctr, 0, sizeof(unsigned long long) * (size_t)nctr, ctx->stream));
+    s.mode = 1; s.ptr = d_ptr;
+    if ((rc = launch(s))) return rc;
+    if (sort) {
+        hipLaunchKernelGGL(k_roadmap_sort, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, nq, (const int64_t*)d_ptr, (const int32_t*)s.idx,
+                           (const double*)s.dist, (const uint8_t*)s.bits, s.idx1, d_dist2, d_bits2);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    tm.end(timer);
+    out->usable_host.assign((size_t)nq, 0);
+    HIPCHK(ctx, hipMemcpyAsync(out->usable_host.data(), s.usable_cnt, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = rm_stats(ctx, s.ctr, nctr, total))) return rc;
+    out->ptr = d_ptr; out->idx1 = s.idx1; out->dist = sort ? d_dist2 : s.dist; out->bits = sort ? d_bits2 : s.bits;
+    return MPFMT_OK;
+}
+
+// the reduce form: one launch, no list
+static int32_t rm_drive_reduce(mpfmt_ctx* ctx, mpfmt_tmp& tmp, int64_t nq, const char* timer, int nctr, const rm_launcher& launch)
+{
+    int32_t rc;
+    rm_slots s{};
+    HIPCHK(ctx, tmp.get(&s.near_cnt, sizeof(int64_t) * (size_t)nq));
+    HIPCHK(ctx, tmp.get(&s.ctr, sizeof(unsigned long long) * (size_t)nctr));
+    HIPCHK(ctx, hipMemsetAsync(s.ctr, 0, sizeof(unsigned long long) * (size_t)nctr, ctx->stream));
+    mpfmt_timed tm(ctx);
+    s.mode = 2;
+    if ((rc = launch(s))) return rc;
+    tm.end(timer);
+    std::vector<int64_t> cnt((size_t)nq);
+    HIPCHK(ctx, hipMemcpyAsync(cnt.data(), s.near_cnt, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    int64_t total = 0;
+    for (int64_t c : cnt) total += c;
+    return rm_stats(ctx, s.ctr, nctr, total);
+}
+
+// ---- the Euclidean space: k_roadmap (one counter; the fill is in cell order) ----------------------------------------------------------------
+
 int32_t mpfmt_roadmap_lists(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, int dir, const uint64_t* d_F, mpfmt_rm_list* out, bool count_only)
 {
     int32_t rc;
     if ((rc = mpfmt_roadmap_grid(ctx))) return rc;
-    int64_t *d_cnt = nullptr, *d_us = nullptr, *d_ptr = nullptr;
-    unsigned long long* d_nc = nullptr;
-    HIPCHK(ctx, tmp.get(&d_cnt, sizeof(int64_t) * (size_t)nq));
-    HIPCHK(ctx, tmp.get(&d_us, sizeof(int64_t) * (size_t)nq));
-    HIPCHK(ctx, tmp.get(&d_ptr, sizeof(int64_t) * (size_t)(nq + 1)));
-    HIPCHK(ctx, tmp.get(&d_nc, sizeof(unsigned long long)));
-    HIPCHK(ctx, hipMemsetAsync(d_nc, 0, sizeof(unsigned long long), ctx->stream));
-    mpfmt_timed tm(ctx);
-    rm_args a{};
-    a.Q = d_Q; a.nq = nq; a.dir = dir; a.mode = 0; a.F = d_F; a.near_cnt = d_cnt; a.usable_cnt = d_us; a.ncand = d_nc;
-    if ((rc = rm_launch(ctx, a))) return rc;
-    out->ptr_host.assign((size_t)nq + 1, 0);
-    HIPCHK(ctx, hipMemcpyAsync(out->ptr_host.data() + 1, d_cnt, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int64_t i = 0; i < nq; ++i) out->ptr_host[(size_t)i + 1] += out->ptr_host[(size_t)i];
-    const int64_t total = out->ptr_host[(size_t)nq];
-    if (count_only) {
-        tm.end("roadmap_near");
-        out->total = total;
-        return rm_stats(ctx, d_nc, total);
-    }
-    HIPCHK(ctx, hipMemcpyAsync(d_ptr, out->ptr_host.data(), sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice, ctx->stream));
-    int32_t* d_idx = nullptr; double *d_dist = nullptr, *d_dist2 = nullptr; uint8_t *d_bits = nullptr, *d_bits2 = nullptr; int64_t* d_idx1 = nullptr;
-    HIPCHK(ctx, tmp.get(&d_idx, sizeof(int32_t) * (size_t)total));
-    HIPCHK(ctx, tmp.get(&d_dist, sizeof(double) * (size_t)total));
-    HIPCHK(ctx, tmp.get(&d_bits, (size_t)total));
-    HIPCHK(ctx, tmp.get(&d_idx1, sizeof(int64_t) * (size_t)total));
-    HIPCHK(ctx, tmp.get(&d_dist2, sizeof(double) * (size_t)total));
-    HIPCHK(ctx, tmp.get(&d_bits2, (size_t)total));
-    HIPCHK(ctx, hipMemsetAsync(d_nc, 0, sizeof(unsigned long long), ctx->stream));
-    a.mode = 1; a.ptr = d_ptr; a.idx = d_idx; a.dist = d_dist; a.bits = d_bits;
-    if ((rc = rm_launch(ctx, a))) return rc;
-    hipLaunchKernelGGL(k_roadmap_sort, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, nq, (const int64_t*)d_ptr, (const int32_t*)d_idx,
-                       (const double*)d_dist, (const uint8_t*)d_bits, d_idx1, d_dist2, d_bits2);
-    HIPCHK(ctx, hipGetLastError());
-    tm.end("roadmap_near");
-    out->usable_host.assign((size_t)nq, 0);
-    HIPCHK(ctx, hipMemcpyAsync(out->usable_host.data(), d_us, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = rm_stats(ctx, d_nc, total))) return rc;
-    out->ptr = d_ptr; out->idx1 = d_idx1; out->dist = d_dist2; out->bits = d_bits2; out->total = total;
-    return MPFMT_OK;
+    return rm_drive_lists(ctx, tmp, nq, out, count_only, "roadmap_near", 1, true, [&](const rm_slots& s) {
+        rm_args a{};
+        a.Q = d_Q; a.nq = nq; a.dir = dir; a.mode = s.mode; a.F = d_F; a.near_cnt = s.near_cnt; a.usable_cnt = s.usable_cnt; a.ncand = s.ctr;
+        a.ptr = s.ptr; a.idx = s.idx; a.dist = s.dist; a.bits = s.bits;
+        return rm_launch(ctx, a);
+    });
 }
 
-// the reduce form over a device field d_C [N]
+// the reduce form over a device field d_C [N]: head direction
 int32_t mpfmt_roadmap_reduce(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, const double* d_C, double* d_cost, int64_t* d_parent)
 {
     int32_t rc;
     if ((rc = mpfmt_roadmap_grid(ctx))) return rc;
-    int64_t* d_cnt = nullptr;
-    unsigned long long* d_nc = nullptr;
-    HIPCHK(ctx, tmp.get(&d_cnt, sizeof(int64_t) * (size_t)nq));
-    HIPCHK(ctx, tmp.get(&d_nc, sizeof(unsigned long long)));
-    HIPCHK(ctx, hipMemsetAsync(d_nc, 0, sizeof(unsigned long long), ctx->stream));
-    mpfmt_timed tm(ctx);
-    rm_args a{};
-    a.Q = d_Q; a.nq = nq; a.dir = 1; a.mode = 2; a.near_cnt = d_cnt; a.C = d_C; a.best_cost = d_cost; a.best_parent = d_parent; a.ncand = d_nc;
-    if ((rc = rm_launch(ctx, a))) return rc;
-    tm.end("roadmap_attach");
-    std::vector<int64_t> cnt((size_t)nq);
-    HIPCHK(ctx, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    int64_t total = 0;
-    for (int64_t c : cnt) total += c;
-    return rm_stats(ctx, d_nc, total);
+    return rm_drive_reduce(ctx, tmp, nq, "roadmap_attach", 1, [&](const rm_slots& s) {
+        rm_args a{};
+        a.Q = d_Q; a.nq = nq; a.dir = 1; a.mode = s.mode; a.near_cnt = s.near_cnt; a.C = d_C; a.best_cost = d_cost; a.best_parent = d_parent; a.ncand = s.ctr;
+        return rm_launch(ctx, a);
+    });
 }
 
 int32_t mpfmt_roadmap_goal(mpfmt_ctx* ctx, const mpfmt_rm_list& L, int64_t q, const double* d_C, const int64_t* d_A, int64_t* d_res)
@@ -371,7 +412,7 @@ int32_t mpfmt_roadmap_goal(mpfmt_ctx* ctx, const mpfmt_rm_list& L, int64_t q, co
     return MPFMT_OK;
 }
 
-// ---- the same lists for a resident steering graph (steer_roadmap.h; k_di_roadmap in kernels_di.hip, k_car_roadmap in kernels_car.hip) ------
+// ---- the steering spaces (steer_roadmap.h; k_di_roadmap in kernels_di.hip, k_car_roadmap in kernels_car.hip): two counters ------------------
 // d_X / nx: the samples the queries meet -- ctx->Xo / N, or with pair the goals of a pair query (query i meets d_X[i] alone: the direct
 // edge).  Lists come out of the fill in ascending order: no ordering pass.
 
@@ -380,76 +421,25 @@ static int32_t srm_launch(mpfmt_ctx* ctx, srm_args& a)
     return ctx->steer_kind == MPFMT_STEER_DI ? mpfmt_di_roadmap_launch(ctx, a) : mpfmt_car_roadmap_launch(ctx, a);
 }
 
-static int32_t srm_stats(mpfmt_ctx* ctx, const unsigned long long* d_ctr, int64_t near_total)
-{
-    unsigned long long c[2] = {0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(c, d_ctr, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->roadmap_candidates = (int64_t)c[0]; ctx->steer_roadmap_steered = (int64_t)c[1]; ctx->roadmap_near_total = near_total;
-    return MPFMT_OK;
-}
-
 int32_t mpfmt_steer_roadmap_lists(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, int dir, const uint64_t* d_F, mpfmt_rm_list* out,
                                   bool count_only, const double* d_X, int64_t nx, bool pair)
 {
-    int32_t rc;
-    int64_t *d_cnt = nullptr, *d_us = nullptr, *d_ptr = nullptr;
-    unsigned long long* d_ctr = nullptr;
-    HIPCHK(ctx, tmp.get(&d_cnt, sizeof(int64_t) * (size_t)nq));
-    HIPCHK(ctx, tmp.get(&d_us, sizeof(int64_t) * (size_t)nq));
-    HIPCHK(ctx, tmp.get(&d_ptr, sizeof(int64_t) * (size_t)(nq + 1)));
-    HIPCHK(ctx, tmp.get(&d_ctr, 2 * sizeof(unsigned long long)));
-    HIPCHK(ctx, hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    mpfmt_timed tm(ctx);
-    srm_args a{};
-    a.Q = d_Q; a.nq = nq; a.dir = dir; a.mode = 0; a.X = d_X; a.N = nx; a.pair = pair ? 1 : 0; a.F = d_F;
-    a.near_cnt = d_cnt; a.usable_cnt = d_us; a.ctr = d_ctr;
-    if ((rc = srm_launch(ctx, a))) return rc;
-    out->ptr_host.assign((size_t)nq + 1, 0);
-    HIPCHK(ctx, hipMemcpyAsync(out->ptr_host.data() + 1, d_cnt, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int64_t i = 0; i < nq; ++i) out->ptr_host[(size_t)i + 1] += out->ptr_host[(size_t)i];
-    const int64_t total = out->ptr_host[(size_t)nq];
-    if (count_only) {
-        tm.end("steer_roadmap_near");
-        out->total = total;
-        return srm_stats(ctx, d_ctr, total);
-    }
-    HIPCHK(ctx, hipMemcpyAsync(d_ptr, out->ptr_host.data(), sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice, ctx->stream));
-    int64_t* d_idx1 = nullptr; double* d_dist = nullptr; uint8_t* d_bits = nullptr;
-    HIPCHK(ctx, tmp.get(&d_idx1, sizeof(int64_t) * (size_t)total));
-    HIPCHK(ctx, tmp.get(&d_dist, sizeof(double) * (size_t)total));
-    HIPCHK(ctx, tmp.get(&d_bits, (size_t)total));
-    HIPCHK(ctx, hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    a.mode = 1; a.ptr = d_ptr; a.idx1 = d_idx1; a.dist = d_dist; a.bits = d_bits;
-    if ((rc = srm_launch(ctx, a))) return rc;
-    tm.end("steer_roadmap_near");
-    out->usable_host.assign((size_t)nq, 0);
-    HIPCHK(ctx, hipMemcpyAsync(out->usable_host.data(), d_us, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = srm_stats(ctx, d_ctr, total))) return rc;
-    out->ptr = d_ptr; out->idx1 = d_idx1; out->dist = d_dist; out->bits = d_bits; out->total = total;
-    return MPFMT_OK;
+    return rm_drive_lists(ctx, tmp, nq, out, count_only, "steer_roadmap_near", 2, false, [&](const rm_slots& s) {
+        srm_args a{};
+        a.Q = d_Q; a.nq = nq; a.dir = dir; a.mode = s.mode; a.X = d_X; a.N = nx; a.pair = pair ? 1 : 0; a.F = d_F;
+        a.near_cnt = s.near_cnt; a.usable_cnt = s.usable_cnt; a.ctr = s.ctr;
+        a.ptr = s.ptr; a.idx1 = s.idx1; a.dist = s.dist; a.bits = s.bits;
+        return srm_launch(ctx, a);
+    });
 }
 
-// the reduce form over a device field d_C [N]: head direction, one launch, no list
+// the reduce form over a device field d_C [N]: head direction
 int32_t mpfmt_steer_roadmap_reduce(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, const double* d_C, double* d_cost, int64_t* d_parent)
 {
-    int32_t rc;
-    int64_t* d_cnt = nullptr;
-    unsigned long long* d_ctr = nullptr;
-    HIPCHK(ctx, tmp.get(&d_cnt, sizeof(int64_t) * (size_t)nq));
-    HIPCHK(ctx, tmp.get(&d_ctr, 2 * sizeof(unsigned long long)));
-    HIPCHK(ctx, hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    mpfmt_timed tm(ctx);
-    srm_args a{};
-    a.Q = d_Q; a.nq = nq; a.dir = 1; a.mode = 2; a.X = ctx->Xo; a.N = ctx->N; a.near_cnt = d_cnt; a.C = d_C; a.best_cost = d_cost;
-    a.best_parent = d_parent; a.ctr = d_ctr;
-    if ((rc = srm_launch(ctx, a))) return rc;
-    tm.end("steer_roadmap_attach");
-    std::vector<int64_t> cnt((size_t)nq);
-    HIPCHK(ctx, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    int64_t total = 0;
-    for (int64_t c : cnt) total += c;
-    return srm_stats(ctx, d_ctr, total);
+    return rm_drive_reduce(ctx, tmp, nq, "steer_roadmap_attach", 2, [&](const rm_slots& s) {
+        srm_args a{};
+        a.Q = d_Q; a.nq = nq; a.dir = 1; a.mode = s.mode; a.X = ctx->Xo; a.N = ctx->N; a.near_cnt = s.near_cnt; a.C = d_C; a.best_cost = d_cost;
+        a.best_parent = d_parent; a.ctr = s.ctr;
+        return srm_launch(ctx, a);
+    });
 }

@@ -1662,215 +1662,6 @@ static int32_t roadmap_ready(mpfmt_ctx* ctx)
     return MPFMT_OK;
 }
 
-static int32_t roadmap_finite(mpfmt_ctx* ctx, const double* Q, int64_t nq, const char* what)
-{
-    for (int64_t i = 0; i < nq * ctx->d; ++i)
-        if (!std::isfinite(Q[i])) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%s: non-finite coordinate in state %lld", what, (long long)(i / ctx->d + 1));
-    return MPFMT_OK;
-}
-
-static int32_t up_d(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* h, size_t n, double** d)
-{
-    HIPCHK(ctx, tmp.get(d, sizeof(double) * n));
-    HIPCHK(ctx, hipMemcpyAsync(*d, h, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    return MPFMT_OK;
-}
-
-int32_t mpfmt_roadmap_near(mpfmt_ctx* ctx, const double* Q, int64_t nq, int32_t direction, int64_t* ptr, int64_t cap, int64_t* idx, double* dist,
-                           uint64_t* free_mask, int64_t* total)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (nq < 0 || cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_near: nq / cap < 0");
-    if (direction != 0 && direction != 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_near: direction must be 0 (tail) or 1 (head)");
-    if (nq > 0 && (!Q || !ptr || !total)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_near: Q / ptr / total is NULL");
-    if (nq > 0 && cap > 0 && (!idx || !dist || !free_mask)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_near: idx / dist / free_mask is NULL");
-    int32_t rc;
-    if ((rc = roadmap_ready(ctx))) return rc;
-    if (nq == 0) return MPFMT_OK;
-    if ((rc = roadmap_finite(ctx, Q, nq, "roadmap_near"))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    mpfmt_tmp tmp;
-    double* dQ = nullptr;
-    if ((rc = up_d(ctx, tmp, Q, (size_t)nq * ctx->d, &dQ))) return rc;
-    mpfmt_rm_list L;
-    if ((rc = mpfmt_roadmap_lists(ctx, tmp, dQ, nq, direction, nullptr, &L, cap == 0))) return rc;      // (cap == 0 asks for the sizes: the count pass alone)
-    memcpy(ptr, L.ptr_host.data(), sizeof(int64_t) * (size_t)(nq + 1));
-    *total = L.total;
-    if (L.total > cap) return mpfmt_fail(ctx, MPFMT_ERR_CAPACITY, "roadmap_near: %lld entries exceed capacity %lld", (long long)L.total, (long long)cap);
-    if (L.total == 0) return MPFMT_OK;
-    std::vector<uint8_t> bits((size_t)L.total);
-    HIPCHK(ctx, hipMemcpyAsync(idx, L.idx1, sizeof(int64_t) * (size_t)L.total, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dist, L.dist, sizeof(double) * (size_t)L.total, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(bits.data(), L.bits, (size_t)L.total, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int64_t w = 0; w < (L.total + 63) / 64; ++w) free_mask[w] = 0;
-    for (int64_t e = 0; e < L.total; ++e) if (bits[(size_t)e] & 1) free_mask[e >> 6] |= 1ull << (e & 63);
-    return MPFMT_OK;
-}
-
-int32_t mpfmt_roadmap_attach(mpfmt_ctx* ctx, const double* Q, int64_t nq, const double* C, int64_t* parent, double* cost)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (nq < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_attach: nq < 0");
-    if (nq > 0 && (!Q || !C || !parent || !cost)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_attach: Q / C / parent / cost is NULL");
-    int32_t rc;
-    if ((rc = roadmap_ready(ctx))) return rc;
-    if (nq == 0) return MPFMT_OK;
-    if ((rc = roadmap_finite(ctx, Q, nq, "roadmap_attach"))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    mpfmt_tmp tmp;
-    double *dQ = nullptr, *dC = nullptr, *d_cost = nullptr; int64_t* d_par = nullptr;
-    if ((rc = up_d(ctx, tmp, Q, (size_t)nq * ctx->d, &dQ))) return rc;
-    if ((rc = up_d(ctx, tmp, C, (size_t)ctx->N, &dC))) return rc;
-    HIPCHK(ctx, tmp.get(&d_cost, sizeof(double) * (size_t)nq));
-    HIPCHK(ctx, tmp.get(&d_par, sizeof(int64_t) * (size_t)nq));
-    if ((rc = mpfmt_roadmap_reduce(ctx, tmp, dQ, nq, dC, d_cost, d_par))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(parent, d_par, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return MPFMT_OK;
-}
-
-int32_t mpfmt_roadmap_query(mpfmt_ctx* ctx, const double* S, const double* G, int64_t nq, int32_t checkpts, double* cost, int64_t* path_ptr,
-                            int64_t* path, int64_t path_cap, mpfmt_roadmap_info* info)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (nq < 0 || path_cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_query: nq / path_cap < 0");
-    if (nq > 0 && (!S || !G || !cost || !path_ptr || (path_cap > 0 && !path))) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_query: S / G / cost / path_ptr / path is NULL");
-    int32_t rc;
-    if ((rc = roadmap_ready(ctx))) return rc;
-    if (nq == 0) return MPFMT_OK;
-    if ((rc = roadmap_finite(ctx, S, nq, "roadmap_query (S)"))) return rc;
-    if ((rc = roadmap_finite(ctx, G, nq, "roadmap_query (G)"))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int d = ctx->d;
-    const int64_t N = ctx->N, words = (nq + 63) / 64;
-    mpfmt_tmp tmp;
-    double *dS = nullptr, *dG = nullptr;
-    if ((rc = up_d(ctx, tmp, S, (size_t)nq * d, &dS))) return rc;
-    if ((rc = up_d(ctx, tmp, G, (size_t)nq * d, &dG))) return rc;
-    // the two states of every pair and the direct edge
-    uint64_t* d_m = nullptr;
-    HIPCHK(ctx, tmp.get(&d_m, sizeof(uint64_t) * 3 * (size_t)words));
-    if ((rc = mpfmt_launch_states_free(ctx, dS, nq, d_m))) return rc;
-    if ((rc = mpfmt_launch_states_free(ctx, dG, nq, d_m + words))) return rc;
-    if ((rc = mpfmt_launch_motions_free(ctx, dS, dG, nq, d_m + 2 * words))) return rc;
-    std::vector<uint64_t> m((size_t)(3 * words));
-    HIPCHK(ctx, hipMemcpyAsync(m.data(), d_m, sizeof(uint64_t) * 3 * (size_t)words, hipMemcpyDeviceToHost, ctx->stream));
-    if (checkpts && (rc = sssp_point_bitmap(ctx))) return rc;
-    const uint64_t* d_F = checkpts ? ctx->sssp_F.get() : nullptr;
-    // all attachments, one launch each way
-    mpfmt_rm_list Ls, Lg;
-    if ((rc = mpfmt_roadmap_lists(ctx, tmp, dS, nq, 0, d_F, &Ls))) return rc;
-    const int64_t cand_s = ctx->roadmap_candidates, tot_s = ctx->roadmap_near_total;
-    if ((rc = mpfmt_roadmap_lists(ctx, tmp, dG, nq, 1, nullptr, &Lg))) return rc;
-    ctx->roadmap_candidates += cand_s; ctx->roadmap_near_total += tot_s;
-    int64_t* d_res = nullptr;
-    HIPCHK(ctx, tmp.get(&d_res, sizeof(int64_t) * (size_t)(N + 8)));
-    int64_t res[3];
-    std::vector<int64_t> hops;
-    const double r2 = ctx->graph_r * ctx->graph_r;
-    int64_t used = 0;
-    bool over = false;
-    path_ptr[0] = 0;
-    for (int64_t q = 0; q < nq; ++q) {
-        mpfmt_roadmap_info inf;
-        memset(&inf, 0, sizeof inf);
-        inf.near_s = Ls.ptr_host[(size_t)q + 1] - Ls.ptr_host[(size_t)q]; inf.usable_s = Ls.usable_host[(size_t)q];
-        inf.near_g = Lg.ptr_host[(size_t)q + 1] - Lg.ptr_host[(size_t)q]; inf.usable_g = Lg.usable_host[(size_t)q];
-        cost[q] = INFINITY;
-        int64_t len = 0;
-        if (!((m[(size_t)(q >> 6)] >> (q & 63)) & 1ull)) inf.status = 2;
-        else if (!((m[(size_t)(words + (q >> 6))] >> (q & 63)) & 1ull)) inf.status = 3;
-        else {
-            const int64_t s0 = Ls.ptr_host[(size_t)q];
-            mpfmt_sssp_info fi;
-            if ((rc = mpfmt_sssp_seeded_device(ctx, Ls.idx1 + s0, Ls.dist + s0, Ls.bits + s0, inf.near_s, d_F, &fi))) return rc;
-            inf.rounds = fi.rounds; inf.ms_device = fi.ms_device;
-            if ((rc = mpfmt_roadmap_goal(ctx, Lg, q, ctx->sssp_C, ctx->sssp_A, d_res))) return rc;
-            HIPCHK(ctx, hipMemcpyAsync(res, d_res, sizeof(int64_t) * 3, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            double best; memcpy(&best, &res[0], sizeof best);
-            const int64_t last = res[1];
-            double dsg2 = 0.0;
-            for (int i = 0; i < d; ++i) { const double t = S[q * d + i] - G[q * d + i]; const double tt = t * t; dsg2 = (i == 0) ? tt : dsg2 + tt; }
-            const bool direct = dsg2 <= r2 && ((m[(size_t)(2 * words + (q >> 6))] >> (q & 63)) & 1ull);
-            const double dsg = std::sqrt(dsg2);
-            if (direct && (last == 0 || dsg <= best)) { cost[q] = dsg; inf.status = 0; }
-            else if (last == 0) inf.status = 1;
-            else {
-                cost[q] = best; inf.status = 0; len = res[2];
-                if (used + len <= path_cap) {
-                    hops.resize((size_t)len);
-                    HIPCHK(ctx, hipMemcpyAsync(hops.data(), d_res + 3, sizeof(int64_t) * (size_t)len, hipMemcpyDeviceToHost, ctx->stream));
-                    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                    for (int64_t i = 0; i < len; ++i) path[used + i] = hops[(size_t)(len - 1 - i)];
-                } else over = true;
-            }
-        }
-        inf.path_len = len;
-        used += len;
-        path_ptr[q + 1] = used;
-        if (info) info[q] = inf;
-    }
-    if (over) return mpfmt_fail(ctx, MPFMT_ERR_CAPACITY, "roadmap_query: %lld path samples exceed capacity %lld", (long long)used, (long long)path_cap);
-    return MPFMT_OK;
-}
-
-// the ns x ng cost matrix between external starts and goals at the price of ns fields (kernels_sssp_multi.hip)
-int32_t mpfmt_roadmap_matrix(mpfmt_ctx* ctx, const double* S, int64_t ns, const double* G, int64_t ng, int32_t checkpts, double* cost, int32_t* status,
-                             mpfmt_roadmap_matrix_info* info)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (ns < 0 || ng < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_matrix: ns / ng < 0");
-    if (ns > 0 && ng > 0 && (!S || !G || !cost)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_matrix: S / G / cost is NULL");
-    int32_t rc;
-    if ((rc = roadmap_ready(ctx))) return rc;
-    if (info) memset(info, 0, sizeof *info);
-    if (ns == 0 || ng == 0) return MPFMT_OK;
-    if ((rc = roadmap_finite(ctx, S, ns, "roadmap_matrix (S)"))) return rc;
-    if ((rc = roadmap_finite(ctx, G, ng, "roadmap_matrix (G)"))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int d = ctx->d;
-    const int64_t np = ns * ng, ws = (ns + 63) / 64, wg = (ng + 63) / 64, wp = (np + 63) / 64;
-    mpfmt_tmp tmp;
-    double *dS = nullptr, *dG = nullptr, *dP = nullptr, *dQ = nullptr, *d_cost = nullptr;
-    int32_t* d_status = nullptr;
-    if ((rc = up_d(ctx, tmp, S, (size_t)ns * d, &dS))) return rc;
-    if ((rc = up_d(ctx, tmp, G, (size_t)ng * d, &dG))) return rc;
-    // the states of both sides and the direct edge of every pair: the tests of the pair query, through the same kernels
-    uint64_t* d_m = nullptr;
-    HIPCHK(ctx, tmp.get(&d_m, sizeof(uint64_t) * (size_t)(ws + wg + wp)));
-    HIPCHK(ctx, tmp.get(&dP, sizeof(double) * (size_t)np * d));
-    HIPCHK(ctx, tmp.get(&dQ, sizeof(double) * (size_t)np * d));
-    HIPCHK(ctx, tmp.get(&d_cost, sizeof(double) * (size_t)np));
-    HIPCHK(ctx, tmp.get(&d_status, sizeof(int32_t) * (size_t)np));
-    if ((rc = mpfmt_launch_states_free(ctx, dS, ns, d_m))) return rc;
-    if ((rc = mpfmt_launch_states_free(ctx, dG, ng, d_m + ws))) return rc;
-    if ((rc = mpfmt_roadmap_pairs(ctx, dS, ns, dG, ng, dP, dQ))) return rc;
-    if ((rc = mpfmt_launch_motions_free(ctx, dP, dQ, np, d_m + ws + wg))) return rc;
-    if (checkpts && (rc = sssp_point_bitmap(ctx))) return rc;
-    const uint64_t* d_F = checkpts ? ctx->sssp_F.get() : nullptr;
-    // all attachments, one launch each way
-    mpfmt_rm_list Ls, Lg;
-    if ((rc = mpfmt_roadmap_lists(ctx, tmp, dS, ns, 0, d_F, &Ls))) return rc;
-    const int64_t cand_s = ctx->roadmap_candidates, tot_s = ctx->roadmap_near_total;
-    if ((rc = mpfmt_roadmap_lists(ctx, tmp, dG, ng, 1, nullptr, &Lg))) return rc;
-    ctx->roadmap_candidates += cand_s; ctx->roadmap_near_total += tot_s;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // (the lists' usable counts have arrived)
-    mpfmt_roadmap_matrix_info inf;
-    memset(&inf, 0, sizeof inf);
-    if ((rc = mpfmt_roadmap_matrix_device(ctx, dS, ns, dG, ng, d_F, d_m, d_m + ws, d_m + ws + wg, Ls, Lg, d_cost, d_status, &inf))) return rc;
-    inf.near_s = Ls.total; inf.near_g = Lg.total;
-    for (int64_t v : Ls.usable_host) inf.usable_s += v;
-    for (int64_t v : Lg.usable_host) inf.usable_g += v;
-    HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIPCHK(ctx, hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (info) *info = inf;
-    return MPFMT_OK;
-}
-
 // ---- adaptive shortcutting of solution paths (kernels_shortcut.hip; host reference: mpfmt_host_adaptive_shortcut) ------------------------
 
 int32_t mpfmt_adaptive_shortcut_batch(mpfmt_ctx* ctx, const double* P, const int64_t* offsets, int64_t B, int32_t iterations, int64_t max_states,
@@ -2005,28 +1796,37 @@ static steer_space steer_space_of(const mpfmt_ctx* ctx, mpfmt_steer kind)
     return {kind, 3, 2, kind == MPFMT_STEER_REEDSSHEPP};
 }
 
-// is_free_state of every sample of a steering space: the states on the host (X) and the bitmap F.  Shared by the planners' prelude and
-// by the checkpts bitmap of the fields over a resident steering graph (steer_point_bitmap).
-static int32_t steer_state_bitmap(mpfmt_ctx* ctx, const steer_space& s, std::vector<double>& X, std::vector<uint64_t>& F)
+// is_free_state(v, CC, SS) = in_state_space(v) && point-vs-obstacles on the workspace coordinates, of n states V [n][d] on the host
+// into the bitmap F.  The point test runs on the workspace points with the state-space bounds (which have the states' dimension)
+// switched off; they are applied here.  Shared by the samples' bitmap (steer_state_bitmap) and the external states of a pair query.
+static int32_t steer_states_free(mpfmt_ctx* ctx, const steer_space& s, const double* V, int64_t n, std::vector<uint64_t>& F)
 {
-    const int64_t N = ctx->N;
-    int32_t rc;
-    std::vector<double> P;
-    if ((rc = mpfmt_states_host(ctx, s.dw, X, P))) return rc;
-    F.assign((size_t)(N + 63) / 64, 0);
+    std::vector<double> P((size_t)n * s.dw);
+    for (int64_t i = 0; i < n; ++i)
+        for (int q = 0; q < s.dw; ++q) P[(size_t)i * s.dw + q] = V[(size_t)i * s.d + q];
+    F.assign((size_t)(n + 63) / 64, 0);
     const mpfmt_ss keep = ctx->ss;
     ctx->ss.has = 0;
-    rc = mpfmt_states_free(ctx, P.data(), N, F.data());
+    const int32_t rc = mpfmt_states_free(ctx, P.data(), n, F.data());
     ctx->ss = keep;
     if (rc) return rc;
     if (keep.has)
-        for (int64_t i = 0; i < N; ++i) {
-            const double* v = &X[(size_t)i * s.d];
+        for (int64_t i = 0; i < n; ++i) {
+            const double* v = V + (size_t)i * s.d;
             bool ok = true;
             for (int q = 0; q < s.d; ++q) ok = ok && (keep.lo[q] <= v[q]) && (v[q] <= keep.hi[q]);
-            if (!ok) F[i >> 6] &= ~(1ull << (i & 63));
+            if (!ok) F[(size_t)(i >> 6)] &= ~(1ull << (i & 63));
         }
     return MPFMT_OK;
+}
+
+// that predicate over every sample: the states on the host (X) and the bitmap F.  Shared by the planners' prelude and by the checkpts
+// bitmap of the fields over a resident steering graph (steer_point_bitmap).
+static int32_t steer_state_bitmap(mpfmt_ctx* ctx, const steer_space& s, std::vector<double>& X, std::vector<uint64_t>& F)
+{
+    X.resize((size_t)ctx->N * ctx->d);
+    HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * X.size(), hipMemcpyDeviceToHost));
+    return steer_states_free(ctx, s, X.data(), ctx->N, F);
 }
 
 // that bitmap for the resident steering graph, left on the device in ctx->sssp_F (allocated by the caller)
@@ -2071,50 +1871,73 @@ static int32_t steer_roadmap_ready(mpfmt_ctx* ctx)
     return MPFMT_OK;
 }
 
-// is_free_state of nq external states Q [nq][d] (host): the steering planners' predicate, as steer_state_bitmap applies it to the samples
-static int32_t steer_query_states_free(mpfmt_ctx* ctx, const double* Q, int64_t nq, std::vector<uint64_t>& F)
+// ---- the calls on external states, Euclidean and steering: one body per call --------------------------------------------
+// A public call names its space.  The spaces differ in the ready check, the prefix of the call's name in messages, how the free bits of the
+// external states are obtained, the checkpts bitmap, the list / reduce launchers and the direct edge of a pair: each is a switch on `steer`
+// in one of the helpers below, and the bodies have none.
+
+struct ext_call {                        // one public call: its space, its temporaries, its stats (a running sum over its list calls)
+    mpfmt_ctx* ctx; bool steer;
+    mpfmt_tmp tmp;
+    int64_t cand = 0, near = 0, steered = 0;
+    const char* pre() const { return steer ? "steer_" : ""; }
+};
+
+static int32_t ext_ready(ext_call& c) { return c.steer ? steer_roadmap_ready(c.ctx) : roadmap_ready(c.ctx); }
+
+static int32_t ext_finite(ext_call& c, const double* Q, int64_t nq, const char* call)
 {
-    const steer_space s = steer_space_of(ctx, ctx->steer_kind);
-    std::vector<double> P((size_t)nq * s.dw);
-    for (int64_t i = 0; i < nq; ++i)
-        for (int q = 0; q < s.dw; ++q) P[(size_t)i * s.dw + q] = Q[(size_t)i * s.d + q];
-    F.assign((size_t)(nq + 63) / 64, 0);
-    const mpfmt_ss keep = ctx->ss;
-    ctx->ss.has = 0;
-    const int32_t rc = mpfmt_states_free(ctx, P.data(), nq, F.data());
-    ctx->ss = keep;
-    if (rc) return rc;
-    if (keep.has)
-        for (int64_t i = 0; i < nq; ++i) {
-            const double* v = Q + (size_t)i * s.d;
-            bool ok = true;
-            for (int q = 0; q < s.d; ++q) ok = ok && (keep.lo[q] <= v[q]) && (v[q] <= keep.hi[q]);
-            if (!ok) F[(size_t)(i >> 6)] &= ~(1ull << (i & 63));
-        }
+    for (int64_t i = 0; i < nq * c.ctx->d; ++i)
+        if (!std::isfinite(Q[i]))
+            return mpfmt_fail(c.ctx, MPFMT_ERR_ARG, "%sroadmap_%s: non-finite coordinate in state %lld", c.pre(), call, (long long)(i / c.ctx->d + 1));
     return MPFMT_OK;
 }
 
-int32_t mpfmt_steer_roadmap_near(mpfmt_ctx* ctx, const double* Q, int64_t nq, int32_t direction, int64_t* ptr, int64_t cap, int64_t* idx, double* dist,
-                                 uint64_t* free_mask, int64_t* total)
+static int32_t up_d(ext_call& c, const double* h, size_t n, double** d)
+{
+    HIPCHK(c.ctx, c.tmp.get(d, sizeof(double) * n));
+    HIPCHK(c.ctx, hipMemcpyAsync(*d, h, sizeof(double) * n, hipMemcpyHostToDevice, c.ctx->stream));
+    return MPFMT_OK;
+}
+
+// One list call of the public call; its stats join the call's sums, which the ctx holds from then on.  d_pair (steering): query i meets
+// d_pair[i] alone -- the direct edges, which count as candidates and steers and are no near-set entries.
+static int32_t ext_lists(ext_call& c, const double* dQ, int64_t nq, int dir, const uint64_t* d_F, mpfmt_rm_list* L, bool count_only = false,
+                         const double* d_pair = nullptr)
+{
+    mpfmt_ctx* ctx = c.ctx;
+    const int32_t rc = !c.steer ? mpfmt_roadmap_lists(ctx, c.tmp, dQ, nq, dir, d_F, L, count_only)
+                     : d_pair   ? mpfmt_steer_roadmap_lists(ctx, c.tmp, dQ, nq, dir, d_F, L, count_only, d_pair, nq, true)
+                                : mpfmt_steer_roadmap_lists(ctx, c.tmp, dQ, nq, dir, d_F, L, count_only, ctx->Xo, ctx->N, false);
+    if (rc) return rc;
+    ctx->roadmap_candidates = c.cand += ctx->roadmap_candidates;
+    ctx->roadmap_near_total = c.near += d_pair ? 0 : ctx->roadmap_near_total;
+    if (c.steer) ctx->steer_roadmap_steered = c.steered += ctx->steer_roadmap_steered;
+    return MPFMT_OK;
+}
+
+static int32_t ext_near(mpfmt_ctx* ctx, bool steer, const double* Q, int64_t nq, int32_t direction, int64_t* ptr, int64_t cap, int64_t* idx, double* dist,
+                        uint64_t* free_mask, int64_t* total)
 {
     if (!ctx) return MPFMT_ERR_ARG;
-    if (nq < 0 || cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_near: nq / cap < 0");
-    if (direction != 0 && direction != 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_near: direction must be 0 (tail) or 1 (head)");
-    if (nq > 0 && (!Q || !ptr || !total)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_near: Q / ptr / total is NULL");
-    if (nq > 0 && cap > 0 && (!idx || !dist || !free_mask)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_near: idx / dist / free_mask is NULL");
+    ext_call c{ctx, steer};
+    const char* p = c.pre();
+    if (nq < 0 || cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%sroadmap_near: nq / cap < 0", p);
+    if (direction != 0 && direction != 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%sroadmap_near: direction must be 0 (tail) or 1 (head)", p);
+    if (nq > 0 && (!Q || !ptr || !total)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%sroadmap_near: Q / ptr / total is NULL", p);
+    if (nq > 0 && cap > 0 && (!idx || !dist || !free_mask)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%sroadmap_near: idx / dist / free_mask is NULL", p);
     int32_t rc;
-    if ((rc = steer_roadmap_ready(ctx))) return rc;
+    if ((rc = ext_ready(c))) return rc;
     if (nq == 0) return MPFMT_OK;
-    if ((rc = roadmap_finite(ctx, Q, nq, "steer_roadmap_near"))) return rc;
+    if ((rc = ext_finite(c, Q, nq, "near"))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    mpfmt_tmp tmp;
     double* dQ = nullptr;
-    if ((rc = up_d(ctx, tmp, Q, (size_t)nq * ctx->d, &dQ))) return rc;
+    if ((rc = up_d(c, Q, (size_t)nq * ctx->d, &dQ))) return rc;
     mpfmt_rm_list L;
-    if ((rc = mpfmt_steer_roadmap_lists(ctx, tmp, dQ, nq, direction, nullptr, &L, cap == 0, ctx->Xo, ctx->N, false))) return rc;
+    if ((rc = ext_lists(c, dQ, nq, direction, nullptr, &L, cap == 0))) return rc;      // (cap == 0 asks for the sizes: the count pass alone)
     memcpy(ptr, L.ptr_host.data(), sizeof(int64_t) * (size_t)(nq + 1));
     *total = L.total;
-    if (L.total > cap) return mpfmt_fail(ctx, MPFMT_ERR_CAPACITY, "steer_roadmap_near: %lld entries exceed capacity %lld", (long long)L.total, (long long)cap);
+    if (L.total > cap) return mpfmt_fail(ctx, MPFMT_ERR_CAPACITY, "%sroadmap_near: %lld entries exceed capacity %lld", p, (long long)L.total, (long long)cap);
     if (L.total == 0) return MPFMT_OK;
     std::vector<uint8_t> bits((size_t)L.total);
     HIPCHK(ctx, hipMemcpyAsync(idx, L.idx1, sizeof(int64_t) * (size_t)L.total, hipMemcpyDeviceToHost, ctx->stream));
@@ -2126,72 +1949,137 @@ int32_t mpfmt_steer_roadmap_near(mpfmt_ctx* ctx, const double* Q, int64_t nq, in
     return MPFMT_OK;
 }
 
-int32_t mpfmt_steer_roadmap_attach(mpfmt_ctx* ctx, const double* Q, int64_t nq, const double* C, int64_t* parent, double* cost)
+static int32_t ext_attach(mpfmt_ctx* ctx, bool steer, const double* Q, int64_t nq, const double* C, int64_t* parent, double* cost)
 {
     if (!ctx) return MPFMT_ERR_ARG;
-    if (nq < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_attach: nq < 0");
-    if (nq > 0 && (!Q || !C || !parent || !cost)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_attach: Q / C / parent / cost is NULL");
+    ext_call c{ctx, steer};
+    if (nq < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%sroadmap_attach: nq < 0", c.pre());
+    if (nq > 0 && (!Q || !C || !parent || !cost)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%sroadmap_attach: Q / C / parent / cost is NULL", c.pre());
     int32_t rc;
-    if ((rc = steer_roadmap_ready(ctx))) return rc;
+    if ((rc = ext_ready(c))) return rc;
     if (nq == 0) return MPFMT_OK;
-    if ((rc = roadmap_finite(ctx, Q, nq, "steer_roadmap_attach"))) return rc;
+    if ((rc = ext_finite(c, Q, nq, "attach"))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    mpfmt_tmp tmp;
     double *dQ = nullptr, *dC = nullptr, *d_cost = nullptr; int64_t* d_par = nullptr;
-    if ((rc = up_d(ctx, tmp, Q, (size_t)nq * ctx->d, &dQ))) return rc;
-    if ((rc = up_d(ctx, tmp, C, (size_t)ctx->N, &dC))) return rc;
-    HIPCHK(ctx, tmp.get(&d_cost, sizeof(double) * (size_t)nq));
-    HIPCHK(ctx, tmp.get(&d_par, sizeof(int64_t) * (size_t)nq));
-    if ((rc = mpfmt_steer_roadmap_reduce(ctx, tmp, dQ, nq, dC, d_cost, d_par))) return rc;
+    if ((rc = up_d(c, Q, (size_t)nq * ctx->d, &dQ))) return rc;
+    if ((rc = up_d(c, C, (size_t)ctx->N, &dC))) return rc;
+    HIPCHK(ctx, c.tmp.get(&d_cost, sizeof(double) * (size_t)nq));
+    HIPCHK(ctx, c.tmp.get(&d_par, sizeof(int64_t) * (size_t)nq));
+    if ((rc = (steer ? mpfmt_steer_roadmap_reduce : mpfmt_roadmap_reduce)(ctx, c.tmp, dQ, nq, dC, d_cost, d_par))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(parent, d_par, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return MPFMT_OK;
 }
 
-// mpfmt_roadmap_query's loop with three changes: the steering state test, the resident steering bitmap, and the direct edge from a
-// 1 x 1 tail-list evaluation (query s_i against the single "sample" g_i)
-int32_t mpfmt_steer_roadmap_query(mpfmt_ctx* ctx, const double* S, const double* G, int64_t nq, int32_t checkpts, double* cost, int64_t* path_ptr,
-                                  int64_t* path, int64_t path_cap, mpfmt_roadmap_info* info)
+// The external states of the two sides of a pair query or a cost matrix: uploaded, with their free bits.
+//   Euclidean: mpfmt_launch_states_free on the device; the bits stay there, d_m = [S: ws words | G: wg words | extra words for the caller's
+//              motion bits].  pairs: S[i] -> G[i] are the pairs of a query -- their motion bits (mpfmt_launch_motions_free) fill the extra
+//              words and all of d_m is on its way to m (it has arrived once a list call has synchronised the stream).
+//   steering:  the host predicate ahead of the upload, the bits in fs / fg.
+struct ext_sides { double *dS = nullptr, *dG = nullptr; uint64_t* d_m = nullptr; std::vector<uint64_t> m, fs, fg; };
+
+static int32_t ext_sides_free(ext_call& c, const double* S, int64_t ns, const double* G, int64_t ng, int64_t extra, bool pairs, ext_sides* o)
+{
+    mpfmt_ctx* ctx = c.ctx;
+    const int d = ctx->d;
+    const int64_t ws = (ns + 63) / 64, wg = (ng + 63) / 64;
+    int32_t rc;
+    if (c.steer) {
+        const steer_space s = steer_space_of(ctx, ctx->steer_kind);
+        if ((rc = steer_states_free(ctx, s, S, ns, o->fs))) return rc;
+        if ((rc = steer_states_free(ctx, s, G, ng, o->fg))) return rc;
+    }
+    if ((rc = up_d(c, S, (size_t)ns * d, &o->dS))) return rc;
+    if ((rc = up_d(c, G, (size_t)ng * d, &o->dG))) return rc;
+    if (c.steer) return MPFMT_OK;
+    HIPCHK(ctx, c.tmp.get(&o->d_m, sizeof(uint64_t) * (size_t)(ws + wg + extra)));
+    if ((rc = mpfmt_launch_states_free(ctx, o->dS, ns, o->d_m))) return rc;
+    if ((rc = mpfmt_launch_states_free(ctx, o->dG, ng, o->d_m + ws))) return rc;
+    if (!pairs) return MPFMT_OK;
+    if ((rc = mpfmt_launch_motions_free(ctx, o->dS, o->dG, ns, o->d_m + ws + wg))) return rc;
+    o->m.resize((size_t)(ws + wg + extra));
+    HIPCHK(ctx, hipMemcpyAsync(o->m.data(), o->d_m, sizeof(uint64_t) * o->m.size(), hipMemcpyDeviceToHost, ctx->stream));
+    return MPFMT_OK;
+}
+
+// the checkpts bitmap of the resident graph's samples: ctx->sssp_F, or nullptr without checkpts
+static int32_t ext_bitmap(ext_call& c, int32_t checkpts, const uint64_t** d_F)
+{
+    int32_t rc;
+    if (checkpts && (rc = c.steer ? sssp_resident_bitmap(c.ctx) : sssp_point_bitmap(c.ctx))) return rc;
+    *d_F = checkpts ? c.ctx->sssp_F.get() : nullptr;
+    return MPFMT_OK;
+}
+
+// The list calls of a pair query in their order, and the direct edge of every pair as (direct[q], dsg[q]: its weight, +Inf without).
+//   steering:  a 1 x 1 tail-list evaluation ahead of the attachments (query s_i against the single "sample" g_i), weight and free bit read back.
+//   Euclidean: the squared distance folded on the host against r * r, and the motion bit of ext_sides_free, which has arrived with the
+//              lists; the free bits of the two sides move to fs / fg, where the steering space has them.
+static int32_t ext_query_lists(ext_call& c, ext_sides& e, const double* S, const double* G, int64_t nq, const uint64_t* d_F, mpfmt_rm_list* Ls,
+                               mpfmt_rm_list* Lg, std::vector<uint8_t>& direct, std::vector<double>& dsg)
+{
+    mpfmt_ctx* ctx = c.ctx;
+    int32_t rc;
+    direct.assign((size_t)nq, 0);
+    dsg.assign((size_t)nq, INFINITY);
+    if (c.steer) {
+        mpfmt_rm_list Ld;
+        if ((rc = ext_lists(c, e.dS, nq, 0, nullptr, &Ld, false, e.dG))) return rc;
+        std::vector<double> w((size_t)Ld.total);
+        std::vector<uint8_t> b((size_t)Ld.total);
+        if (Ld.total > 0) {
+            HIPCHK(ctx, hipMemcpyAsync(w.data(), Ld.dist, sizeof(double) * (size_t)Ld.total, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(b.data(), Ld.bits, (size_t)Ld.total, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        for (int64_t q = 0; q < nq; ++q) {
+            const int64_t at = Ld.ptr_host[(size_t)q];
+            if (Ld.ptr_host[(size_t)q + 1] > at && (b[(size_t)at] & 1)) { direct[(size_t)q] = 1; dsg[(size_t)q] = w[(size_t)at]; }
+        }
+    }
+    if ((rc = ext_lists(c, e.dS, nq, 0, d_F, Ls))) return rc;
+    if ((rc = ext_lists(c, e.dG, nq, 1, nullptr, Lg))) return rc;
+    if (c.steer) return MPFMT_OK;
+    const int d = ctx->d;
+    const int64_t words = (nq + 63) / 64;
+    const double r2 = ctx->graph_r * ctx->graph_r;
+    e.fs.assign(e.m.begin(), e.m.begin() + words);
+    e.fg.assign(e.m.begin() + words, e.m.begin() + 2 * words);
+    for (int64_t q = 0; q < nq; ++q) {
+        double dsg2 = 0.0;
+        for (int i = 0; i < d; ++i) { const double t = S[q * d + i] - G[q * d + i]; const double tt = t * t; dsg2 = (i == 0) ? tt : dsg2 + tt; }
+        if (dsg2 <= r2 && ((e.m[(size_t)(2 * words + (q >> 6))] >> (q & 63)) & 1ull)) { direct[(size_t)q] = 1; dsg[(size_t)q] = std::sqrt(dsg2); }
+    }
+    return MPFMT_OK;
+}
+
+static int32_t ext_query(mpfmt_ctx* ctx, bool steer, const double* S, const double* G, int64_t nq, int32_t checkpts, double* cost, int64_t* path_ptr,
+                         int64_t* path, int64_t path_cap, mpfmt_roadmap_info* info)
 {
     if (!ctx) return MPFMT_ERR_ARG;
-    if (nq < 0 || path_cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_query: nq / path_cap < 0");
+    ext_call c{ctx, steer};
+    if (nq < 0 || path_cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%sroadmap_query: nq / path_cap < 0", c.pre());
     if (nq > 0 && (!S || !G || !cost || !path_ptr || (path_cap > 0 && !path)))
-        return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_roadmap_query: S / G / cost / path_ptr / path is NULL");
+        return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%sroadmap_query: S / G / cost / path_ptr / path is NULL", c.pre());
     int32_t rc;
-    if ((rc = steer_roadmap_ready(ctx))) return rc;
+    if ((rc = ext_ready(c))) return rc;
     if (nq == 0) return MPFMT_OK;
-    if ((rc = roadmap_finite(ctx, S, nq, "steer_roadmap_query (S)"))) return rc;
-    if ((rc = roadmap_finite(ctx, G, nq, "steer_roadmap_query (G)"))) return rc;
+    if ((rc = ext_finite(c, S, nq, "query (S)"))) return rc;
+    if ((rc = ext_finite(c, G, nq, "query (G)"))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int d = ctx->d;
     const int64_t N = ctx->N;
-    std::vector<uint64_t> fs, fg;
-    if ((rc = steer_query_states_free(ctx, S, nq, fs))) return rc;
-    if ((rc = steer_query_states_free(ctx, G, nq, fg))) return rc;
-    mpfmt_tmp tmp;
-    double *dS = nullptr, *dG = nullptr;
-    if ((rc = up_d(ctx, tmp, S, (size_t)nq * d, &dS))) return rc;
-    if ((rc = up_d(ctx, tmp, G, (size_t)nq * d, &dG))) return rc;
-    if (checkpts && (rc = sssp_resident_bitmap(ctx))) return rc;
-    const uint64_t* d_F = checkpts ? ctx->sssp_F.get() : nullptr;
-    // the direct edges, then all attachments, one count and one fill launch each
-    mpfmt_rm_list Ld, Ls, Lg;
-    if ((rc = mpfmt_steer_roadmap_lists(ctx, tmp, dS, nq, 0, nullptr, &Ld, false, dG, nq, true))) return rc;
-    int64_t cand = ctx->roadmap_candidates, tot = 0, steered = ctx->steer_roadmap_steered;      // (the direct edges are no near-set entries)
-    std::vector<double> dw((size_t)std::max<int64_t>(Ld.total, 1));
-    std::vector<uint8_t> db((size_t)std::max<int64_t>(Ld.total, 1));
-    if (Ld.total > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(dw.data(), Ld.dist, sizeof(double) * (size_t)Ld.total, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(db.data(), Ld.bits, (size_t)Ld.total, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    if ((rc = mpfmt_steer_roadmap_lists(ctx, tmp, dS, nq, 0, d_F, &Ls, false, ctx->Xo, N, false))) return rc;
-    cand += ctx->roadmap_candidates; tot += ctx->roadmap_near_total; steered += ctx->steer_roadmap_steered;
-    if ((rc = mpfmt_steer_roadmap_lists(ctx, tmp, dG, nq, 1, nullptr, &Lg, false, ctx->Xo, N, false))) return rc;
-    ctx->roadmap_candidates += cand; ctx->roadmap_near_total += tot; ctx->steer_roadmap_steered += steered;
+    // the two states of every pair, the direct edge, and all attachments: one count and one fill launch each way
+    ext_sides e;
+    const uint64_t* d_F;
+    mpfmt_rm_list Ls, Lg;
+    std::vector<uint8_t> direct;
+    std::vector<double> dsg;
+    if ((rc = ext_sides_free(c, S, nq, G, nq, (nq + 63) / 64, true, &e))) return rc;
+    if ((rc = ext_bitmap(c, checkpts, &d_F))) return rc;
+    if ((rc = ext_query_lists(c, e, S, G, nq, d_F, &Ls, &Lg, direct, dsg))) return rc;
     int64_t* d_res = nullptr;
-    HIPCHK(ctx, tmp.get(&d_res, sizeof(int64_t) * (size_t)(N + 8)));
+    HIPCHK(ctx, c.tmp.get(&d_res, sizeof(int64_t) * (size_t)(N + 8)));
     int64_t res[3];
     std::vector<int64_t> hops;
     int64_t used = 0;
@@ -2204,8 +2092,8 @@ int32_t mpfmt_steer_roadmap_query(mpfmt_ctx* ctx, const double* S, const double*
         inf.near_g = Lg.ptr_host[(size_t)q + 1] - Lg.ptr_host[(size_t)q]; inf.usable_g = Lg.usable_host[(size_t)q];
         cost[q] = INFINITY;
         int64_t len = 0;
-        if (!((fs[(size_t)(q >> 6)] >> (q & 63)) & 1ull)) inf.status = 2;
-        else if (!((fg[(size_t)(q >> 6)] >> (q & 63)) & 1ull)) inf.status = 3;
+        if (!bit(e.fs, q)) inf.status = 2;
+        else if (!bit(e.fg, q)) inf.status = 3;
         else {
             const int64_t s0 = Ls.ptr_host[(size_t)q];
             mpfmt_sssp_info fi;
@@ -2216,10 +2104,7 @@ int32_t mpfmt_steer_roadmap_query(mpfmt_ctx* ctx, const double* S, const double*
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             double best; memcpy(&best, &res[0], sizeof best);
             const int64_t last = res[1];
-            const int64_t e = Ld.ptr_host[(size_t)q];
-            const bool direct = Ld.ptr_host[(size_t)q + 1] > e && (db[(size_t)e] & 1);
-            const double dsg = direct ? dw[(size_t)e] : INFINITY;
-            if (direct && (last == 0 || dsg <= best)) { cost[q] = dsg; inf.status = 0; }
+            if (direct[(size_t)q] && (last == 0 || dsg[(size_t)q] <= best)) { cost[q] = dsg[(size_t)q]; inf.status = 0; }
             else if (last == 0) inf.status = 1;
             else {
                 cost[q] = best; inf.status = 0; len = res[2];
@@ -2236,7 +2121,78 @@ int32_t mpfmt_steer_roadmap_query(mpfmt_ctx* ctx, const double* S, const double*
         path_ptr[q + 1] = used;
         if (info) info[q] = inf;
     }
-    if (over) return mpfmt_fail(ctx, MPFMT_ERR_CAPACITY, "steer_roadmap_query: %lld path samples exceed capacity %lld", (long long)used, (long long)path_cap);
+    if (over) return mpfmt_fail(ctx, MPFMT_ERR_CAPACITY, "%sroadmap_query: %lld path samples exceed capacity %lld", c.pre(), (long long)used, (long long)path_cap);
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_roadmap_near(mpfmt_ctx* ctx, const double* Q, int64_t nq, int32_t direction, int64_t* ptr, int64_t cap, int64_t* idx, double* dist,
+                           uint64_t* free_mask, int64_t* total)
+{ return ext_near(ctx, false, Q, nq, direction, ptr, cap, idx, dist, free_mask, total); }
+
+int32_t mpfmt_steer_roadmap_near(mpfmt_ctx* ctx, const double* Q, int64_t nq, int32_t direction, int64_t* ptr, int64_t cap, int64_t* idx, double* dist,
+                                 uint64_t* free_mask, int64_t* total)
+{ return ext_near(ctx, true, Q, nq, direction, ptr, cap, idx, dist, free_mask, total); }
+
+int32_t mpfmt_roadmap_attach(mpfmt_ctx* ctx, const double* Q, int64_t nq, const double* C, int64_t* parent, double* cost)
+{ return ext_attach(ctx, false, Q, nq, C, parent, cost); }
+
+int32_t mpfmt_steer_roadmap_attach(mpfmt_ctx* ctx, const double* Q, int64_t nq, const double* C, int64_t* parent, double* cost)
+{ return ext_attach(ctx, true, Q, nq, C, parent, cost); }
+
+int32_t mpfmt_roadmap_query(mpfmt_ctx* ctx, const double* S, const double* G, int64_t nq, int32_t checkpts, double* cost, int64_t* path_ptr,
+                            int64_t* path, int64_t path_cap, mpfmt_roadmap_info* info)
+{ return ext_query(ctx, false, S, G, nq, checkpts, cost, path_ptr, path, path_cap, info); }
+
+int32_t mpfmt_steer_roadmap_query(mpfmt_ctx* ctx, const double* S, const double* G, int64_t nq, int32_t checkpts, double* cost, int64_t* path_ptr,
+                                  int64_t* path, int64_t path_cap, mpfmt_roadmap_info* info)
+{ return ext_query(ctx, true, S, G, nq, checkpts, cost, path_ptr, path, path_cap, info); }
+
+// the ns x ng cost matrix between external starts and goals at the price of ns fields (kernels_sssp_multi.hip); Euclidean graphs
+int32_t mpfmt_roadmap_matrix(mpfmt_ctx* ctx, const double* S, int64_t ns, const double* G, int64_t ng, int32_t checkpts, double* cost, int32_t* status,
+                             mpfmt_roadmap_matrix_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    ext_call c{ctx, false};
+    if (ns < 0 || ng < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_matrix: ns / ng < 0");
+    if (ns > 0 && ng > 0 && (!S || !G || !cost)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "roadmap_matrix: S / G / cost is NULL");
+    int32_t rc;
+    if ((rc = ext_ready(c))) return rc;
+    if (info) memset(info, 0, sizeof *info);
+    if (ns == 0 || ng == 0) return MPFMT_OK;
+    if ((rc = ext_finite(c, S, ns, "matrix (S)"))) return rc;
+    if ((rc = ext_finite(c, G, ng, "matrix (G)"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int d = ctx->d;
+    const int64_t np = ns * ng, ws = (ns + 63) / 64, wg = (ng + 63) / 64, wp = (np + 63) / 64;
+    double *dP = nullptr, *dQ = nullptr, *d_cost = nullptr;
+    int32_t* d_status = nullptr;
+    HIPCHK(ctx, c.tmp.get(&dP, sizeof(double) * (size_t)np * d));
+    HIPCHK(ctx, c.tmp.get(&dQ, sizeof(double) * (size_t)np * d));
+    HIPCHK(ctx, c.tmp.get(&d_cost, sizeof(double) * (size_t)np));
+    HIPCHK(ctx, c.tmp.get(&d_status, sizeof(int32_t) * (size_t)np));
+    // the states of both sides and the direct edge of every pair: the tests of the pair query, through the same kernels
+    ext_sides e;
+    if ((rc = ext_sides_free(c, S, ns, G, ng, wp, false, &e))) return rc;
+    uint64_t* d_direct = e.d_m + ws + wg;
+    if ((rc = mpfmt_roadmap_pairs(ctx, e.dS, ns, e.dG, ng, dP, dQ))) return rc;
+    if ((rc = mpfmt_launch_motions_free(ctx, dP, dQ, np, d_direct))) return rc;
+    // all attachments, one launch each way
+    const uint64_t* d_F;
+    mpfmt_rm_list Ls, Lg;
+    if ((rc = ext_bitmap(c, checkpts, &d_F))) return rc;
+    if ((rc = ext_lists(c, e.dS, ns, 0, d_F, &Ls))) return rc;
+    if ((rc = ext_lists(c, e.dG, ng, 1, nullptr, &Lg))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // (the lists' usable counts have arrived)
+    mpfmt_roadmap_matrix_info inf;
+    memset(&inf, 0, sizeof inf);
+    if ((rc = mpfmt_roadmap_matrix_device(ctx, e.dS, ns, e.dG, ng, d_F, e.d_m, e.d_m + ws, d_direct, Ls, Lg, d_cost, d_status, &inf))) return rc;
+    inf.near_s = Ls.total; inf.near_g = Lg.total;
+    for (int64_t v : Ls.usable_host) inf.usable_s += v;
+    for (int64_t v : Lg.usable_host) inf.usable_g += v;
+    HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIPCHK(ctx, hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (info) *info = inf;
     return MPFMT_OK;
 }
 

@@ -140,6 +140,9 @@ def check_queries(ctx, g, sc, S, G, names):
     return cost, paths, info
 
 
+STATS = ("roadmap_candidates", "roadmap_near_total")
+
+
 @pytest.mark.parametrize("d,N,r", [(2, 1000, 0.12), (3, 2000, 0.15), (6, 4096, 0.5)])
 def test_pair_queries_equal_the_host(orc, d, N, r):
     sc = rc.Scene(d, N, r, 8, seed=40 + d)
@@ -154,6 +157,15 @@ def test_pair_queries_equal_the_host(orc, d, N, r):
         assert st["start inside a box"] == 2 and st["goal outside the bounds"] == 3 and st["goal far from every sample"] == 1
         assert st["the only seed has F = 0"] == 1 and st["direct edge free"] == 0 and sum(1 for s in st.values() if s == 0) >= 6
         assert any(len(p) >= 2 for p in paths)
+        if d == 2:                                       # the stats of a pair query: the sums over its two list calls
+            ctx.roadmap_query(S, G)
+            got = [ctx.stat(k) for k in STATS]
+            ctx.roadmap_near(S, 0)
+            tail = [ctx.stat(k) for k in STATS]
+            ctx.roadmap_near(G, 1)
+            head = [ctx.stat(k) for k in STATS]
+            print("pair query stats %s = tail %s + head %s" % (got, tail, head))
+            assert got == [a + b for a, b in zip(tail, head)] and got[1] > 0
         # a path goes straight into the shortcutter
         i = max(range(len(paths)), key=lambda k: len(paths[k]))
         states = np.vstack([S[i:i + 1], sc.X[paths[i] - 1], G[i:i + 1]])

@@ -61,6 +61,9 @@ def equals_host(ctx, sc, g, S, G, checkpts, cost, status, cells):
         assert bits(cost[i, j]) == bits(wc) and status[i, j] == wi["status"], (i, j, cost[i, j], wc, status[i, j], wi)
 
 
+STATS = ("roadmap_candidates", "roadmap_near_total")
+
+
 @pytest.mark.parametrize("d,N,r,extra", [(2, 1000, 0.12, 0), (3, 2000, 0.15, 58), (6, 4096, 0.5, 0)])
 def test_matrix_equals_the_pair_queries(orc, d, N, r, extra):
     """The scene's starts crossed with its goals: start / goal on a sample, a direct edge free and blocked, a goal far from every sample, a
@@ -84,6 +87,13 @@ def test_matrix_equals_the_pair_queries(orc, d, N, r, extra):
         g = exported(ctx)
         for checkpts in (True, False):
             cost, status, info = ctx.roadmap_matrix(S, G, checkpts=checkpts)
+            got = [ctx.stat(k) for k in STATS]           # the stats of the call: the sums over its two list calls
+            ctx.roadmap_near(S, 0)
+            tail = [ctx.stat(k) for k in STATS]
+            ctx.roadmap_near(G, 1)
+            head = [ctx.stat(k) for k in STATS]
+            print("matrix stats %s = tail %s + head %s" % (got, tail, head))
+            assert got == [a + b for a, b in zip(tail, head)] and got[1] > 0
             qi = equals_pair_queries(ctx, S, G, checkpts, cost, status)
             row = names.index("direct edge blocked by the wall")
             equals_host(ctx, sc, g, S, G, checkpts, cost, status,

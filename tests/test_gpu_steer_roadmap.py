@@ -230,6 +230,19 @@ def test_pair_queries_equal_the_appended_sample_dijkstra(orc, name):
         else:
             assert name == "W4"
         assert sum(1 for v in seen.values() if v[0] == 0 and v[1] > 0) >= 2      # paths through samples
+        # the stats of a pair query: the sums over its list calls; the direct-edge pass pre-tests one pair per query, may steer it, and
+        # adds no near-set entry
+        keys = ("roadmap_candidates", "roadmap_near_total", "steer_roadmap_steered")
+        nq = len(c.S)
+        ctx.steer_roadmap_query(c.S, c.G)
+        cand, tot, steered = [ctx.stat(k) for k in keys]
+        ctx.steer_roadmap_near(c.S, 0)
+        _, tot_s, st_s = [ctx.stat(k) for k in keys]
+        ctx.steer_roadmap_near(c.G, 1)
+        _, tot_g, st_g = [ctx.stat(k) for k in keys]
+        print("%s pair query stats: %d candidates, %d = %d + %d entries, %d steers against %d + %d" % (name, cand, tot, tot_s, tot_g, steered, st_s, st_g))
+        assert cand == nq * (2 * w.N + 1) and tot == tot_s + tot_g
+        assert st_s + st_g <= steered <= st_s + st_g + nq
 
 
 # ---- 4. in-place box edits on the resident graph ---------------------------------------------------------------------------------------
