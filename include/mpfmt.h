@@ -668,6 +668,68 @@ MPFMT_API int32_t mpfmt_adaptive_shortcut_batch(mpfmt_ctx* ctx, const double* P,
 MPFMT_API int32_t mpfmt_adaptive_shortcut(mpfmt_ctx* ctx, const double* P, int64_t n, int32_t iterations, int64_t max_states, double* out_P,
                                 int64_t out_cap, double* cumcost, mpfmt_shortcut_info* info);
 
+/* ---- time discretisation of solution paths: time_discretize_solution! / time_space_solution! of src/postprocessors.jl:61-83, i.e.
+ *      steering_control(SS, path...) (statespaces.jl:147) followed by propagate(d, v, us, times) (statespaces.jl:104-119), for ONE path on
+ *      the host and for a BATCH of paths on the device (lane = output sample).
+ *      A path is n >= 2 states p_1 .. p_n (d doubles each, all finite) in one of four spaces:
+ *        MPFMT_SPACE_EUCLID      d as mpfmt_euclid_steer accepts (1 .. MPFMT_MAX_DIM)   params NULL
+ *        MPFMT_SPACE_DI          d = 2 m, m = 1 .. 6                                    params {rho, r}  (r: the Newton bracket tm of steer,
+ *                                                                                       linearquadratic.jl:191-195); both > 0
+ *        MPFMT_SPACE_DUBINS      d = 3                                                  params {turn_radius, speed}, both > 0
+ *        MPFMT_SPACE_REEDSSHEPP  d = 3                                                  params {turn_radius, speed}, both > 0
+ *      Control steps: every consecutive pair (p_i, p_i+1) is steered on its own, from the GIVEN states: Euclidean one step (t, u) with the
+ *        arithmetic of mpfmt_euclid_steer; double integrator one step (t*, target p_i+1), t* of mpfmt_di_steer; Dubins 3 steps (duration,
+ *        speed, curvature) as mpfmt_dubins_steer returns them; Reeds-Shepp nsegs <= 5 steps as mpfmt_reedsshepp_steer returns them.  The
+ *        steps of a path are numbered j = 1 .. K in order.  A Euclidean pair of equal states gives one step of duration 0 with u = 0 (the
+ *        reference would produce NaN there: a declared guard).
+ *      Chain: S_1 = p_1, S_j+1 = propagate(S_j, c_j), the full step: Euclidean S_j + t_j * u_j (unfused); cars: the propagate of
+ *        simplecars.jl:55-67, mod 2 pi included; double integrator: the target p_i+1 exactly (linearquadratic.jl:80).  T0_1 = 0, T0_j+1 =
+ *        fl(T0_j + t_j), tf = T0_K+1: the left-to-right fold of duration(::ControlSequence) (primitivetypes.jl:132).
+ *      Times: mode MPFMT_DISC_DT (time_discretize_solution!), dt > 0 finite: n_out = floor(fl(tf / dt)) + 1, t_k = min(fl(k * dt), tf) for
+ *        k = 0 .. n_out - 1; with append_end != 0 and the last t_k < tf one more sample at tf follows (the [0:dt:t; t] of waypoints,
+ *        statespaces.jl:127-131).  Mode MPFMT_DISC_N (time_space_solution!), n_out = n_samples >= 2: t_k = fl(fl(k / (n_samples - 1)) * tf),
+ *        so the last time is tf exactly.  Both are DECLARED forms: Julia's FloatRange and LinSpace can differ from them in the last bit,
+ *        and in the count where tf / dt lies within an ulp of an integer.
+ *      Sample at t_k: j = the first step with t_k < T0_j+1, or K if there is none -- what the reference's loop `while t >= t0 +
+ *        duration(u[i]) && i < length(u)` (statespaces.jl:111) arrives at, T0 being that loop's own running sum; steps of duration 0 are
+ *        passed over unless one is the last step.  With s = t_k - T0_j the state is propagate(S_j, c_j, s) (statespaces.jl:79-81,
+ *        linearquadratic.jl:81-82): s <= 0 gives S_j, s >= t_j the full step, otherwise Euclidean S_j + s * u_j, cars the car propagate
+ *        with duration s, double integrator the closed-form state x(p_i, p_i+1, t*, s) of the collision waypoints.
+ *      Per sample: the state (out_X, d doubles), T = t_k (out_T), seg = the 1-based index i of the pair the step j belongs to (out_seg,
+ *        may be NULL).  Per path: mpfmt_disc_info {n_out, steps = K, duration = tf}.
+ *      Layout as mpfmt_adaptive_shortcut_batch: paths d x n column-major, offsets[B + 1] 0-based with offsets[0] = 0; out_offsets[B + 1]
+ *        likewise.  out_cap == 0 is the size query (only the steer and the chain run; out_offsets and info are written; out_X / out_T
+ *        may be NULL); a total above out_cap returns MPFMT_ERR_CAPACITY with out_offsets and info written.
+ *      MPFMT_ERR_ARG: a path of fewer than 2 states, a non-finite coordinate or parameter (or one <= 0), dt <= 0 or not finite in DT
+ *        mode, n_samples < 2 in N mode, a d that does not fit the space, a total above 2^31 - 1 samples; MPFMT_ERR_STATE: a sharded ctx.
+ *      Nothing resident is needed or touched: no samples, no graph, no obstacle set; a fresh ctx serves.  Timer "discretize_batch" (also
+ *        "discretize_steer", "discretize_chain", "discretize_sample" by launch); stats "discretize_steps", "discretize_samples" (last
+ *        batch).  Every loop on the device is bounded by an array length or by K; the only iterative arithmetic is the Newton search of
+ *        mpfmt_di_steer, unchanged.
+ *      mpfmt_host_discretize: one path, no ctx, no device: the sequential loop of statespaces.jl:104-119 statement for statement; the CPU
+ *        baseline and the checker of the device result, which is bit-equal in all four spaces (same operations, same mp_math.h
+ *        trigonometry, unfused, correctly rounded / and sqrt). */
+#define MPFMT_SPACE_EUCLID     0
+#define MPFMT_SPACE_DI         1
+#define MPFMT_SPACE_DUBINS     2
+#define MPFMT_SPACE_REEDSSHEPP 3
+#define MPFMT_DISC_DT 0
+#define MPFMT_DISC_N  1
+typedef struct {
+    int64_t n_out;             /* samples of the path */
+    int64_t steps;             /* K */
+    double duration;           /* tf */
+} mpfmt_disc_info;
+MPFMT_API int32_t mpfmt_host_discretize(int32_t space, int32_t d, const double* params, const double* P, int64_t n, int32_t mode, double dt,
+                              int64_t n_samples, int32_t append_end, double* out_X, double* out_T, int32_t* out_seg, int64_t out_cap,
+                              mpfmt_disc_info* info);
+MPFMT_API int32_t mpfmt_discretize_batch(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, const int64_t* offsets,
+                               int64_t B, int32_t mode, double dt, int64_t n_samples, int32_t append_end, double* out_X, double* out_T,
+                               int32_t* out_seg, int64_t* out_offsets, int64_t out_cap, mpfmt_disc_info* info);
+MPFMT_API int32_t mpfmt_discretize(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, int64_t n, int32_t mode,
+                         double dt, int64_t n_samples, int32_t append_end, double* out_X, double* out_T, int32_t* out_seg, int64_t out_cap,
+                         mpfmt_disc_info* info);
+
 /* ---- Monte-Carlo collision probability of candidate edges (BASELINE.json configs[4]).  The reference
  *      has no implementation (README.md:9-10 cites the papers only); the workload is the one SURVEY 8d defines: per edge
  *      (src[e] -> dst[e], 1-based sample indices) `rollouts` perturbed copies of the 2-point trajectory, each put through

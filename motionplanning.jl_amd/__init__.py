@@ -9,5 +9,7 @@ No CPU fallback exists for any compute entry point.
 from . import _lib, workloads, distributed, mirror  # noqa: F401
 from .mirror import *  # noqa: F401,F403  (the reference's names: MPProblem, UnitHypercube, fmtstar_, ...)
 from ._lib import Context, MPFMTError  # noqa: F401
+from ._lib import host_discretize, SPACE_EUCLID, SPACE_DI, SPACE_DUBINS, SPACE_REEDSSHEPP  # noqa: F401
+from .mirror import time_discretize_solution_, time_space_solution_, discretize_paths_  # noqa: F401
 
 __version__ = "0.1.0"

@@ -72,7 +72,13 @@ class RoadmapMatrixInfo(C.Structure):
                 ("usable_g", C.c_int64), ("ms_device", C.c_double)]
 
 
+class DiscInfo(C.Structure):
+    _fields_ = [("n_out", C.c_int64), ("steps", C.c_int64), ("duration", C.c_double)]
+
+
 SHORTCUT_DONE, SHORTCUT_TRUNCATED, SHORTCUT_STUCK = 0, 1, 2
+SPACE_EUCLID, SPACE_DI, SPACE_DUBINS, SPACE_REEDSSHEPP = 0, 1, 2, 3
+DISC_DT, DISC_N = 0, 1
 ROADMAP_SOLVED, ROADMAP_NO_PATH, ROADMAP_START_BLOCKED, ROADMAP_GOAL_BLOCKED = 0, 1, 2, 3
 WF_SINGLE, WF_EAGER, WF_LAZY = 1, 2, 4
 COMM_ID_BYTES = 128
@@ -155,6 +161,12 @@ SYMBOLS = [
     ("mpfmt_adaptive_shortcut_batch", C.c_int32, [C.c_void_p, c_d_p, c_i64_p, C.c_int64, C.c_int32, C.c_int64, c_d_p, c_i64_p, C.c_int64, c_d_p,
                                                   C.POINTER(ShortcutInfo)]),
     ("mpfmt_adaptive_shortcut", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, C.c_int32, C.c_int64, c_d_p, C.c_int64, c_d_p, C.POINTER(ShortcutInfo)]),
+    ("mpfmt_host_discretize", C.c_int32, [C.c_int32, C.c_int32, c_d_p, c_d_p, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, c_d_p, c_d_p,
+                                          C.POINTER(C.c_int32), C.c_int64, C.POINTER(DiscInfo)]),
+    ("mpfmt_discretize_batch", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, c_d_p, c_d_p, c_i64_p, C.c_int64, C.c_int32, C.c_double, C.c_int64,
+                                           C.c_int32, c_d_p, c_d_p, C.POINTER(C.c_int32), c_i64_p, C.c_int64, C.POINTER(DiscInfo)]),
+    ("mpfmt_discretize", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, c_d_p, c_d_p, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, c_d_p,
+                                     c_d_p, C.POINTER(C.c_int32), C.c_int64, C.POINTER(DiscInfo)]),
     ("mpfmt_mc_edges_collision", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, c_i64_p]),
     ("mpfmt_mc_edges_collision_is", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("mpfmt_mc_edges_collision_ais", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, C.POINTER(C.c_uint64),
@@ -469,6 +481,46 @@ def host_adaptive_shortcut(path, lohi, ss_lo=None, ss_hi=None, iterations=10, ma
     if rc != 0:
         raise MPFMTError(rc, "mpfmt_host_adaptive_shortcut rejected its arguments")
     return out[:info.n_out].copy(), cc[:info.n_out].copy(), _shortcut_info(info)
+
+
+def _disc_info(i):
+    return dict(n_out=int(i.n_out), steps=int(i.steps), duration=float(i.duration))
+
+
+def _disc_args(space, params, dt, n, append_end):
+    """(params array or None, mode, dt, n_samples, append_end) of the discretise calls: exactly one of dt / n is given."""
+    if (dt is None) == (n is None):
+        raise ValueError("give exactly one of dt (time_discretize_solution!) and n (time_space_solution!)")
+    prm = None if params is None else np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
+    if space in (SPACE_DI, SPACE_DUBINS, SPACE_REEDSSHEPP) and (prm is None or prm.size != 2):
+        raise ValueError("params = (rho, r) for the double integrator, (turn_radius, speed) for the cars")
+    return prm, (DISC_DT if n is None else DISC_N), (0.0 if dt is None else float(dt)), (0 if n is None else int(n)), (1 if append_end else 0)
+
+
+def _ip32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def host_discretize(path, space, params=None, dt=None, n=None, append_end=False):
+    """Time discretisation of one path (n_states, d) on the host: the sequential loop of src/statespaces.jl:104-119 (include/mpfmt.h,
+    "time discretisation"); no GPU needed; the CPU baseline and the checker of Context.discretize.
+    Returns (X (n_out, d), T (n_out,), seg (n_out,) int32 1-based, info dict)."""
+    P = np.ascontiguousarray(path, dtype=np.float64)
+    if P.ndim != 2:
+        raise ValueError("path must be (n, d)")
+    prm, mode, dtv, ns, app = _disc_args(space, params, dt, n, append_end)
+    info = DiscInfo()
+    L = lib()
+    rc = L.mpfmt_host_discretize(int(space), P.shape[1], _dp(prm), _dp(P), P.shape[0], mode, dtv, ns, app, None, None, None, 0, C.byref(info))
+    if rc != 0:
+        raise MPFMTError(rc, "mpfmt_host_discretize rejected its arguments")
+    cap = int(info.n_out)
+    X = np.empty((cap, P.shape[1]), dtype=np.float64); T = np.empty(cap, dtype=np.float64); seg = np.empty(cap, dtype=np.int32)
+    rc = L.mpfmt_host_discretize(int(space), P.shape[1], _dp(prm), _dp(P), P.shape[0], mode, dtv, ns, app, _dp(X), _dp(T), _ip32(seg), cap,
+                                 C.byref(info))
+    if rc != 0:
+        raise MPFMTError(rc, "mpfmt_host_discretize failed")
+    return X, T, seg, _disc_info(info)
 
 
 class Context:
@@ -1262,6 +1314,36 @@ class Context:
             self._chk(rc)
             break
         return [(out[out_off[b]:out_off[b + 1]].copy(), cc[out_off[b]:out_off[b + 1]].copy(), _shortcut_info(info[b])) for b in range(B)]
+
+    def discretize(self, paths, space, params=None, dt=None, n=None, append_end=False):
+        """Time discretisation of a batch of paths on the device, lane = output sample (include/mpfmt.h, "time discretisation"):
+        time_discretize_solution! with dt, time_space_solution! with n.  space: SPACE_EUCLID / _DI / _DUBINS / _REEDSSHEPP; params: None,
+        (rho, r) or (turn_radius, speed).  paths: a list of (n_i, d) arrays -> (a list of (X, T, seg) triples, a list of info dicts); one
+        (n, d) array -> ((X, T, seg), info).  Needs nothing resident on the ctx and leaves it as it was."""
+        single = isinstance(paths, np.ndarray) and paths.ndim == 2
+        plist = [np.ascontiguousarray(p, dtype=np.float64) for p in ([paths] if single else list(paths))]
+        for p in plist:
+            if p.ndim != 2 or p.shape[1] != plist[0].shape[1]:
+                raise ValueError("every path must be (n, d) with one d")
+        prm, mode, dtv, ns, app = _disc_args(space, params, dt, n, append_end)
+        B = len(plist)
+        if B == 0:
+            return [], []
+        d = plist[0].shape[1]
+        off = np.zeros(B + 1, dtype=np.int64)
+        off[1:] = np.cumsum([p.shape[0] for p in plist])
+        P = np.ascontiguousarray(np.concatenate(plist, axis=0))
+        info = (DiscInfo * B)()
+        out_off = np.zeros(B + 1, dtype=np.int64)
+        self._chk(self._L.mpfmt_discretize_batch(self._h, int(space), d, _dp(prm), _dp(P), _ip(off), B, mode, dtv, ns, app, None, None, None,
+                                                 _ip(out_off), 0, info))                   # the size query
+        cap = max(int(out_off[-1]), 1)
+        X = np.empty((cap, d), dtype=np.float64); T = np.empty(cap, dtype=np.float64); seg = np.empty(cap, dtype=np.int32)
+        self._chk(self._L.mpfmt_discretize_batch(self._h, int(space), d, _dp(prm), _dp(P), _ip(off), B, mode, dtv, ns, app, _dp(X), _dp(T),
+                                                 _ip32(seg), _ip(out_off), cap, info))
+        res = [(X[out_off[b]:out_off[b + 1]].copy(), T[out_off[b]:out_off[b + 1]].copy(), seg[out_off[b]:out_off[b + 1]].copy()) for b in range(B)]
+        infos = [_disc_info(info[b]) for b in range(B)]
+        return (res[0], infos[0]) if single else (res, infos)
 
     def path_free(self, P):
         """is_free_path(p, CC, SS) for the states P (n, d): (free, per-segment bits)."""

@@ -1702,6 +1702,48 @@ int32_t mpfmt_adaptive_shortcut(mpfmt_ctx* ctx, const double* P, int64_t n, int3
     return mpfmt_adaptive_shortcut_batch(ctx, P, offsets, 1, iterations, max_states, out_P, out_offsets, out_cap, cumcost, info);
 }
 
+// ---- time discretisation of solution paths (kernels_discretize.hip; host reference: mpfmt_host_discretize) --------------------------------
+int32_t mpfmt_discretize_batch(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, const int64_t* offsets,
+                               int64_t B, int32_t mode, double dt, int64_t n_samples, int32_t append_end, double* out_X, double* out_T,
+                               int32_t* out_seg, int64_t* out_offsets, int64_t out_cap, mpfmt_disc_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (B < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "discretize: B < 0");
+    if (!offsets || !out_offsets) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "discretize: offsets / out_offsets is NULL");
+    if (B > 0 && (!P || !info)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "discretize: P / info is NULL");
+    if (out_cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "discretize: out_cap < 0");
+    if (out_cap > 0 && (!out_X || !out_T)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "discretize: out_X / out_T is NULL");
+    if (const char* why = mpfmt_disc_check(space, d, params, mode, dt, n_samples)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "discretize: %s", why);
+    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "discretize runs on an unsharded ctx");
+    if (offsets[0] != 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "discretize: offsets[0] must be 0");
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t n = offsets[b + 1] - offsets[b];
+        if (n < 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "discretize: path %lld has %lld states (a path has at least 2)", (long long)(b + 1), (long long)n);
+    }
+    const int64_t total = offsets[B];
+    if (total > (int64_t)1 << 40) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "discretize: the batch holds more than 2^40 states");
+    for (int64_t i = 0; i < total * d; ++i)
+        if (!std::isfinite(P[i])) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "discretize: non-finite coordinate in state %lld", (long long)(i / d + 1));
+    out_offsets[0] = 0;
+    ctx->disc_steps = 0; ctx->disc_samples = 0;
+    if (B == 0) return MPFMT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return mpfmt_discretize_batch_device(ctx, space, d, params, P, offsets, B, mode, dt, n_samples, append_end, out_X, out_T, out_seg, out_offsets,
+                                         out_cap, info);
+}
+
+int32_t mpfmt_discretize(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, int64_t n, int32_t mode, double dt,
+                         int64_t n_samples, int32_t append_end, double* out_X, double* out_T, int32_t* out_seg, int64_t out_cap,
+                         mpfmt_disc_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (n < 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "discretize: a path has at least 2 states");
+    const int64_t offsets[2] = {0, n};
+    int64_t out_offsets[2];
+    return mpfmt_discretize_batch(ctx, space, d, params, P, offsets, 1, mode, dt, n_samples, append_end, out_X, out_T, out_seg, out_offsets, out_cap,
+                                  info);
+}
+
 // graph + mask (reused when resident), checkpts bitmap, field from init_idx, goal extraction; k > 0: the k-nearest graph
 static int32_t prmstar_impl(mpfmt_ctx* ctx, double r, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
                             int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
@@ -2747,6 +2789,8 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "steer_roadmap_steered") == 0) { *value = ctx->steer_roadmap_steered; return MPFMT_OK; }
     if (strcmp(name, "shortcut_tests_evaluated") == 0) { *value = ctx->shortcut_tests; return MPFMT_OK; }
     if (strcmp(name, "shortcut_checks") == 0) { *value = ctx->shortcut_checks; return MPFMT_OK; }
+    if (strcmp(name, "discretize_steps") == 0) { *value = ctx->disc_steps; return MPFMT_OK; }
+    if (strcmp(name, "discretize_samples") == 0) { *value = ctx->disc_samples; return MPFMT_OK; }
     if (strcmp(name, "steer_swept") == 0) { *value = (ctx->steer_filled && ctx->steer_swept) ? 1 : 0; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_path") == 0) { *value = ctx->bd_path; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_columns") == 0) { *value = ctx->bd_columns; return MPFMT_OK; }

@@ -3,6 +3,7 @@
 // this file is compiled into the library by hipcc and, unchanged, into the sanitizer test binary of tests/asan/ by g++
 // (-fsanitize=address,undefined).
 #include "mpfmt_host.h"
+#include "discretize_core.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -800,4 +801,102 @@ int32_t mpfmt_host_roadmap_query(int64_t N, int32_t d, const double* X, const in
     if ((int64_t)rev.size() > cap) return MPFMT_ERR_CAPACITY;
     for (size_t i = 0; i < rev.size(); ++i) path[i] = rev[rev.size() - 1 - i];
     return MPFMT_OK;
+}
+
+// ---- time discretisation of one solution path (include/mpfmt.h, "time discretisation"): steering_control(SS, path...)
+// (statespaces.jl:147), duration(::ControlSequence) and propagate(d, v, us, times) (statespaces.jl:104-119) statement for statement --
+// the running (v, t0, i) of the reference's loop, not a search.  The CPU baseline and the checker of mpfmt_discretize_batch
+// (kernels_discretize.hip), which shares the per-step arithmetic of discretize_core.h with this loop.
+namespace {
+
+template <class SP>
+int32_t disc_host(const double* prm, const double* P, int64_t n, int32_t mode, double dt, int64_t n_samples, int32_t append_end, double* out_X,
+                  double* out_T, int32_t* out_seg, int64_t out_cap, mpfmt_disc_info* info)
+{
+    constexpr int d = SP::d, nc = SP::nc, maxs = SP::maxs;
+    std::vector<double> st, sc;                                          // us: durations, controls
+    std::vector<int64_t> sp;                                             // the pair a step came from (0-based)
+    for (int64_t i = 0; i + 1 < n; ++i) {                                // vcat([steering_control(SS.dist, V[i], V[i+1]) ...]...)
+        double t[maxs], c[maxs * nc];
+        const int L = SP::steer(P + i * d, P + (i + 1) * d, prm, t, c);
+        for (int q = 0; q < L; ++q) { st.push_back(t[q]); sp.push_back(i); sc.insert(sc.end(), c + q * nc, c + (q + 1) * nc); }
+    }
+    const int64_t K = (int64_t)st.size();
+    double tf = 0.0;
+    for (int64_t j = 0; j < K; ++j) tf = tf + st[(size_t)j];             // duration(us)
+    info->steps = K; info->duration = tf;
+    int64_t n_grid = 0, n_out = 0;
+    const bool ok = disc_counts(mode, tf, dt, n_samples, append_end, &n_grid, &n_out);
+    info->n_out = n_out;
+    if (!ok) return MPFMT_ERR_ARG;
+    if (out_cap == 0) return MPFMT_OK;                                   // the size query
+    if (n_out > out_cap) return MPFMT_ERR_CAPACITY;
+    double v[d], nv[d];
+    for (int c = 0; c < d; ++c) v[c] = P[c];
+    double t0 = 0.0;
+    int64_t i = 0;
+    for (int64_t k = 0; k < n_out; ++k) {                                // for t in s
+        const double t = disc_time(mode, k, n_grid, tf, dt, n_samples);
+        while (t >= t0 + st[(size_t)i] && i < K - 1) {
+            const int64_t pr = sp[(size_t)i];
+            SP::full(v, P + pr * d, P + (pr + 1) * d, st[(size_t)i], &sc[(size_t)i * nc], nv);
+            for (int c = 0; c < d; ++c) v[c] = nv[c];
+            t0 = t0 + st[(size_t)i];
+            ++i;
+        }
+        const int64_t pr = sp[(size_t)i];
+        const double s = t - t0, ti = st[(size_t)i];
+        double* o = out_X + k * d;
+        if (s <= 0) { for (int c = 0; c < d; ++c) o[c] = v[c]; }
+        else if (s >= ti) SP::full(v, P + pr * d, P + (pr + 1) * d, ti, &sc[(size_t)i * nc], o);
+        else SP::part(v, P + pr * d, P + (pr + 1) * d, ti, &sc[(size_t)i * nc], s, o);
+        out_T[k] = t;
+        if (out_seg) out_seg[k] = (int32_t)(pr + 1);
+    }
+    return MPFMT_OK;
+}
+
+}  // namespace
+
+const char* mpfmt_disc_check(int32_t space, int32_t d, const double* params, int32_t mode, double dt, int64_t n_samples)
+{
+    if (space == MPFMT_SPACE_EUCLID) { if (d < 1 || d > MPFMT_MAX_DIM) return "d does not fit the Euclidean space"; }
+    else if (space == MPFMT_SPACE_DI) { if (d < 2 || d > 12 || (d & 1)) return "the double integrator has d = 2 m, m = 1 .. 6"; }
+    else if (space == MPFMT_SPACE_DUBINS || space == MPFMT_SPACE_REEDSSHEPP) { if (d != 3) return "the car spaces have d = 3"; }
+    else return "unknown space";
+    if (space != MPFMT_SPACE_EUCLID) {
+        if (!params) return "params is NULL";
+        if (!std::isfinite(params[0]) || !std::isfinite(params[1]) || !(params[0] > 0) || !(params[1] > 0)) return "params must be finite and > 0";
+    }
+    if (mode == MPFMT_DISC_DT) { if (!std::isfinite(dt) || !(dt > 0)) return "dt must be finite and > 0"; }
+    else if (mode == MPFMT_DISC_N) { if (n_samples < 2 || n_samples > 2147483647LL) return "n_samples must lie in [2, 2^31 - 1]"; }
+    else return "unknown mode";
+    return nullptr;
+}
+
+int32_t mpfmt_host_discretize(int32_t space, int32_t d, const double* params, const double* P, int64_t n, int32_t mode, double dt,
+                              int64_t n_samples, int32_t append_end, double* out_X, double* out_T, int32_t* out_seg, int64_t out_cap,
+                              mpfmt_disc_info* info)
+{
+    if (!P || !info || out_cap < 0 || (out_cap > 0 && (!out_X || !out_T))) return MPFMT_ERR_ARG;
+    if (mpfmt_disc_check(space, d, params, mode, dt, n_samples)) return MPFMT_ERR_ARG;
+    if (n < 2) return MPFMT_ERR_ARG;
+    for (int64_t i = 0; i < n * d; ++i) if (!std::isfinite(P[i])) return MPFMT_ERR_ARG;
+    memset(info, 0, sizeof *info);
+#define DISC_GO(SP) return disc_host<SP>(params, P, n, mode, dt, n_samples, append_end, out_X, out_T, out_seg, out_cap, info)
+    if (space == MPFMT_SPACE_DUBINS) DISC_GO(disc_car<1>);
+    if (space == MPFMT_SPACE_REEDSSHEPP) DISC_GO(disc_car<2>);
+    if (space == MPFMT_SPACE_DI) {
+        switch (d / 2) {
+            case 1: DISC_GO(disc_di<1>); case 2: DISC_GO(disc_di<2>); case 3: DISC_GO(disc_di<3>);
+            case 4: DISC_GO(disc_di<4>); case 5: DISC_GO(disc_di<5>); default: DISC_GO(disc_di<6>);
+        }
+    }
+    switch (d) {
+        case 1: DISC_GO(disc_euclid<1>); case 2: DISC_GO(disc_euclid<2>); case 3: DISC_GO(disc_euclid<3>); case 4: DISC_GO(disc_euclid<4>);
+        case 5: DISC_GO(disc_euclid<5>); case 6: DISC_GO(disc_euclid<6>); case 7: DISC_GO(disc_euclid<7>); case 8: DISC_GO(disc_euclid<8>);
+        case 9: DISC_GO(disc_euclid<9>); case 10: DISC_GO(disc_euclid<10>); case 11: DISC_GO(disc_euclid<11>); case 12: DISC_GO(disc_euclid<12>);
+        case 13: DISC_GO(disc_euclid<13>); case 14: DISC_GO(disc_euclid<14>); case 15: DISC_GO(disc_euclid<15>); default: DISC_GO(disc_euclid<16>);
+    }
+#undef DISC_GO
 }

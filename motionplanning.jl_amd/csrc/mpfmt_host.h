@@ -25,3 +25,6 @@ void mpfmt_directed_fmt_recursion(int64_t N, const int64_t* colptr, const int32_
 // chosen goal node z (0-based, -1 = none)
 void mpfmt_walk_back(int64_t N, const double* C, const int64_t* A, int64_t init_idx, int64_t z, int64_t* path, mpfmt_fmt_result* res);
 int64_t mpfmt_validate_csc(int64_t N, const int64_t* colptr, const int64_t* rowval, char* err, size_t errlen);
+// argument check shared by mpfmt_host_discretize and mpfmt_discretize_batch: NULL when space / d / params / mode / dt / n_samples are
+// acceptable, else what is wrong with them
+const char* mpfmt_disc_check(int32_t space, int32_t d, const double* params, int32_t mode, double dt, int64_t n_samples);

@@ -414,6 +414,8 @@ struct mpfmt_ctx {
 
     // ---- adaptive shortcutting (kernels_shortcut.hip): stats of the last batch ----
     int64_t shortcut_tests = 0, shortcut_checks = 0;
+    // ---- time discretisation (kernels_discretize.hip): stats of the last batch ----
+    int64_t disc_steps = 0, disc_samples = 0;
 
     // ---- roadmap queries for external states (kernels_roadmap.hip, the seeded field of kernels_sssp.hip) ----
     mpfmt_dbuf<double> sssp_seed;         // [N] seed labels of the running pair query (+Inf: no usable edge from the start)
@@ -679,6 +681,12 @@ void mpfmt_sssp_multi_free(mpfmt_ctx* ctx);
 // the batch on the device; arguments already validated (mpfmt_adaptive_shortcut_batch, mpfmt_capi.hip)
 int32_t mpfmt_shortcut_batch_device(mpfmt_ctx* ctx, const double* P, const int64_t* offsets, int64_t B, int32_t iterations, int64_t max_states,
                                     double* out_P, int64_t* out_offsets, int64_t out_cap, double* cumcost, mpfmt_shortcut_info* info);
+
+// kernels_discretize.hip ---------------------------------------------------------------------------
+// the batch on the device; arguments already validated (mpfmt_discretize_batch, mpfmt_capi.hip)
+int32_t mpfmt_discretize_batch_device(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, const int64_t* offsets,
+                                      int64_t B, int32_t mode, double dt, int64_t n_samples, int32_t append_end, double* out_X, double* out_T,
+                                      int32_t* out_seg, int64_t* out_offsets, int64_t out_cap, mpfmt_disc_info* info);
 
 // kernels_expand.hip ----------------------------------------------------------------------------
 int32_t mpfmt_launch_expand(mpfmt_ctx* ctx, const uint64_t* d_W, const uint64_t* d_H, const uint64_t* d_F,

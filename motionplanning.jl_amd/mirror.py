@@ -888,3 +888,67 @@ def shortcut_paths_(P, nodes, iterations=10, max_states=256):
     out = P.ctx.adaptive_shortcut([np.ascontiguousarray(P.V.V[p - 1]) for p in idx], iterations, max_states)
     P.CC.count += sum(i["collision_checks"] for _, _, i in out)
     return out
+
+
+# ---- path discretisation (src/postprocessors.jl:59-83) -----------------------------------------------------------------------------
+def _disc_space(P):
+    """(space, params) of the discretise calls for P.SS: the double integrator's Newton bracket is the radius the plan was made with."""
+    dist = P.SS.dist
+    if isinstance(dist, LinearQuadratic):
+        r = float(P.solution.metadata.get("r", 0.0)) if P.solution is not None else 0.0
+        return _lib.SPACE_DI, (dist.rho, r if r > 0 else dist.cmax)
+    if isinstance(dist, DubinsExact):
+        return _lib.SPACE_DUBINS, (dist.r, dist.s)
+    if isinstance(dist, ReedsSheppExact):
+        return _lib.SPACE_REEDSSHEPP, (dist.r, dist.s)
+    return _lib.SPACE_EUCLID, None
+
+
+def _solution_states(P, usesmoothed):
+    """The states postprocessors.jl:62-68 picks: the smoothed path when there is one and it is wanted, else the samples of the path."""
+    if P.status != "solved":
+        raise RuntimeError("Cannot post-process unsolved problem! (path discretization)")
+    S = P.solution
+    if usesmoothed and "smoothed_path" in S.metadata:
+        return np.ascontiguousarray(S.metadata["smoothed_path"])
+    return np.ascontiguousarray(P.V.V[S.metadata["path"] - 1])
+
+
+def _discretize_solution(P, usesmoothed, **kw):
+    path = _solution_states(P, usesmoothed)
+    space, params = _disc_space(P)
+    (X, T, seg), info = P.ctx.discretize(path, space, params, **kw)
+    S = P.solution
+    S.metadata["discretized_path"] = X
+    S.metadata["discretized_times"] = T
+    S.metadata["discretized_segments"] = seg
+    S.metadata["discretized_info"] = info
+    return X
+
+
+def time_discretize_solution_(P, dt, usesmoothed=True):
+    """time_discretize_solution!(P, dt, usesmoothed) (postprocessors.jl:61-71) on the device: the solution's trajectory at the times
+    0:dt:duration.  Fills metadata["discretized_path"] (n_out, d), ["discretized_times"], ["discretized_segments"] (the 1-based path pair
+    of every sample) and ["discretized_info"]; returns the discretised path (include/mpfmt.h, "time discretisation")."""
+    return _discretize_solution(P, usesmoothed, dt=float(dt))
+
+
+def time_space_solution_(P, n, usesmoothed=True):
+    """time_space_solution!(P, n, usesmoothed) (postprocessors.jl:73-83) on the device: n states at equal times from 0 to the duration.
+    Fills the same metadata as time_discretize_solution_."""
+    return _discretize_solution(P, usesmoothed, n=int(n))
+
+
+def discretize_paths_(P, nodes_or_index_paths, dt=None, n=None):
+    """The multi-query use after a planner or cost_to_go_: a batch of paths discretised in ONE call on the device.
+    nodes_or_index_paths: sample indices (1-based) -- their tree paths out of metadata["tree"] are taken -- or a list of index paths as
+    tree_paths / successor_paths return them.  Returns (a list of (X, T, seg), a list of info dicts), one per path."""
+    if P.solution is None:
+        raise RuntimeError("Cannot post-process unsolved problem! (path discretization)")
+    items = list(nodes_or_index_paths)
+    if items and np.ndim(items[0]) == 0:
+        if "tree" not in P.solution.metadata:
+            raise RuntimeError("discretize_paths_ with sample indices needs a planner's tree (metadata[\"tree\"])")
+        items = tree_paths(P.solution.metadata["tree"], items, int(P.solution.metadata["path"][0]))
+    space, params = _disc_space(P)
+    return P.ctx.discretize([np.ascontiguousarray(P.V.V[np.asarray(p, dtype=np.int64) - 1]) for p in items], space, params, dt=dt, n=n)
