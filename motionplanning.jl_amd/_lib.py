@@ -754,12 +754,7 @@ class Context:
         return xs[:n].copy(), ym[:n].copy(), cm[:n].copy(), fr[:n].astype(bool)
 
     def fmtstar(self, r, goal_kind, goal_params, init_idx=1, checkpts=True):
-        g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A, Cc, path = self._fmt_arrays()
-        res = FmtResult()
-        self._chk(self._L.mpfmt_fmtstar(self._h, float(r), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g),
-                                        _ip(A), _dp(Cc), _ip(path), C.byref(res)))
-        return self._fmt_out(res, A, Cc, path)
+        return self._plan(self._L.mpfmt_fmtstar, (float(r),), goal_kind, goal_params, init_idx, checkpts)
 
     # ---- k-nearest connections (connections = :K, fmt.jl:6,17-19) -------------------------------
     def knn_graph(self, k):
@@ -782,12 +777,7 @@ class Context:
 
     def knn_fmtstar(self, k, goal_kind, goal_params, init_idx=1, checkpts=True):
         """fmtstar! with connections = :K: forward sets = mutual k-nearest, backward sets = k-nearest; same dict as fmtstar."""
-        g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A, Cc, path = self._fmt_arrays()
-        res = FmtResult()
-        self._chk(self._L.mpfmt_knn_fmtstar(self._h, int(k), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g),
-                                            _ip(A), _dp(Cc), _ip(path), C.byref(res)))
-        return self._fmt_out(res, A, Cc, path)
+        return self._plan(self._L.mpfmt_knn_fmtstar, (int(k),), goal_kind, goal_params, init_idx, checkpts)
 
     # ---- PRM* roadmap queries: shortest paths over the resident free-edge graph ------------------------------
     def graph_sssp(self, sources, checkpts=True, want_parents=True):
@@ -1005,23 +995,28 @@ class Context:
     def prmstar(self, r, goal_kind, goal_params, init_idx=1, checkpts=True):
         """PRM*: graph_step_device(r) (reused when resident), then the exact cost-to-come field of init_idx over the free-edge graph and
         the best goal sample; same dict as fmtstar, with C = +Inf for unreached samples."""
-        g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A, Cc, path = self._fmt_arrays()
-        res = FmtResult()
-        self._chk(self._L.mpfmt_prmstar(self._h, float(r), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g),
-                                        _ip(A), _dp(Cc), _ip(path), C.byref(res)))
-        self.nnz = int(res.nnz)
-        return self._fmt_out(res, A, Cc, path)
+        return self._plan(self._L.mpfmt_prmstar, (float(r),), goal_kind, goal_params, init_idx, checkpts, set_nnz=True)
 
     def knn_prmstar(self, k, goal_kind, goal_params, init_idx=1, checkpts=True):
         """prmstar over the (directed) k-nearest graph."""
+        return self._plan(self._L.mpfmt_knn_prmstar, (int(k),), goal_kind, goal_params, init_idx, checkpts, set_nnz=True)
+
+    def _plan(self, fn, lead, goal_kind, goal_params, init_idx, checkpts, wavefront=None, want_tree=True, set_nnz=False):
+        """One single-shot planner call: fn(ctx, *lead, init_idx, checkpts, goal_kind, goal_params[, band, flags], A, C, path, res[, info]).
+        lead = the space's scalars (r | k | the steering parameters); wavefront = (band, flags) for the forms with the recursion on the
+        device, which also return their counters and may go without the tree; set_nnz: the roadmap planners leave their graph resident
+        and self.nnz says so."""
         g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A, Cc, path = self._fmt_arrays()
-        res = FmtResult()
-        self._chk(self._L.mpfmt_knn_prmstar(self._h, int(k), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g),
-                                            _ip(A), _dp(Cc), _ip(path), C.byref(res)))
-        self.nnz = int(res.nnz)
-        return self._fmt_out(res, A, Cc, path)
+        A, Cc, path = self._fmt_arrays(want_tree)
+        res, info = FmtResult(), WfInfo()
+        args = [self._h, *lead, int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g)]
+        if wavefront is not None:
+            args += [float(wavefront[0]), int(wavefront[1])]
+        args += [_ip(A), _dp(Cc), _ip(path), C.byref(res)] + ([C.byref(info)] if wavefront is not None else [])
+        self._chk(fn(*args))
+        if set_nnz:
+            self.nnz = int(res.nnz)
+        return self._fmt_out(res, A, Cc, path) if wavefront is None else self._wf_out(res, info, A, Cc, path)
 
     def _fmt_arrays(self, want_tree=True):
         """The output arrays of a plan: parents A and costs C (None without the tree) and the path."""
@@ -1048,13 +1043,9 @@ class Context:
                           want_tree=True):
         """fmtstar! with the recursion on the device (include/mpfmt.h): band = cost width of a batch; single = one node per
         step (the reference's order exactly)."""
-        g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A, Cc, path = self._fmt_arrays(want_tree)
-        res, info = FmtResult(), WfInfo()
         flags = (WF_SINGLE if single else 0) | (WF_EAGER if eager else 0) | (WF_LAZY if lazy else 0)
-        self._chk(self._L.mpfmt_fmtstar_wavefront(self._h, float(r), int(init_idx), int(bool(checkpts)), int(goal_kind), _dp(g), float(band),
-                                                  flags, _ip(A), _dp(Cc), _ip(path), C.byref(res), C.byref(info)))
-        return self._wf_out(res, info, A, Cc, path)
+        return self._plan(self._L.mpfmt_fmtstar_wavefront, (float(r),), goal_kind, goal_params, init_idx, checkpts, wavefront=(band, flags),
+                          want_tree=want_tree)
 
     def wf_begin(self, r, goal_kind, goal_params, band=0.0, single=False, eager=False, init_idx=1, checkpts=True, lazy=False):
         g = np.ascontiguousarray(goal_params, dtype=np.float64)
@@ -1175,31 +1166,10 @@ class Context:
         self._chk(getattr(self._L, f"mpfmt_{space}_graph_edges_free")(self._h, _up(mask), nseg.ctypes.data_as(c_u8_p)))
         return mask[:nwords(n)], nseg[:n]
 
-    def _steer_fmtstar(self, space, params, goal_kind, goal_params, init_idx, checkpts):
-        g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A, Cc, path = self._fmt_arrays()
-        res = FmtResult()
-        self._chk(getattr(self._L, f"mpfmt_{space}_fmtstar")(self._h, *map(float, params), int(init_idx), int(bool(checkpts)), int(goal_kind),
-                                                             _dp(g), _ip(A), _dp(Cc), _ip(path), C.byref(res)))
-        return self._fmt_out(res, A, Cc, path)
-
-    def _steer_prmstar(self, space, params, goal_kind, goal_params, init_idx, checkpts):
-        g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A, Cc, path = self._fmt_arrays()
-        res = FmtResult()
-        self._chk(getattr(self._L, f"mpfmt_{space}_prmstar")(self._h, *map(float, params), int(init_idx), int(bool(checkpts)), int(goal_kind),
-                                                             _dp(g), _ip(A), _dp(Cc), _ip(path), C.byref(res)))
-        self.nnz = int(res.nnz)
-        return self._fmt_out(res, A, Cc, path)
-
-    def _steer_fmtstar_wavefront(self, space, params, goal_kind, goal_params, band, single, init_idx, checkpts, want_tree=True):
-        g = np.ascontiguousarray(goal_params, dtype=np.float64)
-        A, Cc, path = self._fmt_arrays(want_tree)
-        res, info = FmtResult(), WfInfo()
-        self._chk(getattr(self._L, f"mpfmt_{space}_fmtstar_wavefront")(self._h, *map(float, params), int(init_idx), int(bool(checkpts)),
-                                                                       int(goal_kind), _dp(g), float(band), WF_SINGLE if single else 0,
-                                                                       _ip(A), _dp(Cc), _ip(path), C.byref(res), C.byref(info)))
-        return self._wf_out(res, info, A, Cc, path)
+    def _steer_plan(self, space, solver, params, goal_kind, goal_params, init_idx, checkpts, **kw):
+        """_plan for mpfmt_{space}_{solver}: solver = fmtstar | prmstar | fmtstar_wavefront, params = the steering parameters."""
+        return self._plan(getattr(self._L, f"mpfmt_{space}_{solver}"), map(float, params), goal_kind, goal_params, init_idx, checkpts,
+                          set_nnz=solver == "prmstar", **kw)
 
     def dubins_graph(self, turn_radius, speed, r):
         """Chopped backward sets of the Dubins quasi-metric, CSC 1-based: (colptr, rowval, nzval)."""
@@ -1216,7 +1186,7 @@ class Context:
         return cost[:n], ctrl[:n]
 
     def dubins_fmtstar(self, turn_radius, speed, r, goal_kind, goal_params, init_idx=1, checkpts=True):
-        return self._steer_fmtstar("dubins", (turn_radius, speed, r), goal_kind, goal_params, init_idx, checkpts)
+        return self._steer_plan("dubins", "fmtstar", (turn_radius, speed, r), goal_kind, goal_params, init_idx, checkpts)
 
     def reedsshepp_graph(self, turn_radius, speed, r):
         """Chopped Reeds-Shepp neighbourhoods, CSC 1-based: column v = rows w with nzval = reedsshepp(v, w)."""
@@ -1235,7 +1205,7 @@ class Context:
         return cost[:n], ctrl[:n], nsegs[:n]
 
     def reedsshepp_fmtstar(self, turn_radius, speed, r, goal_kind, goal_params, init_idx=1, checkpts=True):
-        return self._steer_fmtstar("reedsshepp", (turn_radius, speed, r), goal_kind, goal_params, init_idx, checkpts)
+        return self._steer_plan("reedsshepp", "fmtstar", (turn_radius, speed, r), goal_kind, goal_params, init_idx, checkpts)
 
     # ---- closest obstacle points ----------------------------------------------------------------
     def closest(self, P, W=None):
@@ -1397,24 +1367,26 @@ class Context:
         return cost[:n], t[:n]
 
     def di_fmtstar(self, rho, r, goal_kind, goal_params, init_idx=1, checkpts=True):
-        return self._steer_fmtstar("di", (rho, r), goal_kind, goal_params, init_idx, checkpts)
+        return self._steer_plan("di", "fmtstar", (rho, r), goal_kind, goal_params, init_idx, checkpts)
 
     def di_prmstar(self, rho, r, goal_kind, goal_params, init_idx=1, checkpts=True):
         """PRM* in the double-integrator space (mpfmt_di_prmstar): the graph and its sweep (reused while resident and valid, also after
         boxes_add / boxes_remove), the exact cost-to-come field of init_idx and the best goal sample; the dict of prmstar."""
-        return self._steer_prmstar("di", (rho, r), goal_kind, goal_params, init_idx, checkpts)
+        return self._steer_plan("di", "prmstar", (rho, r), goal_kind, goal_params, init_idx, checkpts)
 
     def car_prmstar(self, car, turn_radius, speed, r, goal_kind, goal_params, init_idx=1, checkpts=True):
         """dubins / reedsshepp PRM* (mpfmt_dubins_prmstar, mpfmt_reedsshepp_prmstar); the dict of prmstar."""
-        return self._steer_prmstar(car, (turn_radius, speed, r), goal_kind, goal_params, init_idx, checkpts)
+        return self._steer_plan(car, "prmstar", (turn_radius, speed, r), goal_kind, goal_params, init_idx, checkpts)
 
     def car_fmtstar_wavefront(self, car, turn_radius, speed, r, goal_kind, goal_params, band=0.0, single=False, init_idx=1, checkpts=True):
         """dubins / reedsshepp planner with the recursion on the device."""
-        return self._steer_fmtstar_wavefront(car, (turn_radius, speed, r), goal_kind, goal_params, band, single, init_idx, checkpts)
+        return self._steer_plan(car, "fmtstar_wavefront", (turn_radius, speed, r), goal_kind, goal_params, init_idx, checkpts,
+                                wavefront=(band, WF_SINGLE if single else 0))
 
     def di_fmtstar_wavefront(self, rho, r, goal_kind, goal_params, band=0.0, single=False, init_idx=1, checkpts=True, want_tree=True):
         """di_fmtstar with the recursion on the device (directed wavefront form)."""
-        return self._steer_fmtstar_wavefront("di", (rho, r), goal_kind, goal_params, band, single, init_idx, checkpts, want_tree)
+        return self._steer_plan("di", "fmtstar_wavefront", (rho, r), goal_kind, goal_params, init_idx, checkpts,
+                                wavefront=(band, WF_SINGLE if single else 0), want_tree=want_tree)
 
     # ---- device-resident -------------------------------------------------------------------------
     def graph_build_device(self, r):

@@ -903,7 +903,7 @@ int32_t mpfmt_wf_begin(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t check
     // r-disc graph (reused when one of this radius is resident); the edge tests stay lazy unless the checker has no
     // lane-per-obstacle form here (2-D SAT world, non-identity workspace) or the caller asks for the eager mask
     const bool lazy_ok = ctx->cc_kind == 0 && ctx->dw == d;
-    if (!(ctx->graph_filled && ctx->graph_r == r && !ctx->knn_k)) {
+    if (!euclid_resident(ctx, r)) {
         // no graph of this radius is resident: the STEP builds it with every edge's bit (edge tests fused into the build: ~0.4 ms more
         // than the graph alone at the north star), and the recursion then reads bits instead of testing ~1e6 edges one wavefront at a
         // time (2.4 ms); MPFMT_WF_LAZY keeps the graph-only build and the lazy tests
@@ -914,7 +914,7 @@ int32_t mpfmt_wf_begin(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t check
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     auto t2 = std::chrono::steady_clock::now();
     // (a mask a step left for this graph and this obstacle set is used, not recomputed: upload_boxes / set_state_bounds void graph_swept)
-    const bool resident = ctx->graph_swept && ctx->graph_filled && ctx->graph_r == r && !ctx->knn_k && ctx->graph_free && !(flags & MPFMT_WF_LAZY);
+    const bool resident = ctx->graph_swept && euclid_resident(ctx, r) && ctx->graph_free && !(flags & MPFMT_WF_LAZY);
     s->use_mask = ((flags & MPFMT_WF_EAGER) || !lazy_ok || resident) ? 1 : 0;
     if ((rc = mpfmt_sweep_prepare_ss(ctx))) return rc;
     s->all_in = (!ctx->ss.has || ctx->ssflag_all_in) ? 1 : 0;

@@ -575,6 +575,19 @@ int32_t mpfmt_graph_step_finish(mpfmt_ctx* ctx, int64_t* nnz)
     return MPFMT_OK;
 }
 
+// the resident colptr handed to the caller, 1-based: converted in scratch, copied, and there when this returns
+static int32_t colptr_to_host(mpfmt_ctx* ctx, int64_t* colptr)
+{
+    const int64_t n1 = ctx->N + 1;
+    void* scr;
+    int32_t rc;
+    if ((rc = mpfmt_scratch(ctx, sizeof(int64_t) * n1, &scr))) return rc;
+    hipLaunchKernelGGL(k_add1_i64, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, ctx->stream, ctx->colptr, n1, (int64_t*)scr);
+    HIPCHK(ctx, hipMemcpyAsync(colptr, scr, sizeof(int64_t) * n1, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return MPFMT_OK;
+}
+
 int32_t mpfmt_rdisc_count(mpfmt_ctx* ctx, double r, int64_t* colptr, int64_t* nnz)
 {
     if (!ctx) return MPFMT_ERR_ARG;
@@ -585,12 +598,7 @@ int32_t mpfmt_rdisc_count(mpfmt_ctx* ctx, double r, int64_t* colptr, int64_t* nn
     int32_t rc;
     ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
     if ((rc = mpfmt_launch_rdisc_count(ctx, r))) return rc;
-    const int64_t n1 = ctx->N + 1;
-    void* scr;
-    if ((rc = mpfmt_scratch(ctx, sizeof(int64_t) * n1, &scr))) return rc;
-    hipLaunchKernelGGL(k_add1_i64, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, ctx->stream, ctx->colptr, n1, (int64_t*)scr);
-    HIPCHK(ctx, hipMemcpyAsync(colptr, scr, sizeof(int64_t) * n1, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = colptr_to_host(ctx, colptr))) return rc;
     *nnz = ctx->nnz;
     return MPFMT_OK;
 }
@@ -1177,9 +1185,9 @@ int32_t mpfmt_expand(mpfmt_ctx* ctx, const uint64_t* W, const uint64_t* H, const
     return rc;
 }
 
-// ---- fmtstar -------------------------------------------------------------------------------------------
+// ---- what the single-shot planners share with the calls around them (the planners themselves: "one driver", below) ------------
 
-// The sequential recursion itself (fmt.jl:43-101 over finished arrays), the binary heap and the goal predicates live in
+// The sequential recursion itself (fmt.jl:43-101 over finished arrays), the binary heap, the goal predicates and the goal pick live in
 // mpfmt_host.cpp: plain C++ without HIP, so the same translation unit is also built with -fsanitize=address,undefined for the
 // CPU test suite (tests/asan/).
 static inline bool bit(const std::vector<uint64_t>& m, int64_t i) { return (m[i >> 6] >> (i & 63)) & 1ull; }
@@ -1222,59 +1230,11 @@ static int32_t graph_to_host(mpfmt_ctx* ctx, bool want_nseg, host_graph& g)
     return MPFMT_OK;
 }
 
-int32_t mpfmt_fmtstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t checkpts,
-                      int32_t goal_kind, const double* goal_params,
-                      int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!A || !C || !path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
-    if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
-    if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
-    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "fmtstar runs on an unsharded ctx");
-    const int64_t N = ctx->N;
-    const int d = ctx->d;
-    if (init_idx < 1 || init_idx > N) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "init_idx out of range");
-    if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
-    if (!(r > 0.0) || !std::isfinite(r)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "radius must be finite and > 0");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    memset(res, 0, sizeof *res);
-    res->cost = INFINITY;
-    int32_t rc;
-    stamp t[6];
-
-    // checkpts bitmap F (fmt.jl:31-36) -- also answers is_free_state(init) (fmt.jl:24-29)
-    std::vector<uint64_t> F((N + 63) / 64, 0);
-    t[0] = now();
-    if ((rc = mpfmt_points_free(ctx, nullptr, N, F.data()))) return rc;
-    if (!bit(F, init_idx - 1)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
-    t[1] = now();
-
-    // r-disc graph + per-edge free mask, all edges, on the device.  A filled graph of the same samples and radius (a
-    // previous plan, or mpfmt_graph_import) is reused: only the obstacle-dependent sweep is redone.
-    if (!(ctx->graph_filled && ctx->graph_r == r && !ctx->knn_k) && (rc = mpfmt_graph_build_device(ctx, r, nullptr))) return rc;
-    t[2] = now();
-    ctx->pend_valid = false;
-    if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    t[3] = now();
-    host_graph g;
-    if ((rc = graph_to_host(ctx, false, g))) return rc;
-    std::vector<double> X((size_t)N * d);
-    HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * (size_t)N * d, hipMemcpyDeviceToHost));
-    t[4] = now();
-
-    if ((rc = mpfmt_host_fmt_recursion(N, d, X.data(), g.colptr.data(), g.rowval.data(), g.nzval.data(), g.efree.data(),
-                                       checkpts ? F.data() : nullptr, ctx->ss.has ? ctx->ss.lo : nullptr,
-                                       ctx->ss.has ? ctx->ss.hi : nullptr, init_idx, goal_kind, goal_params, A, C, path, res)))
-        return mpfmt_fail(ctx, rc, "host recursion rejected its arguments");
-    t[5] = now();
-    fmt_times(ctx, res, t);
-    return MPFMT_OK;
-}
-
 // ---- k-nearest connections (connections = :K, fmt.jl:6,17-19; mutualknnF! / knnB!, nearneighbors.jl:9-11; kernels_knn.hip) ----------
 
 static bool knn_resident(const mpfmt_ctx* ctx) { return ctx->knn_k > 0 && ctx->graph_filled; }
+// ... and it is the graph a call with this k would build: a column holds min(k, N - 1) entries
+static bool knn_resident_k(const mpfmt_ctx* ctx, int64_t k) { return knn_resident(ctx) && std::min(ctx->knn_k, ctx->N - 1) == std::min(k, ctx->N - 1); }
 
 int32_t mpfmt_knn_count(mpfmt_ctx* ctx, int64_t k, int64_t* colptr, int64_t* nnz)
 {
@@ -1286,12 +1246,7 @@ int32_t mpfmt_knn_count(mpfmt_ctx* ctx, int64_t k, int64_t* colptr, int64_t* nnz
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t rc;
     if ((rc = mpfmt_knn_build(ctx, k))) return rc;
-    const int64_t n1 = ctx->N + 1;
-    void* scr;
-    if ((rc = mpfmt_scratch(ctx, sizeof(int64_t) * n1, &scr))) return rc;
-    hipLaunchKernelGGL(k_add1_i64, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, ctx->stream, ctx->colptr, n1, (int64_t*)scr);
-    HIPCHK(ctx, hipMemcpyAsync(colptr, scr, sizeof(int64_t) * n1, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = colptr_to_host(ctx, colptr))) return rc;
     *nnz = ctx->nnz;
     return MPFMT_OK;
 }
@@ -1335,58 +1290,6 @@ int32_t mpfmt_knn_graph_edges_free(mpfmt_ctx* ctx, uint64_t* mask)
         HIPCHK(ctx, hipMemcpyAsync(mask, ctx->graph_free, sizeof(uint64_t) * words, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
-    return MPFMT_OK;
-}
-
-// fmt.jl:43-101 with nearF = mutualknnF, nearB = knnB: the Euclidean prelude of mpfmt_fmtstar, the k-nearest graph and its sweep on
-// the device, then the directed recursion on the host over the column graph, its transposed view and the mutual bits
-int32_t mpfmt_knn_fmtstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
-                          int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!A || !C || !path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
-    if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
-    if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
-    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "fmtstar runs on an unsharded ctx");
-    const int64_t N = ctx->N;
-    const int d = ctx->d;
-    if (init_idx < 1 || init_idx > N) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "init_idx out of range");
-    if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
-    if (k < 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "k must be >= 1");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    memset(res, 0, sizeof *res);
-    res->cost = INFINITY;
-    int32_t rc;
-    stamp t[6];
-    std::vector<uint64_t> F((N + 63) / 64, 0);
-    t[0] = now();
-    if ((rc = mpfmt_points_free(ctx, nullptr, N, F.data()))) return rc;
-    if (!bit(F, init_idx - 1)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
-    t[1] = now();
-    // (a resident k-nearest graph of the same samples and the same k_eff is reused: only the sweep is redone)
-    if (!(knn_resident(ctx) && std::min(ctx->knn_k, N - 1) == std::min(k, N - 1)) && (rc = mpfmt_knn_build(ctx, k))) return rc;
-    t[2] = now();
-    ctx->pend_valid = false;
-    if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    t[3] = now();
-    host_graph g;
-    if ((rc = graph_to_host(ctx, false, g))) return rc;
-    const size_t words = (size_t)(ctx->nnz + 63) / 64;
-    std::vector<uint64_t> mutual(std::max<size_t>(words, 1), 0);
-    if (words > 0) HIPCHK(ctx, hipMemcpy(mutual.data(), ctx->knn_mutual, sizeof(uint64_t) * words, hipMemcpyDeviceToHost));
-    std::vector<double> X((size_t)N * d);
-    HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * (size_t)N * d, hipMemcpyDeviceToHost));
-    mpfmt_csr_host csr;
-    mpfmt_csr_view csr_view;
-    const mpfmt_csr_view* pre_ptr = nullptr;
-    if (mpfmt_csc_transpose_device(ctx, &csr) == MPFMT_OK) { csr_view = {csr.rowptr.data(), csr.colidx.data(), csr.centry.data()}; pre_ptr = &csr_view; }
-    t[4] = now();
-    auto goal_hit = [&](int64_t z) { return mpfmt_is_goal_pt(&X[(size_t)z * d], d, goal_kind, goal_params); };
-    mpfmt_directed_fmt_recursion(N, g.colptr.data(), g.rowval.data(), g.nzval.data(), g.efree.data(), nullptr, checkpts ? F.data() : nullptr,
-                                 init_idx, goal_hit, A, C, path, res, pre_ptr, mutual.data());
-    t[5] = now();
-    fmt_times(ctx, res, t);
     return MPFMT_OK;
 }
 
@@ -1568,11 +1471,7 @@ int32_t mpfmt_field_goal(mpfmt_ctx* ctx, int32_t goal_kind, const double* goal_p
     HIPCHK(ctx, hipMemcpyAsync(C.data(), ctx->fld_C, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(A.data(), ctx->fld_A, sizeof(int64_t) * (size_t)N, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    // goal node: the reached sample inside the goal region of lowest (C, index)
-    int64_t z = -1;
-    for (int64_t i = 0; i < N; ++i)
-        if (C[i] < INFINITY && (z < 0 || C[i] < C[z]) && mpfmt_is_goal_pt(&X[(size_t)i * d], d, goal_kind, goal_params)) z = i;
-    mpfmt_walk_back(N, C.data(), A.data(), init_idx, z, path, res);
+    mpfmt_walk_back(N, C.data(), A.data(), init_idx, mpfmt_goal_pick(N, d, d, X.data(), C.data(), goal_kind, goal_params), path, res);
     res->nnz = ctx->nnz;
     res->ms_host_loop = std::chrono::duration<double, std::milli>(now() - t0).count();
     return MPFMT_OK;
@@ -1744,77 +1643,6 @@ int32_t mpfmt_discretize(mpfmt_ctx* ctx, int32_t space, int32_t d, const double*
                                   info);
 }
 
-// graph + mask (reused when resident), checkpts bitmap, field from init_idx, goal extraction; k > 0: the k-nearest graph
-static int32_t prmstar_impl(mpfmt_ctx* ctx, double r, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
-                            int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
-{
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!A || !C || !path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
-    if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
-    if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
-    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "prmstar runs on an unsharded ctx");
-    const int64_t N = ctx->N;
-    const int d = ctx->d;
-    if (init_idx < 1 || init_idx > N) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "init_idx out of range");
-    if (goal_kind < 0 || goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", goal_kind);
-    if (k == 0 && (!(r > 0.0) || !std::isfinite(r))) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "radius must be finite and > 0");
-    if (k < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "k must be >= 1");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    memset(res, 0, sizeof *res);
-    res->cost = INFINITY;
-    int32_t rc;
-    stamp t[6];
-    t[0] = now();
-    if ((rc = sssp_point_bitmap(ctx))) return rc;
-    uint64_t init_word = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&init_word, ctx->sssp_F + ((init_idx - 1) >> 6), sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (!((init_word >> ((init_idx - 1) & 63)) & 1ull)) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
-    t[1] = now();
-    t[2] = t[1];
-    if (k > 0) {
-        if (!(knn_resident(ctx) && std::min(ctx->knn_k, N - 1) == std::min(k, N - 1))) {
-            if ((rc = mpfmt_knn_build(ctx, k))) return rc;
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        t[2] = now();
-        if (!ctx->graph_swept) { ctx->pend_valid = false; if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc; }
-    } else if (ctx->graph_filled && ctx->graph_r == r && !ctx->knn_k) {
-        if (!ctx->graph_swept) { ctx->pend_valid = false; if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc; }
-    } else {
-        if ((rc = mpfmt_graph_step_device(ctx, r, nullptr))) return rc;
-        t[2] = now();
-        if (!ctx->graph_swept) { ctx->pend_valid = false; if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc; }
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    t[3] = now();
-    if ((rc = sssp_ready_euclid(ctx))) return rc;
-    t[4] = now();
-    mpfmt_sssp_info inf;
-    if ((rc = mpfmt_sssp_device(ctx, init_idx - 1, checkpts ? ctx->sssp_F : nullptr, C, A, &inf))) return rc;
-    // goal node: the reached sample inside the goal region of lowest (C, index)
-    std::vector<double> X((size_t)N * d);
-    HIPCHK(ctx, hipMemcpy(X.data(), ctx->Xo, sizeof(double) * (size_t)N * d, hipMemcpyDeviceToHost));
-    int64_t z = -1;
-    for (int64_t i = 0; i < N; ++i)
-        if (C[i] < INFINITY && (z < 0 || C[i] < C[z]) && mpfmt_is_goal_pt(&X[(size_t)i * d], d, goal_kind, goal_params)) z = i;
-    mpfmt_walk_back(N, C, A, init_idx, z, path, res);
-    t[5] = now();
-    fmt_times(ctx, res, t);
-    return MPFMT_OK;
-}
-
-int32_t mpfmt_prmstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
-                      int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
-{ return prmstar_impl(ctx, r, 0, init_idx, checkpts, goal_kind, goal_params, A, C, path, res); }
-
-int32_t mpfmt_knn_prmstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
-                          int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
-{
-    if (ctx && k < 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "k must be >= 1");
-    return prmstar_impl(ctx, 0.0, k, init_idx, checkpts, goal_kind, goal_params, A, C, path, res);
-}
-
 // ---- steering spaces: double integrator (LinearQuadratic quasi-metric), Dubins and Reeds-Shepp cars (kernels_di.hip, kernels_car.hip)
 
 static int32_t di_check(mpfmt_ctx* ctx, double rho, double r)
@@ -1832,10 +1660,12 @@ static int32_t di_check(mpfmt_ctx* ctx, double rho, double r)
 // nearneighbors.jl:200-203) or directed (double integrator, Dubins).
 struct steer_space { mpfmt_steer kind; int d, dw; bool symmetric; };
 
+static bool steer_symmetric(mpfmt_steer kind) { return kind == MPFMT_STEER_REEDSSHEPP; }
+
 static steer_space steer_space_of(const mpfmt_ctx* ctx, mpfmt_steer kind)
 {
     if (kind == MPFMT_STEER_DI) return {kind, ctx->d, ctx->d / 2, false};
-    return {kind, 3, 2, kind == MPFMT_STEER_REEDSSHEPP};
+    return {kind, 3, 2, steer_symmetric(kind)};
 }
 
 // is_free_state(v, CC, SS) = in_state_space(v) && point-vs-obstacles on the workspace coordinates, of n states V [n][d] on the host
@@ -2275,149 +2105,318 @@ static int32_t steer_build(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b,
 
 static int32_t steer_sweep(mpfmt_ctx* ctx, mpfmt_steer kind) { return kind == MPFMT_STEER_DI ? mpfmt_di_sweep(ctx) : mpfmt_car_sweep(ctx); }
 
+static bool steer_resident(const mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b, double r)
+{
+    return ctx->steer_filled && ctx->steer_kind == kind && ctx->steer_r == r &&
+           (kind == MPFMT_STEER_DI ? ctx->di_rho == a : (ctx->car_rt == a && ctx->car_sp == b));
+}
+
+// ---- the single-shot planners, every space and solver: one driver ----------------------------------------------------------
+// A plan is five stages -- plan_check, plan_points, plan_graph, a solver, plan_finish -- and an exported planner is a plan_call, a reuse
+// policy and a solver.  What differs between the planners is data of the call: the space, the policy, where the point bitmap lives and a
+// few flags for the checks.
+
+enum plan_space { PLAN_R, PLAN_K, PLAN_STEER };          // Euclidean r-disc graph | Euclidean k-nearest graph | a steering space (kind, a, b, r)
+// what a plan takes from the ctx: nothing (graph and mask anew) | a resident graph of its space and parameters, swept again | that graph
+// and its mask while it is valid (it stays valid across mpfmt_boxes_add / mpfmt_boxes_remove, which bring it up to date in place)
+enum plan_policy { PLAN_REBUILD, PLAN_RESWEEP, PLAN_RESIDENT };
+enum {
+    PLAN_PRM = 1,            // a roadmap planner: "prmstar" in its messages, the Euclidean point bitmap on the device (ctx->sssp_F)
+    PLAN_WAVEFRONT = 2,      // the recursion on the device: A / C / path may be NULL, and res is filled by the solve alone
+    PLAN_K_FIRST = 4,        // mpfmt_knn_prmstar looks at k before anything else
+};
+
+struct plan_call {
+    mpfmt_ctx* ctx; plan_space space; int flags;
+    double r; int64_t k; mpfmt_steer kind; double a, b;                  // the space: r | k | (kind, a, b, r), (a, b) as for steer_build
+    int64_t init_idx; int32_t checkpts, goal_kind; const double* goal_params;
+    int64_t* A; double* C; int64_t* path; mpfmt_fmt_result* res;          // the caller's
+    double band = 0.0; int32_t wf_flags = 0; mpfmt_wf_info* info = nullptr;      // (the wavefront form's)
+    steer_space s{};                                                      // (of `kind`, once the ctx is known to be there)
+    stamp t[6];                                                           // as for fmt_times
+    std::vector<double> X; std::vector<uint64_t> F;                       // the states and the point bitmap, where they are on the host
+    bool steer() const { return space == PLAN_STEER; }
+    // coordinates the goal reads: the state in a Euclidean space; in a steering space the workspace ones, and the whole state for POINT
+    // (StateGoal is exact state equality, goals.jl:128-131)
+    int gd() const { return !steer() ? ctx->d : goal_kind == MPFMT_GOAL_POINT ? s.d : s.dw; }
+};
+
+// The refusals.  Every exported planner keeps its own order of checks and its own words: the Euclidean ones check ctx, pointers, samples,
+// obstacle set, world, init_idx, goal kind and r or k here; a steering one leaves what concerns its space to steer_prelude (plan_points).
+static int32_t plan_check(plan_call& c)
+{
+    mpfmt_ctx* ctx = c.ctx;
+    const bool prm = c.flags & PLAN_PRM, tree = !(c.flags & PLAN_WAVEFRONT);
+    if (ctx && (c.flags & PLAN_K_FIRST) && c.k < 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "k must be >= 1");
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!c.res || !c.goal_params || (tree && (!c.A || !c.C || !c.path))) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
+    if (c.steer()) {                                                     // (only the roadmap planners ask for an unsharded ctx here)
+        if (prm && ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "prmstar runs on an unsharded ctx");
+        c.s = steer_space_of(ctx, c.kind);
+    } else {
+        if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
+        if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no obstacle set uploaded (mpfmt_upload_boxes)");
+        if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "%s runs on an unsharded ctx", prm ? "prmstar" : "fmtstar");
+        if (c.init_idx < 1 || c.init_idx > ctx->N) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "init_idx out of range");
+        if (c.goal_kind < 0 || c.goal_kind > 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown goal kind %d", c.goal_kind);
+        if (c.space == PLAN_R && (!(c.r > 0.0) || !std::isfinite(c.r))) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "radius must be finite and > 0");
+        if (c.space == PLAN_K && c.k < 1) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "k must be >= 1");
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+    }
+    if (tree) {
+        memset(c.res, 0, sizeof *c.res);
+        c.res->cost = INFINITY;
+    }
+    return MPFMT_OK;
+}
+
+// The checkpts bitmap (fmt.jl:31-36), which also answers is_free_state(init) (fmt.jl:24-29).  Three forms, each where its solver reads it:
+// Euclidean FMT* on the host (c.F), Euclidean PRM* on the device (ctx->sssp_F, one word read back), a steering space on the host with the
+// states (c.X, c.F) behind the space's own checks.
+static int32_t plan_points(plan_call& c)
+{
+    mpfmt_ctx* ctx = c.ctx;
+    int32_t rc;
+    if (c.steer()) {
+        c.t[0] = now();
+        if ((rc = steer_prelude(ctx, c.s, c.a, c.r, c.init_idx, c.goal_kind, c.X, c.F))) return rc;
+        c.t[1] = now();
+        return MPFMT_OK;
+    }
+    const int64_t N = ctx->N, i0 = c.init_idx - 1;
+    bool init_free;
+    if (c.flags & PLAN_PRM) {
+        c.t[0] = now();
+        if ((rc = sssp_point_bitmap(ctx))) return rc;
+        uint64_t init_word = 0;
+        HIPCHK(ctx, hipMemcpyAsync(&init_word, ctx->sssp_F + (i0 >> 6), sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        init_free = (init_word >> (i0 & 63)) & 1ull;
+    } else {
+        c.F.assign((size_t)(N + 63) / 64, 0);
+        c.t[0] = now();
+        if ((rc = mpfmt_points_free(ctx, nullptr, N, c.F.data()))) return rc;
+        init_free = bit(c.F, i0);
+    }
+    if (!init_free) return mpfmt_fail(ctx, MPFMT_ERR_INFEASIBLE, "initial state is infeasible");
+    c.t[1] = now();
+    return MPFMT_OK;
+}
+
+// Reuse or build the graph, then reuse or sweep its mask, as the policy says; t[2] = the graph stands, t[3] = its mask does.
+//   steering:  steer_build / steer_sweep; a graph just built is not swept yet.
+//   Euclidean: PLAN_RESWEEP builds the graph alone (mpfmt_graph_build_device, mpfmt_knn_build) and sweeps; PLAN_RESIDENT builds graph and
+//              mask in one (mpfmt_graph_step_device), or the k-nearest graph and then its sweep, and charges a reused r-disc graph nothing
+//              (t[2] = t[1]).
+static int32_t plan_graph(plan_call& c, plan_policy policy)
+{
+    mpfmt_ctx* ctx = c.ctx;
+    int32_t rc;
+    if (c.steer()) {
+        if (!(policy != PLAN_REBUILD && steer_resident(ctx, c.kind, c.a, c.b, c.r)) && (rc = steer_build(ctx, c.kind, c.a, c.b, c.r))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        c.t[2] = now();
+        if (!(policy == PLAN_RESIDENT && ctx->steer_swept) && (rc = steer_sweep(ctx, c.kind))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        c.t[3] = now();
+        return MPFMT_OK;
+    }
+    const bool keep_mask = policy == PLAN_RESIDENT;
+    if (c.space == PLAN_K) {
+        if (!knn_resident_k(ctx, c.k)) {
+            if ((rc = mpfmt_knn_build(ctx, c.k))) return rc;
+            if (keep_mask) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        c.t[2] = now();
+    } else if (!euclid_resident(ctx, c.r)) {
+        if ((rc = keep_mask ? mpfmt_graph_step_device(ctx, c.r, nullptr) : mpfmt_graph_build_device(ctx, c.r, nullptr))) return rc;
+        c.t[2] = now();
+    } else c.t[2] = keep_mask ? c.t[1] : now();
+    if (!(keep_mask && ctx->graph_swept)) {
+        ctx->pend_valid = false;
+        if ((rc = mpfmt_launch_graph_sweep(ctx))) return rc;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    c.t[3] = now();
+    return MPFMT_OK;
+}
+
+// the states on the host, for the Euclidean planners (a steering one has had them since its prelude)
+static int32_t plan_states(plan_call& c)
+{
+    c.X.resize((size_t)c.ctx->N * c.ctx->d);
+    HIPCHK(c.ctx, hipMemcpy(c.X.data(), c.ctx->Xo, sizeof(double) * c.X.size(), hipMemcpyDeviceToHost));
+    return MPFMT_OK;
+}
+
+// The solvers; t[4] = the solve begins, t[5] = it is done.
+
+// the symmetric recursion on the host, column = inball: the r-disc graph (every edge check one test, behind the state-space bounds), and
+// the Reeds-Shepp graph, whose forward and backward sets coincide (the segment counts of its sweep)
+static int32_t plan_solve_symmetric(plan_call& c)
+{
+    mpfmt_ctx* ctx = c.ctx;
+    int32_t rc;
+    host_graph g;
+    if ((rc = graph_to_host(ctx, c.steer(), g))) return rc;
+    if (!c.steer() && (rc = plan_states(c))) return rc;
+    c.t[4] = now();
+    const bool ss = !c.steer() && ctx->ss.has;
+    if ((rc = mpfmt_host_fmt_recursion_impl(ctx->N, ctx->d, c.X.data(), g.colptr.data(), g.rowval.data(), g.nzval.data(), g.efree.data(),
+                                            c.checkpts ? c.F.data() : nullptr, ss ? ctx->ss.lo : nullptr, ss ? ctx->ss.hi : nullptr, c.init_idx,
+                                            c.goal_kind, c.goal_params, c.gd(), c.steer() ? g.nseg.data() : nullptr, c.A, c.C, c.path, c.res)))
+        return mpfmt_fail(ctx, rc, "host recursion rejected its arguments");
+    c.t[5] = now();
+    return MPFMT_OK;
+}
+
+// the forward sets of the resident directed graph for the recursion on the host (without them it builds its own)
+struct csr_forward { mpfmt_csr_host host; mpfmt_csr_view view; const mpfmt_csr_view* ptr = nullptr; };
+
+static void csr_forward_view(mpfmt_ctx* ctx, csr_forward& f)
+{
+    if (mpfmt_csc_transpose_device(ctx, &f.host) != MPFMT_OK) return;
+    f.view = {f.host.rowptr.data(), f.host.colidx.data(), f.host.centry.data()};
+    f.ptr = &f.view;
+}
+
+// the directed recursion on the host over the column graph and its transposed view: the k-nearest graph (fmt.jl:43-101 with
+// nearF = mutualknnF, nearB = knnB: the mutual bits restrict the forward sets), the double integrator and the Dubins car (the segment
+// counts of the sweep).  A steering plan counts the transposition into ms_host_loop, the k-nearest one does not.
+static int32_t plan_solve_directed(plan_call& c)
+{
+    mpfmt_ctx* ctx = c.ctx;
+    const int d = ctx->d;
+    int32_t rc;
+    host_graph g;
+    if ((rc = graph_to_host(ctx, c.steer(), g))) return rc;
+    std::vector<uint64_t> mutual;
+    csr_forward fwd;
+    if (c.steer()) c.t[4] = now();
+    else {
+        const size_t words = (size_t)(ctx->nnz + 63) / 64;
+        mutual.assign(std::max<size_t>(words, 1), 0);
+        if (words > 0) HIPCHK(ctx, hipMemcpy(mutual.data(), ctx->knn_mutual, sizeof(uint64_t) * words, hipMemcpyDeviceToHost));
+        if ((rc = plan_states(c))) return rc;
+    }
+    csr_forward_view(ctx, fwd);
+    if (!c.steer()) c.t[4] = now();
+    auto goal_hit = [&](int64_t z) { return mpfmt_is_goal_pt(&c.X[(size_t)z * d], c.gd(), c.goal_kind, c.goal_params); };
+    mpfmt_directed_fmt_recursion(ctx->N, g.colptr.data(), g.rowval.data(), g.nzval.data(), g.efree.data(), c.steer() ? g.nseg.data() : nullptr,
+                                 c.checkpts ? c.F.data() : nullptr, c.init_idx, goal_hit, c.A, c.C, c.path, c.res, fwd.ptr,
+                                 c.steer() ? nullptr : mutual.data());
+    c.t[5] = now();
+    return MPFMT_OK;
+}
+
+// the recursion on the device over the resident steering graph (kernels_wavefront.hip, directed form; the Reeds-Shepp graph is
+// structurally symmetric, so its rows are its columns and the same form applies): the transpose (forward sets) on the device, then
+// cost-band batches; MPFMT_WF_SINGLE reproduces the host recursion's pop order exactly
+static int32_t plan_solve_wavefront(plan_call& c)
+{
+    mpfmt_ctx* ctx = c.ctx;
+    int32_t rc;
+    c.t[4] = c.t[3];
+    if ((rc = mpfmt_wf_begin_directed(ctx, c.init_idx, c.checkpts, c.F.data(), c.goal_kind, c.goal_params, c.s.dw, c.band, c.wf_flags))) return rc;
+    if ((rc = mpfmt_wf_run(ctx))) return rc;
+    if ((rc = mpfmt_wf_finish(ctx, c.A, c.C, c.path, c.res))) return rc;
+    c.t[5] = now();
+    return MPFMT_OK;
+}
+
+// PRM*: the cost-to-come field from init_idx over the resident graph and mask (kernels_sssp.hip), the goal pick and the walk back
+static int32_t plan_solve_field(plan_call& c)
+{
+    mpfmt_ctx* ctx = c.ctx;
+    int32_t rc;
+    if ((rc = c.steer() ? sssp_ready(ctx) : sssp_ready_euclid(ctx))) return rc;
+    if (c.steer() && c.checkpts) {                                       // (the Euclidean bitmap is on the device already)
+        if ((rc = ctx->sssp_F.ensure(ctx, sizeof(uint64_t) * c.F.size()))) return rc;
+        if ((rc = steer_upload_bitmap(ctx, c.F))) return rc;
+    }
+    c.t[4] = now();
+    mpfmt_sssp_info inf;
+    if ((rc = mpfmt_sssp_device(ctx, c.init_idx - 1, c.checkpts ? ctx->sssp_F.get() : nullptr, c.C, c.A, &inf))) return rc;
+    if (!c.steer() && (rc = plan_states(c))) return rc;
+    const int64_t z = mpfmt_goal_pick(ctx->N, ctx->d, c.gd(), c.X.data(), c.C, c.goal_kind, c.goal_params);
+    mpfmt_walk_back(ctx->N, c.C, c.A, c.init_idx, z, c.path, c.res);
+    c.t[5] = now();
+    return MPFMT_OK;
+}
+
+// the timing fields and, for the wavefront form, its counters
+static void plan_finish(plan_call& c)
+{
+    fmt_times(c.ctx, c.res, c.t);
+    if (c.flags & PLAN_WAVEFRONT) mpfmt_wf_info_now(c.ctx, c.info);
+}
+
+static int32_t plan_run(plan_call& c, plan_policy policy, int32_t (*solve)(plan_call&))
+{
+    int32_t rc;
+    if ((rc = plan_check(c)) || (rc = plan_points(c)) || (rc = plan_graph(c, policy)) || (rc = solve(c))) return rc;
+    plan_finish(c);
+    return MPFMT_OK;
+}
+
+// fmtstar! over the r-disc graph, the recursion on the host.  A filled graph of the same samples and radius (a previous plan, or
+// mpfmt_graph_import) is reused: only the obstacle-dependent sweep is redone.
+int32_t mpfmt_fmtstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                      int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{
+    plan_call c{ctx, PLAN_R, 0, r, 0, MPFMT_STEER_DI, 0.0, 0.0, init_idx, checkpts, goal_kind, goal_params, A, C, path, res};
+    return plan_run(c, PLAN_RESWEEP, plan_solve_symmetric);
+}
+
+// ... with connections = :K (a resident k-nearest graph of the same samples and the same effective k is reused)
+int32_t mpfmt_knn_fmtstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                          int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{
+    plan_call c{ctx, PLAN_K, 0, 0.0, k, MPFMT_STEER_DI, 0.0, 0.0, init_idx, checkpts, goal_kind, goal_params, A, C, path, res};
+    return plan_run(c, PLAN_RESWEEP, plan_solve_directed);
+}
+
+// PRM*: graph and mask (both reused while resident and valid), the field from init_idx, the best goal sample
+int32_t mpfmt_prmstar(mpfmt_ctx* ctx, double r, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                      int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{
+    plan_call c{ctx, PLAN_R, PLAN_PRM, r, 0, MPFMT_STEER_DI, 0.0, 0.0, init_idx, checkpts, goal_kind, goal_params, A, C, path, res};
+    return plan_run(c, PLAN_RESIDENT, plan_solve_field);
+}
+
+int32_t mpfmt_knn_prmstar(mpfmt_ctx* ctx, int64_t k, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
+                          int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
+{
+    plan_call c{ctx, PLAN_K, PLAN_PRM | PLAN_K_FIRST, 0.0, k, MPFMT_STEER_DI, 0.0, 0.0, init_idx, checkpts, goal_kind, goal_params, A, C, path, res};
+    return plan_run(c, PLAN_RESIDENT, plan_solve_field);
+}
+
 // fmtstar! in a steering space with the recursion on the host; the graph and its edge bits are built anew for every plan
 static int32_t steer_fmtstar(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b, double r, int64_t init_idx, int32_t checkpts,
                              int32_t goal_kind, const double* goal_params, int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
 {
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!A || !C || !path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
-    memset(res, 0, sizeof *res);
-    res->cost = INFINITY;
-    const steer_space s = steer_space_of(ctx, kind);
-    std::vector<double> X;
-    std::vector<uint64_t> F;
-    int32_t rc;
-    stamp t[6];
-    t[0] = now();
-    if ((rc = steer_prelude(ctx, s, a, r, init_idx, goal_kind, X, F))) return rc;
-    t[1] = now();
-    if ((rc = steer_build(ctx, kind, a, b, r))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    t[2] = now();
-    if ((rc = steer_sweep(ctx, kind))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    t[3] = now();
-    host_graph g;
-    if ((rc = graph_to_host(ctx, true, g))) return rc;
-    t[4] = now();
-    const int64_t N = ctx->N;
-    const uint64_t* Fc = checkpts ? F.data() : nullptr;
-    if (s.symmetric) {
-        // the symmetric recursion on column = inball; workspace goals act on the workspace coordinates, POINT on the whole state
-        if ((rc = mpfmt_host_fmt_recursion_impl(N, s.d, X.data(), g.colptr.data(), g.rowval.data(), g.nzval.data(), g.efree.data(), Fc,
-                                                nullptr, nullptr, init_idx, goal_kind, goal_params,
-                                                goal_kind == MPFMT_GOAL_POINT ? s.d : s.dw, g.nseg.data(), A, C, path, res)))
-            return mpfmt_fail(ctx, rc, "host recursion rejected its arguments");
-    } else {
-        auto goal_hit = [&](int64_t z) {
-            const double* v = &X[(size_t)z * s.d];
-            if (goal_kind == MPFMT_GOAL_POINT) {                      // StateGoal: exact state equality (goals.jl:128-131)
-                for (int q = 0; q < s.d; ++q) if (!(v[q] == goal_params[q])) return false;
-                return true;
-            }
-            return mpfmt_is_goal_pt(v, s.dw, goal_kind, goal_params);  // workspace goals act on C*v = the first dw coordinates
-        };
-        mpfmt_csr_host csr;
-        mpfmt_csr_view csr_view;
-        const mpfmt_csr_view* pre_ptr = nullptr;
-        if (mpfmt_csc_transpose_device(ctx, &csr) == MPFMT_OK) { csr_view = {csr.rowptr.data(), csr.colidx.data(), csr.centry.data()}; pre_ptr = &csr_view; }
-        mpfmt_directed_fmt_recursion(N, g.colptr.data(), g.rowval.data(), g.nzval.data(), g.efree.data(), g.nseg.data(), Fc,
-                                     init_idx, goal_hit, A, C, path, res, pre_ptr);
-    }
-    t[5] = now();
-    fmt_times(ctx, res, t);
-    return MPFMT_OK;
+    plan_call c{ctx, PLAN_STEER, 0, r, 0, kind, a, b, init_idx, checkpts, goal_kind, goal_params, A, C, path, res};
+    return plan_run(c, PLAN_REBUILD, steer_symmetric(kind) ? plan_solve_symmetric : plan_solve_directed);
 }
 
-// fmtstar! in a steering space with the recursion on the device (kernels_wavefront.hip, directed form; the Reeds-Shepp graph is
-// structurally symmetric, so its rows are its columns and the same form applies): graph, waypoint sweep and the transpose (forward
-// sets) on the device, then cost-band batches; `single` reproduces the host recursion's pop order exactly.  A resident graph of
-// the same space and parameters -- (rho, r) for the double integrator; kind, turning radius, speed and r for the cars -- is reused, and
-// its sweep too while it is valid: it stays valid across mpfmt_boxes_add / mpfmt_boxes_remove, which bring the mask and the segment
-// counts up to date in place (steer_delta.h), and goes with mpfmt_upload_boxes, new bounds or new samples.
+// ... with the recursion on the device.  A resident graph of the same space and parameters -- (rho, r) for the double integrator; kind,
+// turning radius, speed and r for the cars -- is reused, and its sweep too while it is valid: it stays valid across mpfmt_boxes_add /
+// mpfmt_boxes_remove, which bring the mask and the segment counts up to date in place (steer_delta.h), and goes with mpfmt_upload_boxes,
+// new bounds or new samples.
 static int32_t steer_fmtstar_wavefront(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b, double r, int64_t init_idx, int32_t checkpts,
                                        int32_t goal_kind, const double* goal_params, double band, int32_t flags, int64_t* A, double* C,
                                        int64_t* path, mpfmt_fmt_result* res, mpfmt_wf_info* info)
 {
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
-    const steer_space s = steer_space_of(ctx, kind);
-    std::vector<double> X;
-    std::vector<uint64_t> F;
-    int32_t rc;
-    stamp t[6];
-    t[0] = now();
-    if ((rc = steer_prelude(ctx, s, a, r, init_idx, goal_kind, X, F))) return rc;
-    t[1] = now();
-    const bool resident = ctx->steer_filled && ctx->steer_kind == kind && ctx->steer_r == r &&
-                          (kind == MPFMT_STEER_DI ? ctx->di_rho == a : (ctx->car_rt == a && ctx->car_sp == b));
-    if (!resident && (rc = steer_build(ctx, kind, a, b, r))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    t[2] = now();
-    if (!ctx->steer_swept && (rc = steer_sweep(ctx, kind))) return rc;       // (a graph just built is not swept yet)
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    t[3] = t[4] = now();
-    if ((rc = mpfmt_wf_begin_directed(ctx, init_idx, checkpts, F.data(), goal_kind, goal_params, s.dw, band, flags))) return rc;
-    if ((rc = mpfmt_wf_run(ctx))) return rc;
-    if ((rc = mpfmt_wf_finish(ctx, A, C, path, res))) return rc;
-    t[5] = now();
-    fmt_times(ctx, res, t);
-    mpfmt_wf_info_now(ctx, info);
-    return MPFMT_OK;
+    plan_call c{ctx, PLAN_STEER, PLAN_WAVEFRONT, r, 0, kind, a, b, init_idx, checkpts, goal_kind, goal_params, A, C, path, res, band, flags, info};
+    return plan_run(c, PLAN_RESIDENT, plan_solve_wavefront);
 }
 
-// PRM* in a steering space: the prelude, the graph and the sweep exactly as steer_fmtstar_wavefront takes them (a resident graph of the
-// same space and parameters is reused, and its sweep while it is valid), then the cost-to-come field from init_idx over the resident
-// graph (kernels_sssp.hip) and the goal extraction of prmstar_impl with the goal predicate of steer_fmtstar.
+// PRM* in a steering space: graph and sweep as steer_fmtstar_wavefront takes them, then the field over the resident graph
 static int32_t steer_prmstar(mpfmt_ctx* ctx, mpfmt_steer kind, double a, double b, double r, int64_t init_idx, int32_t checkpts,
                              int32_t goal_kind, const double* goal_params, int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res)
 {
-    if (!ctx) return MPFMT_ERR_ARG;
-    if (!A || !C || !path || !res || !goal_params) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL output / goal pointer");
-    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "prmstar runs on an unsharded ctx");
-    memset(res, 0, sizeof *res);
-    res->cost = INFINITY;
-    const steer_space s = steer_space_of(ctx, kind);
-    std::vector<double> X;
-    std::vector<uint64_t> F;
-    int32_t rc;
-    stamp t[6];
-    t[0] = now();
-    if ((rc = steer_prelude(ctx, s, a, r, init_idx, goal_kind, X, F))) return rc;
-    t[1] = now();
-    const bool resident = ctx->steer_filled && ctx->steer_kind == kind && ctx->steer_r == r &&
-                          (kind == MPFMT_STEER_DI ? ctx->di_rho == a : (ctx->car_rt == a && ctx->car_sp == b));
-    if (!resident && (rc = steer_build(ctx, kind, a, b, r))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    t[2] = now();
-    if (!ctx->steer_swept && (rc = steer_sweep(ctx, kind))) return rc;       // (a graph just built is not swept yet)
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    t[3] = now();
-    if ((rc = sssp_ready(ctx))) return rc;
-    if (checkpts) {
-        if ((rc = ctx->sssp_F.ensure(ctx, sizeof(uint64_t) * F.size()))) return rc;
-        if ((rc = steer_upload_bitmap(ctx, F))) return rc;
-    }
-    t[4] = now();
-    const int64_t N = ctx->N;
-    mpfmt_sssp_info inf;
-    if ((rc = mpfmt_sssp_device(ctx, init_idx - 1, checkpts ? ctx->sssp_F.get() : nullptr, C, A, &inf))) return rc;
-    auto goal_hit = [&](int64_t z) {
-        const double* v = &X[(size_t)z * s.d];
-        if (goal_kind == MPFMT_GOAL_POINT) {                          // StateGoal: exact state equality (goals.jl:128-131)
-            for (int q = 0; q < s.d; ++q) if (!(v[q] == goal_params[q])) return false;
-            return true;
-        }
-        return mpfmt_is_goal_pt(v, s.dw, goal_kind, goal_params);      // workspace goals act on the first dw coordinates
-    };
-    // goal node: the reached sample inside the goal region of lowest (C, index)
-    int64_t z = -1;
-    for (int64_t i = 0; i < N; ++i)
-        if (C[i] < INFINITY && (z < 0 || C[i] < C[z]) && goal_hit(i)) z = i;
-    mpfmt_walk_back(N, C, A, init_idx, z, path, res);
-    t[5] = now();
-    fmt_times(ctx, res, t);
-    return MPFMT_OK;
+    plan_call c{ctx, PLAN_STEER, PLAN_PRM, r, 0, kind, a, b, init_idx, checkpts, goal_kind, goal_params, A, C, path, res};
+    return plan_run(c, PLAN_RESIDENT, plan_solve_field);
 }
 
 int32_t mpfmt_di_prmstar(mpfmt_ctx* ctx, double rho, double r, int64_t init_idx, int32_t checkpts, int32_t goal_kind, const double* goal_params,
@@ -2441,12 +2440,7 @@ static int32_t steer_graph_count(mpfmt_ctx* ctx, mpfmt_steer kind, double a, dou
         HIPCHK(ctx, hipSetDevice(ctx->device));
         if ((rc = mpfmt_di_count(ctx, a, r))) return rc;
     } else if ((rc = mpfmt_car_build(ctx, kind, a, b, r))) return rc;
-    const int64_t n1 = ctx->N + 1;
-    void* scr;
-    if ((rc = mpfmt_scratch(ctx, sizeof(int64_t) * n1, &scr))) return rc;
-    hipLaunchKernelGGL(k_add1_i64, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, ctx->stream, ctx->colptr, n1, (int64_t*)scr);
-    HIPCHK(ctx, hipMemcpyAsync(colptr, scr, sizeof(int64_t) * n1, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = colptr_to_host(ctx, colptr))) return rc;
     *nnz = ctx->nnz;
     return MPFMT_OK;
 }

@@ -279,6 +279,17 @@ void mpfmt_directed_fmt_recursion(int64_t N, const int64_t* colptr_, const int32
     res->cost = C[z]; res->z = z + 1; res->collision_checks = count; res->path_len = (int64_t)rev.size(); res->nnz = nnz;
 }
 
+// The goal node of the roadmap planners over a finished field C (+Inf = unreached): the reached sample inside the goal region of lowest
+// (C, index), 0-based, or -1.  X holds N states of d coordinates; the goal reads the first gd of them (d in a Euclidean space; in a steering
+// space the workspace coordinates, and the whole state for a POINT goal: StateGoal is exact state equality, goals.jl:128-131).
+int64_t mpfmt_goal_pick(int64_t N, int d, int gd, const double* X, const double* C, int goal_kind, const double* goal_params)
+{
+    int64_t z = -1;
+    for (int64_t i = 0; i < N; ++i)
+        if (C[i] < INFINITY && (z < 0 || C[i] < C[z]) && mpfmt_is_goal_pt(&X[(size_t)i * d], gd, goal_kind, goal_params)) z = i;
+    return z;
+}
+
 // The goal walk of the roadmap planners over a finished field: labels C, parents A (1-based, 0 = none), the source init_idx (1-based)
 // and the goal node z the caller picked (0-based; -1: no reached sample is a goal).  path = init_idx ... z + 1 by the parents, or
 // [init_idx] without a goal node.  A walk stops at the source, at a parent of 0, and after N hops whatever A holds: path has N slots.

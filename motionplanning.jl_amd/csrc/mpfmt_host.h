@@ -21,6 +21,9 @@ void mpfmt_directed_fmt_recursion(int64_t N, const int64_t* colptr, const int32_
                                   const uint8_t* nseg, const uint64_t* F, int64_t init_idx, const std::function<bool(int64_t)>& goal_hit,
                                   int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res, const mpfmt_csr_view* pre,
                                   const uint64_t* fwd_mask = nullptr);
+// the goal node of the roadmap planners: the reached (C < +Inf) sample of lowest (C, index) whose first gd of d coordinates lie in the goal
+// region, 0-based, or -1
+int64_t mpfmt_goal_pick(int64_t N, int d, int gd, const double* X, const double* C, int goal_kind, const double* goal_params);
 // the goal walk of the roadmap planners: path and status / cost / z / path_len / collision_checks of res from a finished field and the
 // chosen goal node z (0-based, -1 = none)
 void mpfmt_walk_back(int64_t N, const double* C, const int64_t* A, int64_t init_idx, int64_t z, int64_t* path, mpfmt_fmt_result* res);

@@ -489,6 +489,8 @@ struct mpfmt_ctx {
     } while (0)
 
 int32_t mpfmt_scratch(mpfmt_ctx* ctx, size_t bytes, void** out);
+// the filled r-disc graph of radius r is resident (the k-nearest graph shares its slots and is never "a graph of radius graph_r")
+inline bool euclid_resident(const mpfmt_ctx* ctx, double r) { return ctx->graph_filled && ctx->graph_r == r && !ctx->knn_k; }
 // a ctx without the counter arena: the pair counters / the logs' overflow flag as allocations of their own, made once
 inline int32_t mpfmt_own_pairs(mpfmt_ctx* ctx)
 {

@@ -3,6 +3,7 @@
 // (the same translation unit the library ships).  Reads a graph written by the test (the oracle's), runs the symmetric and the
 // directed recursion and the CSC validation on good and malformed inputs, writes the trees back for comparison.
 #include "../../motionplanning.jl_amd/csrc/mpfmt_host.h"
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,9 +17,45 @@ template <class T> static std::vector<T> rd(FILE* f, size_t n)
     return v;
 }
 
+// mpfmt_goal_pick on hand-written fields: five states of d = 3 (a steering space: workspace (x, y), then theta), goals that read gd of them
+static int goal_pick_cases()
+{
+    const double inf = INFINITY;
+    const double X[5 * 3] = {0.1, 0.1, 0.0,   0.5, 0.5, 1.0,   0.5, 0.5, 2.0,   0.52, 0.5, 3.0,   0.9, 0.9, 0.5};
+    const double rect[4] = {0.4, 0.4, 0.6, 0.6}, ball[3] = {0.5, 0.5, 0.05}, pt[3] = {0.5, 0.5, 2.0}, away[3] = {2.0, 2.0, 0.1};
+    int bad = 0;
+    auto pick = [&](const double* C, int gd, int kind, const double* g) { return mpfmt_goal_pick(5, 3, gd, X, C, kind, g); };
+    // no reached sample in the goal: nothing reached there, a goal nobody is in, nothing reached at all, no samples
+    const double c0[5] = {0.0, inf, inf, inf, 1.0}, none[5] = {inf, inf, inf, inf, inf};
+    if (pick(c0, 2, MPFMT_GOAL_RECT, rect) != -1) bad |= 1;
+    if (pick(c0, 2, MPFMT_GOAL_BALL, away) != -1) bad |= 1;
+    if (pick(none, 2, MPFMT_GOAL_RECT, rect) != -1) bad |= 1;
+    if (mpfmt_goal_pick(0, 3, 2, X, c0, MPFMT_GOAL_RECT, rect) != -1) bad |= 1;
+    // two goal samples at equal C: the lower index; a cheaper one later wins, an equal one later does not
+    const double c1[5] = {0.0, 2.0, 2.0, 2.0, 0.5}, c2[5] = {0.0, 2.0, 1.5, 2.0, 0.5}, c3[5] = {0.0, 2.0, 3.0, 2.0, 0.5};
+    if (pick(c1, 2, MPFMT_GOAL_RECT, rect) != 1) bad |= 2;
+    if (pick(c2, 2, MPFMT_GOAL_RECT, rect) != 2) bad |= 2;
+    if (pick(c3, 2, MPFMT_GOAL_BALL, ball) != 1) bad |= 2;
+    // POINT reads the whole state (gd = d): samples 2 and 3 share (x, y) and differ in theta; RECT / BALL with gd = 2 < d take both, and
+    // a POINT goal cut to the workspace (gd = 2) would as well
+    if (pick(c1, 3, MPFMT_GOAL_POINT, pt) != 2) bad |= 4;
+    if (pick(c1, 2, MPFMT_GOAL_POINT, pt) != 1) bad |= 4;
+    if (pick(c1, 2, MPFMT_GOAL_BALL, ball) != 1) bad |= 4;
+    if (pick(c3, 3, MPFMT_GOAL_POINT, pt) != 2) bad |= 4;
+    // an unreached (+Inf) sample inside the goal is ignored, wherever it stands
+    const double c4[5] = {0.0, inf, 4.0, 3.0, 0.5}, c5[5] = {0.0, 4.0, inf, inf, 0.5};
+    if (pick(c4, 2, MPFMT_GOAL_RECT, rect) != 3) bad |= 8;
+    if (pick(c4, 2, MPFMT_GOAL_BALL, ball) != 3) bad |= 8;
+    if (pick(c5, 2, MPFMT_GOAL_RECT, rect) != 1) bad |= 8;
+    if (pick(c5, 3, MPFMT_GOAL_POINT, pt) != -1) bad |= 8;
+    if (bad) fprintf(stderr, "goal_pick: case mask %d\n", bad);
+    return bad;
+}
+
 int main(int argc, char** argv)
 {
     if (argc != 3) return 2;
+    if (goal_pick_cases()) return 8;
     FILE* f = fopen(argv[1], "rb");
     if (!f) return 2;
     int64_t hdr[4];
