@@ -903,6 +903,18 @@ MPFMT_API int32_t mpfmt_di_graph_device_ptrs(mpfmt_ctx* ctx, void** colptr, void
 MPFMT_API int32_t mpfmt_di_fmtstar(mpfmt_ctx* ctx, double rho, double r, int64_t init_idx, int32_t checkpts,
                          int32_t goal_kind, const double* goal_params,
                          int64_t* A, double* C, int64_t* path, mpfmt_fmt_result* res);
+/* DIAGNOSTIC, for tests of the matrix-core candidate test of the double-integrator build (option "di_path"); no planner needs it.
+ * On the resident samples (64 <= N <= 1024, state dimension 2 or 4) it computes the threshold and builds the fp16 operands exactly as
+ * the build does, forms the fragments and the matrix-core instructions of the pair kernel through the kernel's own helpers, and
+ * returns every accumulator: acc float[npad][npad], row = target, column = source, npad = N rounded up to 64 (rows / columns >= N are
+ * pad states), entry = Q(source -> target) - T as the matrix core delivered it (the pair kernel keeps a pair when its entry is
+ * negative).  opsT / opsS: uint16[npad][16], the fp16 bit patterns of the target- and source-role operands.  terms:
+ * double[MPFMT_DI_MF_PROBE_TERMS] = sp, sv, pc[0], pc[1], split term, accumulation term, E, T, negT, usable (0 / 1), Pm, Vm, F, G, N0,
+ * guards (bit 0 arguments, 1 finite box, 2 fp16 range, 3 E small against 1 / rho) -- written even when the call then fails with
+ * MPFMT_ERR_ARG because the prefilter does not apply.  A resident steering graph is dropped (the operand buffer is rewritten). */
+#define MPFMT_DI_MF_PROBE_TERMS 16
+MPFMT_API int32_t mpfmt_di_mf_probe(mpfmt_ctx* ctx, double rho, double r, float* acc, uint16_t* opsT, uint16_t* opsS, double* terms,
+                                    int64_t* npad);
 
 
 /* ---- device-resident forms (bench / multi-GPU: no PCIe in the timed region) -----------------------

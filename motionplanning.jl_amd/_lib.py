@@ -77,6 +77,7 @@ class DiscInfo(C.Structure):
 
 
 SHORTCUT_DONE, SHORTCUT_TRUNCATED, SHORTCUT_STUCK = 0, 1, 2
+DI_MF_PROBE_TERMS = 16                # MPFMT_DI_MF_PROBE_TERMS
 SPACE_EUCLID, SPACE_DI, SPACE_DUBINS, SPACE_REEDSSHEPP = 0, 1, 2, 3
 DISC_DT, DISC_N = 0, 1
 ROADMAP_SOLVED, ROADMAP_NO_PATH, ROADMAP_START_BLOCKED, ROADMAP_GOAL_BLOCKED = 0, 1, 2, 3
@@ -199,6 +200,7 @@ SYMBOLS = [
     ("mpfmt_di_graph_step_device", C.c_int32, [C.c_void_p, C.c_double, C.c_double, c_i64_p]),
     ("mpfmt_di_graph_device_ptrs", C.c_int32, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6),
     ("mpfmt_di_steer", C.c_int32, [C.c_void_p, c_d_p, c_d_p, C.c_int64, C.c_int32, C.c_double, C.c_double, c_d_p, c_d_p]),
+    ("mpfmt_di_mf_probe", C.c_int32, [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), c_d_p, c_i64_p]),
     ("mpfmt_di_fmtstar", C.c_int32, [C.c_void_p, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32, c_d_p,
                                      c_i64_p, c_d_p, c_i64_p, C.POINTER(FmtResult)]),
     ("mpfmt_dubins_fmtstar_wavefront", C.c_int32, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32, c_d_p,
@@ -1365,6 +1367,24 @@ class Context:
         cost = np.empty(max(n, 1)); t = np.empty(max(n, 1))
         self._chk(self._L.mpfmt_di_steer(self._h, _dp(X0), _dp(X1), n, ns // 2, float(rho), float(r), _dp(cost), _dp(t)))
         return cost[:n], t[:n]
+
+    def di_mf_probe(self, rho, r):
+        """DIAGNOSTIC (mpfmt_di_mf_probe, tests only): what the matrix-core candidate test of the double-integrator build computes on the
+        resident samples (64 <= N <= 1024).  Returns a dict: `acc` float32 [npad, npad] (row = target, column = source: Q - T as the
+        matrix core delivered it), `opsT` / `opsS` float16 [npad, 16] (the operands of the target / source role) and the threshold's
+        terms sp, sv, pc, split, accum, E, T, negT, usable, Pm, Vm, F, G, N0, guards.  Drops a resident steering graph."""
+        npad = ((self.N + 63) // 64) * 64 if 64 <= self.N <= 1024 else 64          # (outside that range the library refuses before it writes)
+        acc = np.zeros((npad, npad), np.float32); oT = np.zeros((npad, 16), np.uint16); oS = np.zeros((npad, 16), np.uint16)
+        terms = np.zeros(DI_MF_PROBE_TERMS); n = C.c_int64()
+        rc = self._L.mpfmt_di_mf_probe(self._h, float(rho), float(r), acc.ctypes.data_as(C.POINTER(C.c_float)),
+                                       oT.ctypes.data_as(C.POINTER(C.c_uint16)), oS.ctypes.data_as(C.POINTER(C.c_uint16)), _dp(terms), C.byref(n))
+        out = dict(zip(("sp", "sv", "pc0", "pc1", "split", "accum", "E", "T", "negT", "usable", "Pm", "Vm", "F", "G", "N0", "guards"), terms.tolist()))
+        out["pc"] = np.array([out.pop("pc0"), out.pop("pc1")]); out["usable"] = bool(out["usable"]); out["guards"] = int(out["guards"])
+        out["negT"] = np.float32(out["negT"])
+        self._chk(rc)
+        assert n.value == npad
+        out.update(acc=acc, opsT=oT.view(np.float16), opsS=oS.view(np.float16), npad=npad)
+        return out
 
     def di_fmtstar(self, rho, r, goal_kind, goal_params, init_idx=1, checkpts=True):
         return self._steer_plan("di", "fmtstar", (rho, r), goal_kind, goal_params, init_idx, checkpts)

@@ -21,6 +21,7 @@
 // The graph is the same entry for entry: the filter and both multiply-only tests only ever drop pairs the exact tests would drop.
 #include "mpfmt_internal.h"
 #include "di_steer.h"
+#include "di_mf_bound.h"
 #include <algorithm>
 #include <cmath>
 
@@ -81,6 +82,41 @@ __global__ void k_di_make_ops(const double* __restrict__ X, int64_t N, int64_t n
     opsS[s * 2] = S.v[0]; opsS[s * 2 + 1] = S.v[1];
 }
 
+// ---- fragment and accumulator layout: shared by k_di_pairs_mf and the diagnostic k_di_mf_probe, so that the probe tests no copy ----
+// A fragment of lane (kb = lane >> 5, col = lane & 31) for the 32-row half rb of a tile: target row rb * 32 + col, slots 8 kb .. 8 kb + 7
+__device__ __forceinline__ half8 dimf_load_a(const uint4* opsT, int64_t tile, int rb, int col, int kb)
+{
+    union { uint4 u; half8 h; } cv;
+    cv.u = opsT[(tile * 64 + rb * 32 + col) * 2 + kb];
+    return cv.h;
+}
+// B fragments of a 64-source chunk c through a buffer descriptor over opsS (per-lane offset fixed, chunk offset scalar):
+// bq[h] = source row c * 64 + h * 32 + col, slots 8 kb .. 8 kb + 7
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t dimf_b_rsrc(const uint4* opsS, int64_t npad)
+{ return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(opsS), 0, (int)(npad * 32), 0x00020000); }
+// (the lane's byte offset and the accumulator decode below are macros, not functions: a function is optimised on its own before it is
+// inlined, without the ranges of lane and bit position the kernel knows, and k_di_pairs_mf then compiles to other code than it did)
+#define DIMF_B_VOFF(col, kb) ((col) * 32 + (kb) * 16)
+__device__ __forceinline__ void dimf_load_b(__amdgpu_buffer_rsrc_t rsrc, int voff, int64_t c, u32x4 (&bq)[2])
+{
+    bq[0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, (int)(c * 2048), 0);
+    bq[1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + 1024, (int)(c * 2048), 0);
+}
+// the four 32 x 32 blocks of a 64 x 64 tile-chunk pair: block t = (source half) * 2 + (target half), every accumulator starting at cinit
+__device__ __forceinline__ void dimf_mfma4(const half8 (&aF)[2], const u32x4 (&bq)[2], const f32x16& cinit, f32x16 (&acc)[4])
+{
+    union { u32x4 u; half8 h; } bf0, bf1;
+    bf0.u = bq[0]; bf1.u = bq[1];
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aF[0], bf0.h, cinit, 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aF[1], bf0.h, cinit, 0, 0, 0);
+    acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aF[0], bf1.h, cinit, 0, 0, 0);
+    acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aF[1], bf1.h, cinit, 0, 0, 0);
+}
+// accumulator register r of block t in lane fl  ->  target lane tl of the tile (0 .. 63), source sl of the chunk (0 .. 63)
+#define DIMF_ACC_ROW(r, fl) (((r) & 3) + 8 * ((r) >> 2) + 4 * ((fl) >> 5))
+#define DIMF_ACC_SRC(t, fl) (((t) >> 1) * 32 + ((fl) & 31))
+#define DIMF_ACC_TGT(t, row) (((t) & 1) * 32 + (row))
+
 // ---- the kernel -----------------------------------------------------------------------------------------------------------
 // MODE 0: count   1: fill the staging CSC from the counts   2: count AND keep the accepted hits in slot lists (single pass)
 template <int M, int MODE>
@@ -122,11 +158,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // A fragments: target rows rb * 32 + col, slots 8 kb .. 8 kb + 7
     half8 aF[2];
 #pragma unroll
-    for (int rb = 0; rb < 2; ++rb) {
-        union { uint4 u; half8 h; } cv;
-        cv.u = g.opsT[(tile * 64 + rb * 32 + col) * 2 + kb];
-        aF[rb] = cv.h;
-    }
+    for (int rb = 0; rb < 2; ++rb) aF[rb] = dimf_load_a(g.opsT, tile, rb, col, kb);
     f32x16 cinit;
 #pragma unroll
     for (int k = 0; k < 16; ++k) cinit[k] = g.negT;
@@ -190,9 +222,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             const int bpos = (int)(e & 63u), fl = (int)((e >> 6) & 63u);
             const int64_t qc = (int64_t)(e >> 12);
             const int t = bpos >> 4, r = 15 - (bpos & 15);
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * (fl >> 5);
-            i = qc * 64 + (int64_t)((t >> 1) * 32 + (fl & 31));
-            tl = (t & 1) * 32 + row;
+            const int row = DIMF_ACC_ROW(r, fl);
+            i = qc * 64 + (int64_t)DIMF_ACC_SRC(t, fl);
+            tl = DIMF_ACC_TGT(t, row);
             const int64_t jj = tile * 64 + tl;
             if (i < a.N && jj < a.N && i != jj) {
                 double ca = 0.0, cb = 0.0, cc = 0.0;
@@ -267,28 +299,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     };
 
     // ---- main loop over the slice's source chunks: B fragments through a buffer descriptor (per-lane offset fixed, chunk offset scalar) ----
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(g.opsS), 0, (int)(g.npad * 32), 0x00020000);
-    const int voff = col * 32 + kb * 16;
-    auto load_b = [&](int64_t c, u32x4 (&bq)[2]) {
-        bq[0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, (int)(c * 2048), 0);
-        bq[1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + 1024, (int)(c * 2048), 0);
-    };
+    const __amdgpu_buffer_rsrc_t rsrc = dimf_b_rsrc(g.opsS, g.npad);
+    const int voff = DIMF_B_VOFF(col, kb);
+    auto load_b = [&](int64_t c, u32x4 (&bq)[2]) { dimf_load_b(rsrc, voff, c, bq); };
     auto process = [&](int64_t c, u32x4 (&bq)[2], bool refill, int64_t cn) {
-        union { u32x4 u; half8 h; } bf0, bf1;
-        bf0.u = bq[0]; bf1.u = bq[1];
-        const f32x16 acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(aF[0], bf0.h, cinit, 0, 0, 0);
-        const f32x16 acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(aF[1], bf0.h, cinit, 0, 0, 0);
-        const f32x16 acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(aF[0], bf1.h, cinit, 0, 0, 0);
-        const f32x16 acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(aF[1], bf1.h, cinit, 0, 0, 0);
+        f32x16 acc[4];
+        dimf_mfma4(aF, bq, cinit, acc);
         if (refill) load_b(cn, bq);
         // H: 16 sign bits per 32x32 block t = (source half) * 2 + (target half) at bits [16 t, 16 t + 16); bit (15 - r) <-> accumulator register r
         uint32_t h0 = 0, h1 = 0, h2 = 0, h3 = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            h0 = __builtin_amdgcn_alignbit(h0, __float_as_uint(acc0[r]), 31);
-            h1 = __builtin_amdgcn_alignbit(h1, __float_as_uint(acc1[r]), 31);
-            h2 = __builtin_amdgcn_alignbit(h2, __float_as_uint(acc2[r]), 31);
-            h3 = __builtin_amdgcn_alignbit(h3, __float_as_uint(acc3[r]), 31);
+            h0 = __builtin_amdgcn_alignbit(h0, __float_as_uint(acc[0][r]), 31);
+            h1 = __builtin_amdgcn_alignbit(h1, __float_as_uint(acc[1][r]), 31);
+            h2 = __builtin_amdgcn_alignbit(h2, __float_as_uint(acc[2][r]), 31);
+            h3 = __builtin_amdgcn_alignbit(h3, __float_as_uint(acc[3][r]), 31);
         }
         const unsigned long long H = (unsigned long long)(h0 | (h1 << 16)) | ((unsigned long long)(h2 | (h3 << 16)) << 32);
         const unsigned long long m = __ballot(H != 0);
@@ -325,41 +350,46 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     }
 }
 
+// ---- the diagnostic probe: what the matrix core returns for every pair of the padded set (mpfmt_di_mf_probe) -------------------------
+// one wavefront per (tile of 64 targets, chunk of 64 sources): the fragments and the four MFMAs of k_di_pairs_mf through the same
+// helpers, every accumulator written to acc[target][source] (tile, chunk < npad / 64; tl, sl < 64: inside [npad][npad])
+__global__ __launch_bounds__(64) void k_di_mf_probe(const uint4* __restrict__ opsT, const uint4* __restrict__ opsS, int64_t npad, float negT,
+                                                    float* __restrict__ out)
+{
+    const int lane = threadIdx.x;
+    const int64_t tile = blockIdx.x, c = blockIdx.y;
+    const int kb = lane >> 5, col = lane & 31;
+    half8 aF[2];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) aF[rb] = dimf_load_a(opsT, tile, rb, col, kb);
+    f32x16 cinit;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) cinit[k] = negT;
+    u32x4 bq[2];
+    dimf_load_b(dimf_b_rsrc(opsS, npad), DIMF_B_VOFF(col, kb), c, bq);
+    f32x16 acc[4];
+    dimf_mfma4(aF, bq, cinit, acc);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = DIMF_ACC_ROW(r, lane);
+            const int sl = DIMF_ACC_SRC(t, lane), tl = DIMF_ACC_TGT(t, row);
+            out[(tile * 64 + tl) * npad + c * 64 + sl] = acc[t][r];
+        }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
-// The threshold.  Every slot value x reaches the matrix core as hi + lo with |x - hi - lo| <= 2^-22 |x| + 6.2e-5 (the second term: a
-// remainder below the smallest normal fp16 number, should the core flush subnormal inputs); the products are exact in fp32 and every one
-// of the 17 additions (in whatever order) rounds at 2^-24 of the running magnitude.  With F, G the largest |f|, |g| the samples' box allows:
-//   E = 2M (F dG + G dF + dF dG + 2^-22 F G)      (the three products kept per feature, and the lo x lo product dropped)
-//     + dN0 + dN1 + 17 x 2^-24 (3 x 2M F G + N0 + N1 + 1/rho)
-// times 1.5, plus the slack of the exact test it stands in front of (1e-9 (1 + rho (ta + |tb| + tc))).  *usable = false when E is not
-// small against 1 / rho (a radius far below the samples' extent: the vector-ALU kernel then).
+// The threshold: di_mf_bound.h (plain host arithmetic, held to an independent model by tests/test_di_filter_cpu.py).
 int32_t mpfmt_di_mf_prepare(mpfmt_ctx* ctx, double rho, double r, float* negT, bool* usable, double* sp_out, double* sv_out, double* pc)
 {
     *usable = false;
-    const int m = ctx->d / 2;
-    if (m < 1 || m > 2 || !(r > 0.0) || !(rho > 0.0) || ctx->N < 64 || ctx->N > ((int64_t)1 << 25)) return MPFMT_OK;      // (32-bit operand offsets, 20-bit chunk ids)
-    const double sp = 6.0 / (r * r), sv = 2.0 / r;
-    double Pm = 0.0, Vm = 0.0;
-    for (int i = 0; i < m; ++i) {
-        pc[i] = 0.5 * (ctx->bb_lo[i] + ctx->bb_hi[i]);
-        Pm = std::max(Pm, 0.5 * (ctx->bb_hi[i] - ctx->bb_lo[i]) * sp);
-        Vm = std::max(Vm, std::max(std::fabs(ctx->bb_lo[m + i]), std::fabs(ctx->bb_hi[m + i])) * sv);
-    }
-    if (!std::isfinite(Pm) || !std::isfinite(Vm)) return MPFMT_OK;
-    Pm *= 1.0 + 1e-9; Vm *= 1.0 + 1e-9;
-    const double F = std::max(Pm, Vm), G = std::max(2.0 * (Pm + Vm), 2.0 * Pm + Vm);
-    const double N0 = m * (Pm + Vm) * (Pm + Vm), N1 = N0;
-    if (G > 3.0e4 || N0 > 3.0e4) return MPFMT_OK;            // (fp16 range)
-    const double q = std::ldexp(1.0, -22), tiny = 6.2e-5;
-    const double dF = q * F + tiny, dG = q * G + tiny, dN = q * N0 + tiny;
-    const double S = 3.0 * 2 * m * F * G + N0 + N1 + 1.0 / rho;
-    double E = 2.0 * m * (F * dG + G * dF + dF * dG + q * F * G) + 2.0 * dN + 17.0 * std::ldexp(1.0, -24) * S;
-    E *= 1.5;
-    const double Sq = 4.0 * m * Pm * Pm + 8.0 * m * Pm * Vm + 3.0 * m * Vm * Vm;        // >= ta + |tb| + tc
-    const double T = (1.0 / rho) * (1.0 + 1e-6) + 1e-9 * (1.0 / rho + Sq) + 1e-12 * Sq + E;
-    if (E > 0.05 / rho) return MPFMT_OK;
-    *negT = -(float)(T * (1.0 + 1e-6));
-    *sp_out = sp; *sv_out = sv;
+    if (ctx->d / 2 > 2 || ctx->N < 64 || ctx->N > ((int64_t)1 << 25)) return MPFMT_OK;      // (32-bit operand offsets, 20-bit chunk ids)
+    const di_mf_bound b = di_mf_bound_compute(ctx->d / 2, rho, r, ctx->bb_lo, ctx->bb_hi);
+    if (!b.usable) return MPFMT_OK;
+    pc[0] = b.pc[0]; pc[1] = b.pc[1];
+    *negT = b.negT;
+    *sp_out = b.sp; *sv_out = b.sv;
     *usable = true;
     return MPFMT_OK;
 }
@@ -398,5 +428,43 @@ int32_t mpfmt_di_mf_launch(mpfmt_ctx* ctx, const di_args& a, int mode, float neg
     else return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the matrix-core double-integrator prefilter is built for workspace dim 1, 2");
 #undef LAUNCH
     HIPCHK(ctx, hipGetLastError());
+    return MPFMT_OK;
+}
+
+// Diagnostic (tests): the operands and the threshold exactly as the build makes them, and every accumulator of the matrix core.
+int32_t mpfmt_di_mf_probe(mpfmt_ctx* ctx, double rho, double r, float* acc, uint16_t* opsT, uint16_t* opsS, double* terms, int64_t* npad_out)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (!acc || !opsT || !opsS || !terms || !npad_out) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "NULL array");
+    if (!ctx->Xo) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded");
+    if (ctx->d != 2 && ctx->d != 4) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "the matrix-core prefilter is built for double-integrator states of dimension 2 or 4 (got %d)", ctx->d);
+    if (ctx->N < 64 || ctx->N > 1024) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "the probe takes 64 .. 1024 resident samples (got %lld)", (long long)ctx->N);
+    if (!(rho > 0.0) || !std::isfinite(rho) || !(r > 0.0) || !std::isfinite(r)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "rho and r must be finite and > 0");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const di_mf_bound b = di_mf_bound_compute(ctx->d / 2, rho, r, ctx->bb_lo, ctx->bb_hi);
+    const double tv[MPFMT_DI_MF_PROBE_TERMS] = {b.sp, b.sv, b.pc[0], b.pc[1], b.split, b.accum, b.E, b.T, (double)b.negT, b.usable ? 1.0 : 0.0,
+                                                b.Pm, b.Vm, b.F, b.G, b.N0, (b.args_ok ? 1.0 : 0.0) + (b.finite_ok ? 2.0 : 0.0) + (b.range_ok ? 4.0 : 0.0) + (b.small_ok ? 8.0 : 0.0)};
+    for (int k = 0; k < MPFMT_DI_MF_PROBE_TERMS; ++k) terms[k] = tv[k];
+    float negT = 0.f;
+    bool mf = false;
+    double sp = 0.0, sv = 0.0, pc[2] = {0.0, 0.0};
+    int32_t rc;
+    if ((rc = mpfmt_di_mf_prepare(ctx, rho, r, &negT, &mf, &sp, &sv, pc))) return rc;
+    if (!mf) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "the matrix-core prefilter does not apply here (the fp16 error bound is not small against 1 / rho)");
+    ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;      // (the operand buffer of a counted graph is rewritten)
+    if ((rc = mpfmt_di_mf_build_operands(ctx, sp, sv, pc))) return rc;
+    const int64_t npad = ((ctx->N + 63) / 64) * 64;
+    mpfmt_tmp tmp;
+    float* dacc = nullptr;
+    HIPCHK(ctx, tmp.get(&dacc, sizeof(float) * (size_t)npad * npad));
+    const uint4* dT = (const uint4*)ctx->di_ops.get();
+    const uint4* dS = dT + 2 * npad;
+    hipLaunchKernelGGL(k_di_mf_probe, dim3((unsigned)(npad / 64), (unsigned)(npad / 64)), dim3(64), 0, ctx->stream, dT, dS, npad, negT, dacc);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(acc, dacc, sizeof(float) * (size_t)npad * npad, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(opsT, dT, 32 * (size_t)npad, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(opsS, dS, 32 * (size_t)npad, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *npad_out = npad;
     return MPFMT_OK;
 }
