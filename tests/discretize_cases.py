@@ -14,7 +14,8 @@ B = 70
 
 # name -> (space, d, params)
 SPACES = {"euclid2": (L.SPACE_EUCLID, 2, None), "euclid6": (L.SPACE_EUCLID, 6, None), "di2": (L.SPACE_DI, 4, (1.0, 3.0)),
-          "dubins": (L.SPACE_DUBINS, 3, (0.1, 1.0)), "reedsshepp": (L.SPACE_REEDSSHEPP, 3, (0.1, 1.0))}
+          "dubins": (L.SPACE_DUBINS, 3, (0.1, 1.0)), "reedsshepp": (L.SPACE_REEDSSHEPP, 3, (0.1, 1.0)),
+          "dubins_s": (L.SPACE_DUBINS, 3, (0.1, 0.7)), "reedsshepp_s": (L.SPACE_REEDSSHEPP, 3, (0.1, 0.7))}      # a speed other than 1
 
 
 def random_path(space, d, n, rng, step):

@@ -24,7 +24,10 @@ NQ = 9
 
 
 def params(w):
-    return (sc.RHO, sc.R_DI) if w.kind == "di" else (sc.RT, sc.SP, sc.R_CAR)
+    """(rho, r) or (turning radius, speed, r): those of steer_prm_cases.py unless the world carries its own (w.car = (rt, sp, r))."""
+    if w.kind == "di":
+        return sc.RHO, sc.R_DI
+    return getattr(w, "car", (sc.RT, sc.SP, sc.R_CAR))
 
 
 def radius(w):
@@ -57,9 +60,9 @@ def _car_in_range(X, q, r):
     return np.flatnonzero(dx * dx + dy * dy <= r * r)
 
 
-def oracle_near(orc, w, q, direction, want_bits=True):
+def oracle_near(orc, w, q, direction, want_bits=True, sp=sc.SP):
     """(idx 0-based ascending, weights, free bits) of the external state q over the samples of w: the governing rule evaluated pair by
-    pair with the oracle.  direction 1 = head (y -> q), 0 = tail (q -> y)."""
+    pair with the oracle.  direction 1 = head (y -> q), 0 = tail (q -> y).  sp: the cars' speed."""
     X, lohi = w.X, w.lohi
     q = np.asarray(q, dtype=np.float64)
     idx, wt, bits = [], [], []
@@ -74,7 +77,7 @@ def oracle_near(orc, w, q, direction, want_bits=True):
                 idx.append(y); wt.append(c)
                 bits.append(orc.di_is_free_motion(a, b, rho, r, lohi, w.ss_lo, w.ss_hi) if want_bits else False)
     else:
-        rt, sp, r = params(w)
+        rt, _, r = params(w)
         for y in _car_in_range(X, q, r):
             a, b = (X[y], q) if direction == 1 else (q, X[y])            # the motion runs from the row to the column
             if w.kind == "dubins":
@@ -92,9 +95,9 @@ def oracle_near(orc, w, q, direction, want_bits=True):
     return np.array(idx, dtype=np.int64), np.array(wt, dtype=np.float64), np.array(bits, dtype=bool)
 
 
-def car_margin(orc, w, Q):
+def car_margin(orc, w, Q, sp=sc.SP):
     """The least |cost - r| / r over every car cost the lists of Q evaluate, both directions (positions within r)."""
-    rt, sp, r = params(w)
+    rt, _, r = params(w)
     least = np.inf
     for q in np.atleast_2d(Q):
         for y in _car_in_range(w.X, q, r):
@@ -252,13 +255,13 @@ def slow(w, s):
     return s
 
 
-def motion_free(orc, w, a, b, lohi=None):
+def motion_free(orc, w, a, b, lohi=None, sp=sc.SP):
     lohi = w.lohi if lohi is None else lohi
     if w.kind == "di":
         return orc.di_is_free_motion(a, b, sc.RHO, sc.R_DI, lohi, w.ss_lo, w.ss_hi)
     if w.kind == "dubins":
-        return orc.dubins_is_free_motion(a, b, sc.RT, sc.SP, lohi, w.ss_lo, w.ss_hi)[0]
-    return orc.car_is_free_motion(2, a, b, sc.RT, sc.SP, lohi, w.ss_lo, w.ss_hi)[0]
+        return orc.dubins_is_free_motion(a, b, params(w)[0], sp, lohi, w.ss_lo, w.ss_hi)[0]
+    return orc.car_is_free_motion(2, a, b, params(w)[0], sp, lohi, w.ss_lo, w.ss_hi)[0]
 
 
 def lonely_goal(orc, w, seed, tries=400):

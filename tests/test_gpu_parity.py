@@ -860,16 +860,16 @@ def _assert_car_plan_close(got, want, N):
 def test_dubins_steer_batch(ctx, orc):
     rng = np.random.default_rng(61)
     X0, _, _, _ = _car_world(rng, 4000, 1); X1, _, _, _ = _car_world(rng, 4000, 1)
-    for rt in (0.05, 0.3, 2.0):
-        cost, ctrl = ctx.dubins_steer(X0, X1, rt, 1.0)
+    for rt, sp in [(rt, sp) for rt in (0.05, 0.3, 2.0) for sp in (1.0, 0.7)]:
+        cost, ctrl = ctx.dubins_steer(X0, X1, rt, sp)
         # (1) parity: the oracle with the C library's transcendental functions
-        want = [orc.dubins(a, b, rt, 1.0) for a, b in zip(X0, X1)]
+        want = [orc.dubins(a, b, rt, sp) for a, b in zip(X0, X1)]
         wc = np.array([w[0] for w in want]); wu = np.array([w[1] for w in want])
         assert np.allclose(cost, wc, rtol=1e-12, atol=0)
         assert np.array_equal(ctrl[:, :, 1:], wu[:, :, 1:]) and np.allclose(ctrl, wu, rtol=0, atol=1e-12)      # same word, same durations
         # (2) self-consistency: ONE header on both sides (mp_math.h) -- costs, the winning word and its durations bit-identical
         with orc.device_math():
-            want = [orc.dubins(a, b, rt, 1.0) for a, b in zip(X0, X1)]
+            want = [orc.dubins(a, b, rt, sp) for a, b in zip(X0, X1)]
         assert np.array_equal(cost, np.array([w[0] for w in want])) and np.array_equal(ctrl, np.array([w[1] for w in want]))
 
 
@@ -925,15 +925,15 @@ def test_reedsshepp_steer_batch(ctx, orc):
     X0, _, _, _ = _car_world(rng, 4000, 1); X1, _, _, _ = _car_world(rng, 4000, 1)
     X1[:50] = X0[:50]                                                   # coincident poses
     X1[50:100, 2] = X0[50:100, 2]                                       # pure translations
-    for rt in (0.05, 0.3, 2.0):
-        cost, ctrl, nsegs = ctx.reedsshepp_steer(X0, X1, rt, 1.0)
+    for rt, sp in [(rt, sp) for rt in (0.05, 0.3, 2.0) for sp in (1.0, 0.7)]:
+        cost, ctrl, nsegs = ctx.reedsshepp_steer(X0, X1, rt, sp)
         # (1) parity: libm oracle -- costs to 1e-12, the same word (segment count, directions, gears), durations to 1e-12
-        wc, wl, wu = _rs_batch([orc.reedsshepp(a, b, rt, 1.0) for a, b in zip(X0, X1)])
+        wc, wl, wu = _rs_batch([orc.reedsshepp(a, b, rt, sp) for a, b in zip(X0, X1)])
         assert np.allclose(cost, wc, rtol=1e-12, atol=1e-15)
         assert np.array_equal(nsegs, wl) and np.array_equal(ctrl[:, :, 1:], wu[:, :, 1:]) and np.allclose(ctrl, wu, rtol=0, atol=1e-12)
         # (2) self-consistency: same transcendental functions on both sides (mp_math.h), so ties between words resolve identically
         with orc.device_math():
-            wc, wl, wu = _rs_batch([orc.reedsshepp(a, b, rt, 1.0) for a, b in zip(X0, X1)])
+            wc, wl, wu = _rs_batch([orc.reedsshepp(a, b, rt, sp) for a, b in zip(X0, X1)])
         assert np.array_equal(cost, wc)
         assert np.array_equal(nsegs, wl) and np.array_equal(ctrl, wu)
         for i in range(len(wc)):                                        # segments past nsegs are zero
