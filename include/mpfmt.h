@@ -1116,7 +1116,8 @@ MPFMT_API int32_t mpfmt_timing_get(mpfmt_ctx* ctx, const char* name, double* avg
  * "debug_small_lists": test knob, shrinks the pending lists of the fused edge tests so that their overflow path runs. */
 MPFMT_API int32_t mpfmt_set_option(mpfmt_ctx* ctx, const char* name, int64_t value);
 /* Counters of the last graph build: "rdisc_path_used", "pairs_tested", "survivors" (pairs that passed the
- * MFMA filter), "nnz", "slices", "cells", "rdisc_half_used", "pool_used"; of the last step's edge tests: "sweep_form"
+ * MFMA filter), "nnz", "slices", "cells", "rdisc_half_used", "pool_used", "drains" / "drain_boxes" (drains of the pair kernel that
+ * ran the broad phase's box walk, and the boxes they walked in all; 0 where the drain held no broad phase); of the last step's edge tests: "sweep_form"
  * (0 / 1 / 2 as "fuse_broad"), "pair_items" (pairs listed for the exact tests; a synchronising read); diagnostics: "redo_count" /
  * "redo_reason" (builds redone since the ctx was made and why: 1 a chunk list was cut, 2 a log overflowed, 4 a column too long for the
  * ordering pass, 8 more entries than allocated, 16 the pending-pair list was cut), "qcap" (records a quarter log holds), "ord_per_cu"

@@ -942,13 +942,14 @@ __global__ void k_spec_check(const int32_t* __restrict__ pool_flag, const int32_
 
 // everything the host wants to know after a count, gathered into one block so that ONE copy into pinned memory brings it
 // back (four separate copies into pageable host variables are four blocking round trips: ~100 us of idle GPU per step)
-struct count_readback { unsigned long long pairs[512]; long long nnz; int pool_over, list_mx, max_deg, pad_, qmax, pad2_; };
+struct count_readback { unsigned long long pairs[512]; long long nnz; int pool_over, list_mx, max_deg, pad_, qmax, pad2_; unsigned long long dstat[512]; };
 __global__ __launch_bounds__(512) void k_count_readback(const unsigned long long* __restrict__ pairs, const int64_t* __restrict__ nnz,
                                                         const int32_t* __restrict__ pool_flag, const int32_t* __restrict__ list_max,
                                                         const int32_t* __restrict__ max_deg, count_readback* __restrict__ out,
-                                                        const int32_t* __restrict__ pend_over)
+                                                        const int32_t* __restrict__ pend_over, const unsigned long long* __restrict__ dstat)
 {
     out->pairs[threadIdx.x] = pairs[threadIdx.x];
+    out->dstat[threadIdx.x] = dstat ? dstat[threadIdx.x] : 0ull;      // (the drain's box-walk counters: arena only)
     if (threadIdx.x == 0) {
         out->pad_ = pend_over ? *pend_over : 0;               // (speculative step: a segment of the pending-entry list overflowed)
         out->nnz = *nnz;
@@ -983,10 +984,10 @@ int32_t mpfmt_rdisc_count_launch(mpfmt_ctx* ctx, double r, bool spec)
     // The small per-build counters live in ONE arena zeroed by ONE fill: 512 pair counters + the longest column's
     // word (k_degree), the logs' overflow flag, the pending-pair list's region counters + its overflow flag.  (A ctx whose counters
     // were allocated one by one before -- by the steering spaces' builds -- keeps them and their separate fills.)
-    // (... and the quarter logs' cursors behind them)
+    // (... the drain's 256 x {drains, boxes walked} counters, and the quarter logs' cursors behind them)
     // The fill is issued beside the chunk lists when the step forks there (a fill between two kernels of one stream costs ~15 us of
     // dispatch gaps on top of its 3), else in front of the pair kernel.
-    constexpr size_t ZA_PAIRS = 0, ZA_FLAG = 4128, ZA_PCNT = 4160, ZA_OCTR = 4160 + 4112, ZA_QLEN = ZA_OCTR + 32, ZA_BYTES = ZA_QLEN;
+    constexpr size_t ZA_PAIRS = 0, ZA_FLAG = 4128, ZA_PCNT = 4160, ZA_OCTR = 4160 + 4112, ZA_DSTAT = ZA_OCTR + 32, ZA_QLEN = ZA_DSTAT + 4096, ZA_BYTES = ZA_QLEN;
     const size_t za_need = ZA_BYTES + sizeof(int32_t) * (size_t)std::max<int64_t>(nt * 4, 1);
     bool counters_zeroed = false;
     auto zero_counters = [&]() -> int32_t {
@@ -998,6 +999,7 @@ int32_t mpfmt_rdisc_count_launch(mpfmt_ctx* ctx, double r, bool spec)
             ctx->pair_cnt = (int32_t*)(za + ZA_PCNT);
             ctx->qlen = (int32_t*)(za + ZA_QLEN);
             ctx->ord_ctr = (int32_t*)(za + ZA_OCTR);
+            ctx->d_dstat = (unsigned long long*)(za + ZA_DSTAT);
         }
         if (ctx->zarena) {
             HIPCHK(ctx, hipMemsetAsync(ctx->zarena, 0, za_need, ctx->stream));
@@ -1253,7 +1255,8 @@ int32_t mpfmt_rdisc_count_finish(mpfmt_ctx* ctx, double r, bool* spec_failed)
     if ((rc = ctx->rb_host.ensure(ctx, sizeof(count_readback)))) return rc;
     hipLaunchKernelGGL(k_count_readback, dim3(1), dim3(512), 0, ctx->stream, ctx->d_pairs, ctx->colptr + N, pool ? ctx->pool_flag : nullptr,
                        (ctx->spec_lists && nt > 0) ? ctx->list_max : nullptr, (const int32_t*)(ctx->d_pairs + 512), (count_readback*)ctx->rb_dev.get(),
-                       ctx->sweep_in_order ? (const int32_t*)ctx->pair_over : (ctx->pend_valid && ctx->sweep_pending_used) ? (const int32_t*)ctx->pend_over : nullptr);
+                       ctx->sweep_in_order ? (const int32_t*)ctx->pair_over : (ctx->pend_valid && ctx->sweep_pending_used) ? (const int32_t*)ctx->pend_over : nullptr,
+                       (ctx->zarena && ctx->cnt_mf) ? (const unsigned long long*)ctx->d_dstat : nullptr);
     HIPCHK(ctx, hipMemcpyAsync(ctx->rb_host, ctx->rb_dev, sizeof(count_readback), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     const count_readback* rb = (const count_readback*)ctx->rb_host.get();
@@ -1296,6 +1299,7 @@ int32_t mpfmt_rdisc_count_finish(mpfmt_ctx* ctx, double r, bool* spec_failed)
     for (int i = 1; i < 256; ++i) { pairs[0] += pairs[2 * i]; pairs[1] += pairs[2 * i + 1]; }
     ctx->pairs_tested = (int64_t)pairs[0];
     ctx->survivors = (int64_t)pairs[1];
+    { unsigned long long dr = 0, db = 0; for (int i = 0; i < 256; ++i) { dr += rb->dstat[2 * i]; db += rb->dstat[2 * i + 1]; } ctx->drains = (int64_t)dr; ctx->drain_boxes = (int64_t)db; }
     ctx->graph_r = r;
     ctx->graph_counted = true;
     ctx->graph_filled = false;

@@ -27,6 +27,7 @@
 #include "sweep_cmpx.h"
 #include "sweep_predicates.h"
 #include "mf_operand.h"
+#include "drain_cull.h"
 #include <algorithm>
 #include <cmath>
 
@@ -74,7 +75,7 @@ struct mf_args {
     const int32_t* list_len;        // [tiles of the shard]
     int64_t list_cap;
     unsigned long long* pairs;
-    unsigned long long* survivors;
+    unsigned long long* dstat;      // 256 x {drains that ran the box walk, boxes they walked} sharded counters (nullptr: not counted)
     // MODE 2 (single pass): every exact hit is appended -- while it is found -- to the LOG OF ITS COLUMN'S QUARTER TILE (16 consecutive
     // cell-sorted columns): one log per quarter whoever finds the hit (any slice of the column's own tile; in a half build also the
     // tiles before it, which see the pair from the other end).  A record is 12 bytes in two arrays: a key word -- row sample index
@@ -94,7 +95,7 @@ struct mf_args {
     int32_t fb;
     int32_t M;
     const double* boxes;            // [M][2][D]
-    const unsigned long long* smask;   // [npad] per cell-sorted sample: bit (k & 63) set when box k lies within r (per axis) of the sample
+    const unsigned long long* smask;   // [npad] per cell-sorted sample: bit (k & 63) set when box k lies within r (Euclidean, drain_cull.h) of the sample
                                     // (k_sample_masks): a segment's box can only meet boxes in the masks of BOTH its ends
     // fb == 2: the pairs whose segment box met an obstacle's are listed (MF_NREG regions of icap 16-byte items, one per (pair, box)
     // unit) for k_exact_pairs, which runs the slab tests in both directions and sets bit 31 of the blocked records' key
@@ -385,11 +386,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(6, 6)))
 }
 
 // ---- per-sample obstacle masks for the broad phase in the drain ------------------------------------------------------
-// One wavefront per tile, lane = sample: bit (k & 63) of a sample's mask is set unless box k is farther than r from the sample along
-// some axis (the negated comparisons of boxesND.jl:44-45, so a NaN bound keeps the bit).  Both ends of an edge lie within r of each
-// other, hence the edge's box [min, max] lies within r of either end along every axis: a box that meets it has its bit in BOTH ends'
-// masks.  The drain ORs (mask_q & mask_c) over its 64 pairs and walks only those boxes of the tile's cull -- 12 instead of 20 at
-// the north star (measured on the host, tools/sim_drain_masks.py).
+// One wavefront per tile, lane = sample: bit (k & 63) of a sample's mask is set unless box k is farther than r from the sample -- in
+// the Euclidean norm of the per-axis gaps, behind the per-axis comparisons (negated as in boxesND.jl:44-45, so a NaN bound keeps the
+// bit): drain_cull.h has the rule and its argument.  Where the segment box of an edge meets a box, the per-axis gap between either end
+// and the box is at most the edge's extent along that axis, so the gap vector is no longer than the edge, at most r: the box has its
+// bit in BOTH ends' masks.  The drain ORs (mask_q & mask_c) over its 64 pairs and walks only those boxes of the tile's cull (the same
+// rule on the hull's gap vector) whose bit is in that OR -- 8.6 boxes per drain instead of the per-axis rule's 14.8 at the north star
+// (simulated on the host, tools/sim_drain_masks.py; the device's own figure is stat drain_boxes / drains: 8.15).  A mask is ONE word:
+// beyond 64 boxes, box k answers to bit k & 63 and shares it with up to three others.
 template <int D>
 __global__ __launch_bounds__(256) void k_sample_masks(const double* __restrict__ Xs, const double* __restrict__ tile_lo, const double* __restrict__ tile_hi,
                                                       int64_t tile_begin, int64_t nt, double rpad, const double* __restrict__ boxes, int M,
@@ -404,17 +408,17 @@ __global__ __launch_bounds__(256) void k_sample_masks(const double* __restrict__
         for (int64_t z = z0 + threadIdx.x; z < z1; z += blockDim.x) zero[z] = 0ull;
     }
     const int lane = threadIdx.x & 63;
-    const int64_t tl = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    // (the wavefront's number read back as a scalar: the tile's hull then lives in scalar registers, not in 4 D vector ones)
+    const int64_t tl = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (tl >= nt) return;
     const int64_t tile = tile_begin + tl;
     if (tileneed && !tileneed[tile]) return;                  // (a tile this rank never reads: shard + halo index)
-    const double rm = rpad * (1.0 + 1e-6) + 1e-300;
-    double xl[D], xh[D], ulo[D], uhi[D];
+    const double rm = MF_CULL_MARGIN(rpad);
+    double x[D], tl_[D], th_[D];
 #pragma unroll
     for (int i = 0; i < D; ++i) {
-        const double x = Xs[(tile * 64 + lane) * D + i];
-        xl[i] = x - rm; xh[i] = x + rm;
-        ulo[i] = tile_lo[tile * D + i] - rm; uhi[i] = tile_hi[tile * D + i] + rm;
+        x[i] = Xs[(tile * 64 + lane) * D + i];
+        tl_[i] = tile_lo[tile * D + i]; th_[i] = tile_hi[tile * D + i];
     }
     // the boxes that survive the tile's cull (lane = box) are staged in LDS, then every lane (= sample) walks them with broadcast reads
     // (wave-uniform scalar loads were a chain of ~20 scalar-cache round trips per wavefront: 46 us for the 15 625 tiles)
@@ -430,7 +434,8 @@ __global__ __launch_bounds__(256) void k_sample_masks(const double* __restrict__
         if (kbx < M) {
             const double* bp = boxes + (int64_t)kbx * 2 * D;
 #pragma unroll
-            for (int i = 0; i < D; ++i) { bl[i] = bp[i]; bh[i] = bp[D + i]; out |= (int)(bh[i] < ulo[i]) | (int)(bl[i] > uhi[i]); }
+            for (int i = 0; i < D; ++i) { bl[i] = bp[i]; bh[i] = bp[D + i]; }
+            out = !drain_cull_keep(D, tl_, th_, bl, bh, rm);     // (the hull's gap vector: a lower bound of every sample's)
         }
         const bool sv = kbx < M && !out;
         const unsigned long long mb = __ballot(sv);
@@ -446,10 +451,7 @@ __global__ __launch_bounds__(256) void k_sample_masks(const double* __restrict__
         for (int k = 0; rem; ++k) {
             const int b = __ffsll((long long)rem) - 1;
             rem &= rem - 1;
-            int o2 = 0;
-#pragma unroll
-            for (int i = 0; i < D; ++i) o2 |= (int)(s_bx[wv][k][D + i] < xl[i]) | (int)(s_bx[wv][k][i] > xh[i]);
-            if (!o2) mask |= 1ull << b;
+            if (drain_cull_keep(D, x, x, &s_bx[wv][k][0], &s_bx[wv][k][D], rm)) mask |= 1ull << b;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -496,6 +498,9 @@ int32_t mpfmt_launch_sample_masks(mpfmt_ctx* ctx, double r, void* zero, size_t z
 #define MF_NREG 1024                // regions of the pending-pair list (fb == 2)
 #define MF_RCAP 128                 // record queue entries per wavefront (expanded 64 at a time)
 #define MF_QSZ 320                  // survivor queue entries per wavefront (drained 64 at a time)
+#ifndef MF_NO_DRAIN_STATS           // 1: build without the drain's two statistics counters (A/B of their cost; stats drains / drain_boxes read 0)
+#define MF_NO_DRAIN_STATS 0
+#endif
 #ifndef MF_ABLATE                   // timing experiments only (results invalid): 1 skip extraction, 2 skip refine, 4 skip MFMA
 #define MF_ABLATE 0
 #endif
@@ -545,12 +550,13 @@ __device__ __forceinline__ void rdisc_mfma_body(mf_args a, mpfmt_grid G)
     const int kb = lane >> 5, col = lane & 31;
 
     // ---- broad phase in the drain: the obstacles that can meet a segment out of this tile at all (lane = box).  Both ends of such a
-    // segment lie within r of the tile's hull (the candidate is within r of a query of the tile), so a box farther than that from
-    // the hull in some axis is out for the whole item
+    // segment lie within r of the tile's hull (the candidate is within r of a query of the tile), and a box that meets the segment's
+    // lies within r of its end in the tile (drain_cull.h), so a box whose gap vector to the hull is longer than r is out for the whole item
     unsigned long long bsurv[4] = {0ull, 0ull, 0ull, 0ull};
     if constexpr (MODE == 2) {
         if (a.fb) {
-            // (culled once per tile by k_sample_masks -- with its slightly wider margin, a superset of the boxes within rpad of the hull;
+            // (culled once per tile by k_sample_masks -- with its slightly wider margin, a superset of the boxes within rpad of the hull in
+            // the Euclidean norm of the per-axis gaps;
             // the comparisons of the drain decide -- instead of once per item here: 4 x 12 loads and 24 comparisons per lane)
             const unsigned long long* tb = a.smask + a.npad + tile * 4;
 #pragma unroll
@@ -658,6 +664,7 @@ __device__ __forceinline__ void rdisc_mfma_body(mf_args a, mpfmt_grid G)
     int rcount = 0;                                           // wave-uniform record queue length
     int pool_over = 0;
     [[maybe_unused]] int ndrain = 0;                          // drains of this item so far (wave-uniform): spreads its pending-pair items over the regions
+    [[maybe_unused]] uint32_t nwalk = 0, nwalk_bx = 0;        // drains of this item that ran the box walk, and the boxes they walked (wave-uniform; stats)
     auto drain = [&](int n) {
         // takes the LAST n queue entries (order is irrelevant: columns are sorted afterwards), so nothing moves
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -843,6 +850,11 @@ __device__ __forceinline__ void rdisc_mfma_body(mf_args a, mpfmt_grid G)
                 }
 #else
                 um = ~0ull;
+#endif
+#if !MF_NO_DRAIN_STATS
+                nwalk = (uint32_t)__builtin_amdgcn_readfirstlane((int)(nwalk + 1u));
+                nwalk_bx = (uint32_t)__builtin_amdgcn_readfirstlane((int)(nwalk_bx + (uint32_t)(__popcll(bsurv[0] & um) + __popcll(bsurv[1] & um) +
+                                                                                                  __popcll(bsurv[2] & um) + __popcll(bsurv[3] & um))));
 #endif
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
@@ -1149,6 +1161,7 @@ __device__ __forceinline__ void rdisc_mfma_body(mf_args a, mpfmt_grid G)
 
     if (MODE == 2) {
         if (pool_over) *a.pool_flag = 1;                          // a quarter log overflowed: the build is redone in the two-pass form
+        if (lane == 0 && a.dstat && nwalk) { atomicAdd(a.dstat + 2 * (blockIdx.x & 255), (unsigned long long)nwalk); atomicAdd(a.dstat + 2 * (blockIdx.x & 255) + 1, (unsigned long long)nwalk_bx); }
     }
     if constexpr (MODE == 3) {
         a.slice_cnt[(int64_t)slice * a.npad + qpos] = s_cnt[lane];
@@ -1398,7 +1411,7 @@ int32_t mpfmt_launch_rdisc_mfma(mpfmt_ctx* ctx, double r, float negT)
     a.slice_cnt = ctx->slice_cnt; a.tptr = ctx->tptr; a.rowtmp = ctx->rowtmp; a.valtmp = ctx->valtmp;
     a.lists = (const uint32_t*)ctx->lists.get(); a.list_len = ctx->list_len; a.list_cap = ctx->list_cap;
     a.pairs = (MODE == 1) ? nullptr : ctx->d_pairs;              // 256 x {tested, survivors} sharded counters
-    a.survivors = nullptr;
+    a.dstat = (MODE == 2 && ctx->zarena) ? ctx->d_dstat : nullptr;
     a.pool_flag = ctx->pool_flag; a.qcap = ctx->qcap;
     a.qkey = ctx->qkey; a.qd2 = ctx->qd2; a.qlen = ctx->qlen;
     a.half = (MODE == 2 && ctx->half_used) ? 1 : 0;
@@ -1547,6 +1560,7 @@ int32_t mpfmt_rdisc_stream_impl(mpfmt_ctx* ctx, double r, const double* C_host, 
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 1; i < 256; ++i) { pairs[0] += pairs[2 * i]; pairs[1] += pairs[2 * i + 1]; }
     ctx->pairs_tested = (int64_t)pairs[0]; ctx->survivors = (int64_t)pairs[1];
+    ctx->drains = 0; ctx->drain_boxes = 0;                     // (no box walk in the streaming drain's form)
     ctx->st_C = nullptr; ctx->st_H = nullptr; ctx->st_free = 0;
     if (nnz_out) *nnz_out = (int64_t)tot;
     return MPFMT_OK;

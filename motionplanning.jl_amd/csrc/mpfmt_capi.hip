@@ -2814,6 +2814,8 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "boxes") == 0) { *value = ctx->have_boxes ? ctx->M : 0; return MPFMT_OK; }
     if (strcmp(name, "graph_swept") == 0) { *value = ctx->graph_swept ? 1 : 0; return MPFMT_OK; }
     if (strcmp(name, "survivors") == 0) { *value = ctx->survivors; return MPFMT_OK; }
+    if (strcmp(name, "drains") == 0) { *value = ctx->drains; return MPFMT_OK; }
+    if (strcmp(name, "drain_boxes") == 0) { *value = ctx->drain_boxes; return MPFMT_OK; }
     if (strcmp(name, "pairs_tested") == 0) { *value = ctx->pairs_tested; return MPFMT_OK; }
     if (strcmp(name, "nnz") == 0) { *value = ctx->nnz; return MPFMT_OK; }
     if (strcmp(name, "slices") == 0) { *value = ctx->S; return MPFMT_OK; }

@@ -268,7 +268,7 @@ struct mpfmt_ctx {
     mpfmt_dbuf<double> qd2;               // [quarter tiles of the shard][qcap] squared distances
     const double* st_C = nullptr; const uint64_t* st_H = nullptr; int st_free = 0;      // streaming mode (mpfmt_rdisc_stream): inputs of the launch in flight
     mpfmt_dbuf<void> st_best; mpfmt_dbuf<int32_t> st_besti, st_nfree;                    //   and its per-slice partials [S][npad]
-    mpfmt_dbuf<void> smask;               // [npad] per-sample obstacle masks (k_sample_masks): the drain's broad phase walks the boxes in (mask_q & mask_c) only
+    mpfmt_dbuf<void> smask;               // [npad] per-sample obstacle masks (k_sample_masks: the boxes within r of the sample, Euclidean -- drain_cull.h): the drain's broad phase walks the boxes in (mask_q & mask_c) only
     int64_t pool_hint_qmax = 0;          // records in the fullest quarter (16 consecutive cell-sorted columns) of the last build: sizes the next one's logs
     // half build of the single-pass r-disc graph (kernels_rdisc_mfma.hip: every pair found once, the other column's record goes
     // to a foreign log of that column's tile)
@@ -333,7 +333,9 @@ struct mpfmt_ctx {
     int32_t* pair_over = nullptr;        // view: pair_cnt + 1024
     int32_t* qlen = nullptr;             // view: [quarter tiles of the shard] the logs' cursors
     int32_t* ord_ctr = nullptr;          // view: [8] the ordering kernel's per-XCD quarter counters (arena only)
+    unsigned long long* d_dstat = nullptr;   // view: [512] 256 x {drains that ran the box walk, boxes they walked} sharded counters (arena only)
     int64_t pairs_tested = 0;
+    int64_t drains = 0, drain_boxes = 0; // of the last count whose drain held the broad phase (stats "drains", "drain_boxes"); 0 otherwise
 
     // ---- k-nearest graph (kernels_knn.hip): installed in colptr / rowval / nzval like an r-disc graph, graph_r = its longest entry ----
     int64_t knn_k = 0;                   // > 0 with graph_filled: the resident graph is the k-nearest one of this k (never "a filled graph of radius graph_r")
