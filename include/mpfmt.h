@@ -532,6 +532,61 @@ MPFMT_API int32_t mpfmt_host_roadmap_query(int64_t N, int32_t d, const double* X
                                  const double* ss_hi, double r, const double* s, const double* g, double* cost, int64_t* path, int64_t cap,
                                  mpfmt_roadmap_info* info);
 
+/* ---- growing the sample set of a resident roadmap: addpoints (src/nearneighbors.jl:108) behind fmtstar!(P, N)'s incremental sampling
+ *      (src/planners/fmt.jl:30, src/sampling.jl:43) without the rebuild (DESIGN.md "Growing the sample set").
+ * mpfmt_samples_add : X_add d x n_add column-major host doubles (the ctx's d), appended behind the ctx's samples: new sample j becomes
+ *      index N + j (1-based N + 1 ... N + n_add).  mpfmt_samples_add_device: the same for a batch in HBM of the ctx's device, read on
+ *      the ctx's stream (ordering as for mpfmt_upload_samples_device).
+ *      IN PLACE when the ctx is unsharded, uses the N-D AABB checker with an identity workspace (dw == d), holds a resident r-disc graph
+ *      (built or imported) whose mask is swept and current, and 0 < r_new <= the graph's radius (its own radius keeps it).  After the
+ *      call the ctx holds N + n_add samples, and colptr / rowval / nzval / the free mask (padding bits of the last word included) are
+ *      byte for byte what mpfmt_upload_samples of the concatenated set and mpfmt_graph_step_device(r_new) leave:
+ *        membership  i != v and d2 <= r_new * r_new (d2 the left-to-right unfused fp64 fold), distance sqrt(d2);
+ *        old column  keeps its entries (radius rule below) and gains the new samples within r_new behind them;
+ *        new column  old and new neighbours ascending, self excluded BY INDEX (a bit-copy of another sample is a neighbour at 0);
+ *        free bit    of (row y, column x) is is_free_motion(V[y], V[x]), first-point bounds test included -- both directions of a
+ *                    new pair are tested; old entries keep their bits.
+ *      r_new below the graph's radius: an old entry stays iff its d2 <= fl(r_new * r_new).  Only fl(sqrt(d2)) is stored; with
+ *      s = fl(sqrt(fl(r_new * r_new))) a stored distance < s is a member, > s is not, == s decides nothing and the entry's d2 is
+ *      computed again from the coordinates.  An imported graph's distances are taken as given.
+ *      Afterwards the ctx is in the state mpfmt_graph_import leaves plus a current swept mask: the radius is r_new, the cell grid
+ *      is that of the grown set, a resident steering graph, a tracked field and a tracked cost-to-go are dropped (as new samples drop
+ *      them); mpfmt_prmstar / mpfmt_fmtstar at r_new run without pair phase or sweep, mpfmt_boxes_add / _remove stay in place.
+ *      ALL OR NOTHING: the grown arrays are built in spare buffers that change places with the ctx's own only when everything has
+ *      succeeded.  Footprint: at the peak the ctx holds the graph twice (old and grown colptr / rowval / nzval / mask) plus one
+ *      byte per grown entry and the new samples' lists (about 2 x 21 bytes per added entry); the spare buffers stay with the ctx.
+ *      Refused, leaving samples, graph, mask and tracked state as they were: NULL with a positive count, a non-finite coordinate, an
+ *      r_new that is not finite and positive, N + n_add beyond the sample limit (MPFMT_ERR_ARG); a failed allocation
+ *      (MPFMT_ERR_HIP).  n_add == 0 succeeds and does nothing.
+ *      EVERY OTHER STATE (no resident graph, a k-nearest graph, an unswept or stale mask, a sharded ctx, the 2-D SAT world, a
+ *      non-identity workspace, r_new above the graph's radius): the samples are appended on the device and the ctx is what
+ *      mpfmt_upload_samples of the concatenated set leaves.
+ *      mpfmt_get_stat: "samples_add_path" (1 in place, 0 invalidated), "samples_add_candidates" (distances evaluated),
+ *      "samples_add_entries" (entries added, both directions), "samples_add_dropped" (old entries the smaller radius removed);
+ *      timing keys "samples_add_near", "samples_add_merge", "samples_add".
+ *      Meant for n_add well below N (a refinement step).  The merge moves the whole CSC once whatever n_add is; every new sample walks
+ *      its 3^d cells of the grid on its own.  Measured on one MI355X (profiles/grow_mi355x.json): at N = 1e6 in R^6
+ *      (nnz 1.1e8) 100 new samples cost 1.5 ms against 3.4 ms for the upload and step of the concatenated set, 1e4 cost the same as
+ *      the rebuild, 1e5 five times more; in R^12 100 samples cost 7 ms against 35 ms and 1e4 six times the rebuild.  Growth pays up
+ *      to n_add / N of about 1 % in R^6 and about 0.05 % in R^12; beyond that, upload the concatenated set.
+ * mpfmt_host_graph_grow : the same on the host over the device-native arrays (X d x (N + n_add), all samples; 0-based colptr / rowval,
+ *      nzval and efree of the old graph; lohi (2 d) x M, bounds or both NULL).  No ctx, no device.  cap == 0 is the size query
+ *      (out_colptr, *nnz_out and info are written); *nnz_out > cap: MPFMT_ERR_CAPACITY.  The normative statement of the contract. */
+typedef struct {
+    int64_t candidates;        /* distances evaluated */
+    int64_t entries;           /* entries added, both directions */
+    int64_t dropped;           /* old entries the smaller radius removed */
+} mpfmt_grow_info;
+/* the radius of the resident r-disc graph (built, imported or grown); MPFMT_ERR_STATE when none is resident (a k-nearest or steering graph
+ * is none) */
+MPFMT_API int32_t mpfmt_graph_radius(mpfmt_ctx* ctx, double* r);
+MPFMT_API int32_t mpfmt_samples_add(mpfmt_ctx* ctx, const double* X_add, int64_t n_add, double r_new);
+MPFMT_API int32_t mpfmt_samples_add_device(mpfmt_ctx* ctx, const double* dX_add, int64_t n_add, double r_new);
+MPFMT_API int32_t mpfmt_host_graph_grow(int64_t N, int64_t n_add, int32_t d, const double* X, const int64_t* colptr, const int32_t* rowval,
+                              const double* nzval, const uint64_t* efree, const double* lohi, int32_t M, const double* ss_lo,
+                              const double* ss_hi, double r_new, int64_t* out_colptr, int32_t* out_rowval, double* out_nzval,
+                              uint64_t* out_efree, int64_t cap, int64_t* nnz_out, mpfmt_grow_info* info);
+
 /* ---- many-source fields and cost matrices: up to 64 sources per pass over the graph (DESIGN.md "Many sources per pass").
  *      mpfmt_graph_sssp and mpfmt_roadmap_query compute one field per pass over rowval / nzval / the mask.  The two calls here keep the
  *      labels as L[sample][source], 64 doubles per sample, one wavefront lane per source: one visit of an entry serves 64 fields with one

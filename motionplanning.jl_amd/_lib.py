@@ -67,6 +67,10 @@ class RoadmapInfo(C.Structure):
                 ("usable_g", C.c_int64), ("rounds", C.c_int64), ("path_len", C.c_int64), ("ms_device", C.c_double)]
 
 
+class GrowInfo(C.Structure):
+    _fields_ = [("candidates", C.c_int64), ("entries", C.c_int64), ("dropped", C.c_int64)]
+
+
 class RoadmapMatrixInfo(C.Structure):
     _fields_ = [("groups", C.c_int64), ("rounds", C.c_int64), ("near_s", C.c_int64), ("usable_s", C.c_int64), ("near_g", C.c_int64),
                 ("usable_g", C.c_int64), ("ms_device", C.c_double)]
@@ -94,6 +98,12 @@ SYMBOLS = [
     ("mpfmt_set_shard", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
     ("mpfmt_upload_samples", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, C.c_int32]),
     ("mpfmt_upload_samples_device", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    ("mpfmt_graph_radius", C.c_int32, [C.c_void_p, c_d_p]),
+    ("mpfmt_samples_add", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, C.c_double]),
+    ("mpfmt_samples_add_device", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double]),
+    ("mpfmt_host_graph_grow", C.c_int32, [C.c_int64, C.c_int64, C.c_int32, c_d_p, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_d_p, C.c_int32,
+                                          c_d_p, c_d_p, C.c_double, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, C.c_int64, c_i64_p,
+                                          C.POINTER(GrowInfo)]),
     ("mpfmt_upload_boxes", C.c_int32, [C.c_void_p, c_d_p, C.c_int32, C.c_int32, c_d_p, c_d_p, C.c_int32]),
     ("mpfmt_boxes_add", C.c_int32, [C.c_void_p, c_d_p, C.c_int32]),
     ("mpfmt_boxes_remove", C.c_int32, [C.c_void_p, c_i64_p, C.c_int32]),
@@ -459,6 +469,40 @@ def host_roadmap_query(X, colptr0, rowval0, nzval, efree, F, lohi, ss_lo, ss_hi,
     return float(cost.value), path[:info.path_len].copy(), _roadmap_info(info)
 
 
+def host_graph_grow(X_all, n_old, colptr0, rowval0, nzval, efree, lohi, ss_lo, ss_hi, r_new):
+    """The r-disc graph of the first n_old samples of X_all (N, d) grown by the others, on the host (include/mpfmt.h, "growing the sample
+    set"): no GPU needed; the normative statement of Context.samples_add.  colptr0 / rowval0 0-based (rowval0 int32), efree packed
+    uint64; lohi (M, 2, d); ss_lo / ss_hi or None.  Returns (colptr0, rowval0, nzval, efree, info) of the grown graph at r_new."""
+    X = np.ascontiguousarray(X_all, dtype=np.float64)
+    N, d = X.shape
+    n_old = int(n_old)
+    colptr0 = np.ascontiguousarray(colptr0, dtype=np.int64)
+    rowval0 = np.ascontiguousarray(rowval0, dtype=np.int32)
+    nzval = np.ascontiguousarray(nzval, dtype=np.float64)
+    efree = np.ascontiguousarray(efree, dtype=np.uint64)
+    lohi = np.ascontiguousarray(lohi, dtype=np.float64).reshape(-1, 2, d)
+    lo = None if ss_lo is None else np.ascontiguousarray(ss_lo, dtype=np.float64)
+    hi = None if ss_hi is None else np.ascontiguousarray(ss_hi, dtype=np.float64)
+    if colptr0.size != n_old + 1 or n_old > N:
+        raise ValueError("colptr0 must have n_old + 1 entries, n_old <= N")
+    ocp = np.zeros(N + 1, dtype=np.int64)
+    nnz = C.c_int64(0)
+    info = GrowInfo()
+    L = lib()
+    args = (n_old, N - n_old, d, _dp(X), _ip(colptr0), _ip32(rowval0), _dp(nzval), _up(efree), _dp(lohi), lohi.shape[0], _dp(lo), _dp(hi),
+            float(r_new), _ip(ocp))
+    rc = L.mpfmt_host_graph_grow(*args, None, None, None, 0, C.byref(nnz), C.byref(info))
+    if rc != 0:
+        raise MPFMTError(rc, "mpfmt_host_graph_grow rejected its arguments")
+    n = nnz.value
+    orv = np.zeros(max(n, 1), dtype=np.int32); onz = np.zeros(max(n, 1), dtype=np.float64); oef = np.zeros(max(nwords(n), 1), dtype=np.uint64)
+    if n > 0:
+        rc = L.mpfmt_host_graph_grow(*args, _ip32(orv), _dp(onz), _up(oef), n, C.byref(nnz), C.byref(info))
+        if rc != 0:
+            raise MPFMTError(rc, "mpfmt_host_graph_grow failed")
+    return ocp, orv[:n], onz[:n], oef[:nwords(n)], dict(candidates=int(info.candidates), entries=int(info.entries), dropped=int(info.dropped))
+
+
 def _shortcut_info(i):
     return dict(status=int(i.status), iterations_done=int(i.iterations_done), n_out=int(i.n_out), max_working_len=int(i.max_working_len),
                 max_halvings=int(i.max_halvings), collision_checks=int(i.collision_checks), tests_evaluated=int(i.tests_evaluated))
@@ -589,6 +633,34 @@ class Context:
         self._chk(self._L.mpfmt_upload_samples_device(self._h, C.c_void_p(int(ptr)), int(N), int(d)))
         self.N, self.d = int(N), int(d)
         self.nnz = None
+
+    def samples_add(self, X_add, r=None):
+        """Append X_add (n_add, d) behind the ctx's samples (mpfmt_samples_add).  A resident, swept r-disc graph of an unsharded ctx
+        with the N-D AABB checker follows in place -- graph and mask byte for byte those of a fresh step on the concatenated set at r
+        (default: the graph's radius, r <= it) -- and stat("samples_add_path") == 1; in every other state the ctx is what upload_samples
+        of the concatenated set leaves (then r only has to be finite and positive)."""
+        X_add = np.ascontiguousarray(X_add, dtype=np.float64)
+        if X_add.ndim == 1:
+            X_add = X_add[None]
+        if X_add.ndim != 2 or (X_add.shape[0] > 0 and X_add.shape[1] != self.d):
+            raise ValueError("X_add must be (n_add, %s)" % self.d)
+        self._chk(self._L.mpfmt_samples_add(self._h, _dp(X_add) if X_add.shape[0] else None, X_add.shape[0], self._grow_radius(r)))
+        self.N += X_add.shape[0]
+        self.nnz = None
+
+    def samples_add_device(self, ptr, n_add, r=None):
+        """The same from a device pointer (n_add x d float64, C-contiguous, on this ctx's GPU)."""
+        self._chk(self._L.mpfmt_samples_add_device(self._h, C.c_void_p(int(ptr)), int(n_add), self._grow_radius(r)))
+        self.N += int(n_add)
+        self.nnz = None
+
+    def _grow_radius(self, r):
+        if r is not None:
+            return float(r)
+        g = C.c_double(0.0)
+        if self._L.mpfmt_graph_radius(self._h, C.byref(g)) == OK and g.value > 0.0:
+            return g.value
+        return 1.0                                           # (nothing to grow: any finite positive radius invalidates alike)
 
     def upload_boxes(self, lohi, ss_lo=None, ss_hi=None, dw=None):
         """lohi: (M, 2, dw) float64 (lo then hi per box)."""

@@ -354,6 +354,103 @@ int32_t mpfmt_upload_samples_device(mpfmt_ctx* ctx, const double* dX, int64_t N,
     return adopt_samples(ctx, dX, false, N, d);
 }
 
+// ---- growing the sample set (kernels_grow.hip) ---------------------------------------------------------------------------------------
+// the resident graph and mask can follow the new samples instead of being thrown away
+static bool samples_add_in_place(const mpfmt_ctx* ctx, double r_new)
+{
+    return ctx->world == 1 && ctx->cc_kind == 0 && ctx->have_boxes && ctx->dw == ctx->d && ctx->graph_filled && !ctx->knn_k && ctx->graph_swept &&
+           !ctx->steer_counted && !ctx->steer_filled && (ctx->nnz == 0 || ctx->graph_free) && ctx->step_state != 1 && r_new <= ctx->graph_r;
+}
+
+// Both forms: the grown set is assembled in the spare sample buffer -- the old samples device to device, no host round trip; the new ones
+// beside the finiteness check and their bounding box, as adopt_samples does -- and changes places with the ctx's own once it is accepted.
+static int32_t samples_add(mpfmt_ctx* ctx, const double* src, bool src_on_host, int64_t n_add, double r_new)
+{
+    if (n_add < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "n_add = %lld < 0", (long long)n_add);
+    if (n_add > 0 && !src) return mpfmt_fail(ctx, MPFMT_ERR_ARG, src_on_host ? "X_add is NULL" : "dX_add is NULL");
+    if (!(r_new > 0.0) || !std::isfinite(r_new)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "r_new must be finite and > 0");
+    if (!ctx->Xo || ctx->d < 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no samples uploaded (samples are added to a set: mpfmt_upload_samples fixes d)");
+    const int64_t n_old = ctx->N, N = n_old + n_add;
+    const int32_t d = ctx->d;
+    if (N >= ((int64_t)1 << 31) - 64) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "N + n_add = %lld out of range", (long long)N);
+    if (n_add == 0) return MPFMT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int32_t rc;
+    if ((rc = mpfmt_side_join(ctx))) return rc;
+    constexpr int NB = 256;
+    struct bb_block { double part[NB][2][MPFMT_MAX_DIM]; int32_t bad; int32_t pad_; };
+    if ((rc = ctx->bb_dev.ensure(ctx, sizeof(bb_block)))) return rc;
+    if ((rc = ctx->bb_host.ensure(ctx, sizeof(bb_block)))) return rc;
+    bb_block* dev = (bb_block*)ctx->bb_dev.get();
+    const int nb = (int)std::min<int64_t>(NB, (n_add * d + BBOX_THREADS - 1) / BBOX_THREADS);
+    const int64_t stride = std::max<int64_t>(((int64_t)std::max(nb, 1) * BBOX_THREADS / d) * d, d);
+    if ((rc = ctx->Xo_next.ensure(ctx, sizeof(double) * (size_t)N * d))) return rc;
+    double* dst = ctx->Xo_next.get() + (size_t)n_old * d;
+    mpfmt_timed tm(ctx);
+    if (n_old > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->Xo_next, ctx->Xo, sizeof(double) * (size_t)n_old * d, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(&dev->bad, 0, sizeof(int32_t), ctx->stream));
+    if (src_on_host) HIPCHK(ctx, hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n_add * d, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_bbox_partials, dim3(nb), dim3(BBOX_THREADS), 0, ctx->stream, src_on_host ? (const double*)dst : src, src_on_host ? (double*)nullptr : dst,
+                       n_add, d, stride, &dev->part[0][0][0], &dev->bad);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->bb_host, dev, sizeof(bb_block), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const bb_block* h = (const bb_block*)ctx->bb_host.get();
+    if (h->bad) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "an added sample has a non-finite coordinate (the ctx keeps the sample set and graph it had)");
+    double lo[MPFMT_MAX_DIM], hi[MPFMT_MAX_DIM], lo_was[MPFMT_MAX_DIM], hi_was[MPFMT_MAX_DIM];
+    for (int i = 0; i < d; ++i) {
+        lo_was[i] = ctx->bb_lo[i]; hi_was[i] = ctx->bb_hi[i];
+        lo[i] = n_old > 0 ? lo_was[i] : INFINITY; hi[i] = n_old > 0 ? hi_was[i] : -INFINITY;
+        for (int b = 0; b < nb; ++b) { lo[i] = std::min(lo[i], h->part[b][0][i]); hi[i] = std::max(hi[i], h->part[b][1][i]); }
+    }
+    const bool in_place = samples_add_in_place(ctx, r_new);
+    ctx->Xo.swap(ctx->Xo_next);
+    ctx->N = N;
+    for (int i = 0; i < d; ++i) { ctx->bb_lo[i] = lo[i]; ctx->bb_hi[i] = hi[i]; }
+    if (in_place) {
+        if ((rc = mpfmt_grow_apply(ctx, n_old, r_new))) {     // the ctx is again what it was; the cell order is rebuilt by whoever needs it next
+            ctx->Xo.swap(ctx->Xo_next);
+            ctx->N = n_old;
+            for (int i = 0; i < d; ++i) { ctx->bb_lo[i] = lo_was[i]; ctx->bb_hi[i] = hi_was[i]; }
+            ctx->grid_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0;
+            return rc;
+        }
+    }
+    ctx->samples_epoch += 1;
+    mpfmt_field_drop_internal(ctx);
+    mpfmt_togo_drop_internal(ctx);
+    ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
+    ctx->grow_path = in_place ? 1 : 0;
+    if (!in_place) {                                         // what mpfmt_upload_samples of the concatenated set leaves
+        ctx->grid_r = -1.0; ctx->graph_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0;
+        ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
+        ctx->nnz = 0;
+        ctx->grow_candidates = ctx->grow_entries = ctx->grow_dropped = 0;
+    }
+    tm.end("samples_add");
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_graph_radius(mpfmt_ctx* ctx, double* r)
+{
+    if (!ctx || !r) return MPFMT_ERR_ARG;
+    if (!ctx->graph_filled || ctx->knn_k || ctx->steer_filled) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no resident r-disc graph");
+    *r = ctx->graph_r;
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_samples_add(mpfmt_ctx* ctx, const double* X_add, int64_t n_add, double r_new)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    return samples_add(ctx, X_add, true, n_add, r_new);
+}
+
+int32_t mpfmt_samples_add_device(mpfmt_ctx* ctx, const double* dX_add, int64_t n_add, double r_new)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    return samples_add(ctx, dX_add, false, n_add, r_new);
+}
+
 // state-space bounds on their own: the BoundedStateSpace lo / hi for any state dimension (src/statespaces.jl:29-34).  The 2-D SAT
 // world's upload takes the two workspace bounds only; a steering space over it (double integrator R^4, SE2 cars) sets its own.
 int32_t mpfmt_set_state_bounds(mpfmt_ctx* ctx, const double* ss_lo, const double* ss_hi, int32_t d_state)
@@ -2727,6 +2824,10 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
         }
         return MPFMT_OK;
     }
+    if (strcmp(name, "samples_add_path") == 0) { *value = ctx->grow_path; return MPFMT_OK; }
+    if (strcmp(name, "samples_add_candidates") == 0) { *value = ctx->grow_candidates; return MPFMT_OK; }
+    if (strcmp(name, "samples_add_entries") == 0) { *value = ctx->grow_entries; return MPFMT_OK; }
+    if (strcmp(name, "samples_add_dropped") == 0) { *value = ctx->grow_dropped; return MPFMT_OK; }
     if (strcmp(name, "pend_overflowed") == 0) { *value = ctx->pend_overflowed ? 1 : 0; return MPFMT_OK; }
     if (strcmp(name, "redo_count") == 0) { *value = ctx->redo_count; return MPFMT_OK; }
     if (strcmp(name, "redo_reason") == 0) { *value = ctx->redo_reason; ctx->redo_reason = 0; return MPFMT_OK; }      // (bits since the last read)

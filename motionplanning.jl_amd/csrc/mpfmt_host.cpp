@@ -911,3 +911,92 @@ int32_t mpfmt_host_discretize(int32_t space, int32_t d, const double* params, co
     }
 #undef DISC_GO
 }
+
+// ---- growth of an r-disc graph by appended samples on the host (include/mpfmt.h, "growing the sample set"): the normative statement of
+// what mpfmt_samples_add leaves, and its checker.  Near sets by a scan of all samples, the free-motion test above; old entries are kept by
+// their stored distance, an entry that sits on the tie (nzval == fl(sqrt(fl(r_new * r_new)))) by its recomputed squared distance.
+int32_t mpfmt_host_graph_grow(int64_t N, int64_t n_add, int32_t d, const double* X, const int64_t* colptr, const int32_t* rowval,
+                              const double* nzval, const uint64_t* efree, const double* lohi, int32_t M, const double* ss_lo,
+                              const double* ss_hi, double r_new, int64_t* out_colptr, int32_t* out_rowval, double* out_nzval,
+                              uint64_t* out_efree, int64_t cap, int64_t* nnz_out, mpfmt_grow_info* info)
+{
+    if (!X || !colptr || !out_colptr || !nnz_out || !info || N < 0 || n_add < 0 || d < 1 || d > MPFMT_MAX_DIM || M < 0 || cap < 0) return MPFMT_ERR_ARG;
+    if ((M > 0 && !lohi) || (ss_lo == nullptr) != (ss_hi == nullptr) || !(r_new > 0.0) || !std::isfinite(r_new)) return MPFMT_ERR_ARG;
+    if (N + n_add >= ((int64_t)1 << 31) - 64) return MPFMT_ERR_ARG;
+    if (cap > 0 && (!out_rowval || !out_nzval || !out_efree)) return MPFMT_ERR_ARG;
+    if (colptr[0] != 0) return MPFMT_ERR_ARG;
+    for (int64_t j = 0; j < N; ++j) if (colptr[j + 1] < colptr[j]) return MPFMT_ERR_ARG;
+    const int64_t nnz = colptr[N];
+    if (nnz > 0 && (!rowval || !nzval || !efree)) return MPFMT_ERR_ARG;
+    for (int64_t e = 0; e < nnz; ++e) if (rowval[e] < 0 || rowval[e] >= N || !(nzval[e] >= 0.0)) return MPFMT_ERR_ARG;
+    const int64_t NN = N + n_add;
+    for (int64_t i = 0; i < NN * d; ++i) if (!std::isfinite(X[i])) return MPFMT_ERR_ARG;
+    auto bitp = [](const uint64_t* m, int64_t i) { return (m[i >> 6] >> (i & 63)) & 1ull; };
+    auto dist2 = [&](const double* a, const double* b) {
+        double s2 = 0.0;
+        for (int i = 0; i < d; ++i) { const double t = a[i] - b[i]; const double tt = t * t; s2 = (i == 0) ? tt : s2 + tt; }
+        return s2;
+    };
+    ShortcutWorld W{d, lohi, M, ss_lo, ss_hi};
+    memset(info, 0, sizeof *info);
+    const double r2 = r_new * r_new, s = std::sqrt(r2);
+    // which old entries stay: a stored distance below the rounded root of r2 is a member, above it is not, on it decides nothing
+    auto kept = [&](int64_t x, int64_t e) {
+        if (nzval[e] < s) return true;
+        if (nzval[e] > s) return false;
+        return dist2(X + (size_t)x * d, X + (size_t)rowval[e] * d) <= r2;
+    };
+    // the near sets of the new samples among ALL samples, ascending, self excluded by index
+    struct ent { int32_t y; double d2; };
+    std::vector<std::vector<ent>> nn((size_t)n_add);
+    std::vector<int64_t> addcnt((size_t)N, 0);
+    for (int64_t j = 0; j < n_add; ++j) {
+        const int64_t v = N + j;
+        const double* q = X + (size_t)v * d;
+        for (int64_t y = 0; y < NN; ++y) {
+            if (y == v) continue;
+            ++info->candidates;
+            const double d2 = dist2(q, X + (size_t)y * d);
+            if (d2 <= r2) { nn[(size_t)j].push_back({(int32_t)y, d2}); if (y < N) addcnt[(size_t)y]++; }
+        }
+    }
+    out_colptr[0] = 0;
+    for (int64_t x = 0; x < NN; ++x) {
+        int64_t c;
+        if (x < N) {
+            c = addcnt[(size_t)x];
+            for (int64_t e = colptr[x]; e < colptr[x + 1]; ++e) { if (kept(x, e)) ++c; else ++info->dropped; }
+        } else c = (int64_t)nn[(size_t)(x - N)].size();
+        out_colptr[x + 1] = out_colptr[x] + c;
+    }
+    const int64_t nnz_new = out_colptr[NN];
+    *nnz_out = nnz_new;
+    for (int64_t j = 0; j < n_add; ++j) info->entries += (int64_t)nn[(size_t)j].size();
+    for (int64_t x = 0; x < N; ++x) info->entries += addcnt[(size_t)x];
+    if (cap == 0) return MPFMT_OK;                                       // the size query
+    if (nnz_new > cap) return MPFMT_ERR_CAPACITY;
+    for (int64_t w = 0; w < (nnz_new + 63) / 64; ++w) out_efree[w] = 0;
+    auto put = [&](int64_t o, int32_t y, double dist, bool fr) {
+        out_rowval[o] = y; out_nzval[o] = dist;
+        if (fr) out_efree[o >> 6] |= 1ull << (o & 63);
+    };
+    std::vector<int64_t> cur((size_t)N);
+    for (int64_t x = 0; x < N; ++x) {
+        int64_t o = out_colptr[x];
+        for (int64_t e = colptr[x]; e < colptr[x + 1]; ++e) if (kept(x, e)) put(o++, rowval[e], nzval[e], bitp(efree, e) != 0);
+        cur[(size_t)x] = o;
+    }
+    // new samples in ascending order: the rows appended to an old column ascend
+    for (int64_t j = 0; j < n_add; ++j) {
+        const int64_t v = N + j;
+        const double* q = X + (size_t)v * d;
+        int64_t o = out_colptr[v];
+        for (const ent& t : nn[(size_t)j]) {
+            const double* py = X + (size_t)t.y * d;
+            const double dist = std::sqrt(t.d2);
+            put(o++, t.y, dist, W.free(py, q));                          // entry (row y, column v): the motion y -> v
+            if (t.y < N) put(cur[(size_t)t.y]++, (int32_t)v, dist, W.free(q, py));
+        }
+    }
+    return MPFMT_OK;
+}

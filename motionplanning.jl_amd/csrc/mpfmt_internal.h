@@ -379,6 +379,16 @@ struct mpfmt_ctx {
     int32_t bd_path = 0;                 // 1: the resident mask was updated in place, 0: invalidated
     int64_t bd_columns = 0, bd_entries = 0;
 
+    // ---- growth of the sample set (mpfmt_samples_add, kernels_grow.hip): the grown graph is built in these spare buffers, which change
+    // places with colptr / rowval / nzval / graph_free once everything has succeeded (the ctx holds the graph twice at the peak)
+    mpfmt_dbuf<int64_t> colptr_next;
+    mpfmt_dbuf<int32_t> rowval_next;
+    mpfmt_dbuf<double> nzval_next;
+    mpfmt_dbuf<uint64_t> free_next;
+    mpfmt_dbuf<void> grow_counts, grow_lists, grow_bytes;      // the call's temporaries (grow-only): counters and offsets | the new samples' lists | one byte per grown entry
+    int32_t grow_path = 0;               // 1: the resident graph was grown in place, 0: invalidated
+    int64_t grow_candidates = 0, grow_entries = 0, grow_dropped = 0;      // stats of the last call
+
     // ---- scratch -------------------------------------------------------------------------------
     mpfmt_dbuf<void> scratch;
     std::map<std::string, mpfmt_timer> timers;
@@ -668,6 +678,12 @@ int32_t mpfmt_roadmap_goal(mpfmt_ctx* ctx, const mpfmt_rm_list& L, int64_t q, co
 int32_t mpfmt_steer_roadmap_lists(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, int dir, const uint64_t* d_F, mpfmt_rm_list* out,
                                   bool count_only, const double* d_X, int64_t nx, bool pair);
 int32_t mpfmt_steer_roadmap_reduce(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double* d_Q, int64_t nq, const double* d_C, double* d_cost, int64_t* d_parent);
+
+// kernels_grow.hip -----------------------------------------------------------------------------------
+// The ctx holds the grown sample set (N, Xo, bounding box) and, untouched, the swept graph of its first n_old samples: the graph and
+// mask of radius r_new over all N are built in the spare buffers and change places with the ctx's own.  An error return has changed
+// neither the graph's arrays nor its flags (the cell grid may be that of the grown set: the caller marks it stale).
+int32_t mpfmt_grow_apply(mpfmt_ctx* ctx, int64_t n_old, double r_new);
 
 // kernels_sssp_multi.hip ----------------------------------------------------------------------------
 // nsrc fields (sources 1-based, on the host) in groups of 64 over the resident graph and mask; C_host [nsrc][N], A_host [nsrc][N] or nullptr

@@ -429,12 +429,13 @@ class ImmutableNNC:
 class MetricNN:
     """SampleSet for symmetric distances (nearneighbors.jl:62-74); DS is the device context holding the samples."""
 
-    def __init__(self, V, dist, init, ctx=None):
+    def __init__(self, V, dist, init, ctx=None, upload=True):
         self.V = np.ascontiguousarray(np.atleast_2d(V), dtype=np.float64)
         self.dist, self.init = dist, np.asarray(init, dtype=np.float64)
         self.cache = None
         self.DS = ctx if ctx is not None else Context(0)     # helper_data_structures (geometric.jl:14)
-        self.DS.upload_samples(self.V)
+        if upload:                                           # (upload = False: the context holds these samples already -- grow_)
+            self.DS.upload_samples(self.V)
 
     def __len__(self):
         return len(self.V)
@@ -517,6 +518,12 @@ def sample_free_(P, N, ensure_goal=True, ensure_goal_ct=5, rng=None, seed=None):
                                  goal_params=P.goal.params(), goal_ct=ensure_goal_ct if ensure_goal else 0)
         P.V = addpoints(P.V, W)
         return volume(P.SS)
+    P.V = addpoints(P.V, _draw_free(P, N, ensure_goal, ensure_goal_ct, rng))
+    return volume(P.SS)
+
+
+def _draw_free(P, N, ensure_goal=True, ensure_goal_ct=5, rng=None):
+    """N free samples drawn the way sample_free_ draws them from `rng` (sampling.jl:11-45), not yet added to P.V."""
     W = np.empty((N, dim(P.SS)))
     have = 0
     if not (len(P.V.V) > 0 and np.array_equal(P.V.V[0], P.init)):
@@ -531,8 +538,26 @@ def sample_free_(P, N, ensure_goal=True, ensure_goal_ct=5, rng=None, seed=None):
     if ensure_goal:
         for i in range(1, min(ensure_goal_ct, N - 1) + 1):
             W[N - i] = sample_free_goal(P, rng)
-    P.V = addpoints(P.V, W)
-    return volume(P.SS)
+    return W
+
+
+def grow_(P, N, r=None, ensure_goal_ct=1, rng=None, seed=None):
+    """Refine a plan with more samples, as a second fmtstar!(P, N) does (fmt.jl:30: only N - length(P.V) new samples are drawn and
+    appended), WITHOUT the rebuild: the new samples are drawn like sample_free_'s, P.V is extended without the upload a new MetricNN
+    makes, and Context.samples_add installs them behind the resident ones -- a resident, swept r-disc graph follows in place
+    (P.ctx.stat("samples_add_path") == 1), so that a following prmstar_(P, r=r) / fmtstar_(P, r=r) plans on the grown graph with
+    neither pair phase nor sweep.  r = None keeps the graph's radius; a smaller r (the default rule shrinks it as N grows) drops the
+    entries beyond it.  seed seeds the generator when no rng is given.  Returns the number of samples added."""
+    n_add = int(N) - len(P.V)
+    if n_add <= 0:
+        return 0
+    if rng is None:
+        rng = np.random.default_rng(seed)
+    P.CC._bind(P.ctx, P.SS)
+    W = _draw_free(P, n_add, ensure_goal_ct=ensure_goal_ct, rng=rng)
+    P.ctx.samples_add(W, r=r)
+    P.V = MetricNN(np.concatenate([P.V.V, W]), P.V.dist, P.V.init, P.ctx, upload=False)
+    return n_add
 
 
 # ---- planner (src/planners/fmt.jl) -------------------------------------------------------------------------------------------------
