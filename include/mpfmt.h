@@ -349,7 +349,7 @@ MPFMT_API int32_t mpfmt_reedsshepp_prmstar(mpfmt_ctx* ctx, double turn_radius, d
  *      A TRACKED FIELD is (s, checkpts, C, A, Ab), held in buffers of its own that no other call writes: C and A are exactly what
  *      mpfmt_graph_sssp returns for s; Ab[x] is the entry index b of the parent edge A[x] -> x (undefined for the source and for
  *      unreached samples).
- *      The REPAIR runs after any sequence of in-place box edits (mpfmt_boxes_add / _remove, mixed):
+ *      The REPAIR runs after any sequence of in-place edits (mpfmt_boxes_add / _remove, mpfmt_shapes2d_add / _remove, mixed):
  *        1. F is recomputed when checkpts is set.
  *        2. Invalidate.  I0 = the x != s with C[x] < Inf for which mask bit Ab[x] is now clear, or checkpts is set and F[x] is clear.
  *           I = I0 plus every descendant of I0 in the parent forest A; C[x] = +Inf on I.  I is exactly this closure.
@@ -372,7 +372,8 @@ MPFMT_API int32_t mpfmt_reedsshepp_prmstar(mpfmt_ctx* ctx, double turn_radius, d
  * The field is dropped by new samples, a new graph (another r or k, an import), mpfmt_upload_boxes, mpfmt_upload_shapes2d,
  * mpfmt_set_state_bounds, mpfmt_set_shard and by destroying the ctx; mpfmt_field_update / _read / _goal then return MPFMT_ERR_STATE
  * until mpfmt_field_begin.  mpfmt_graph_sssp, mpfmt_prmstar and the roadmap queries keep scratch buffers of their own and leave it alone.
- * Unsharded ctx, Euclidean samples; the in-place edits are those of the AABB checker.
+ * Unsharded ctx, Euclidean samples; the in-place edits are those of the AABB checker (mpfmt_boxes_add / _remove) and of the 2-D SAT
+ * world (mpfmt_shapes2d_add / _remove, which flag their columns for the repair in the same way).
  * mpfmt_get_stat: "field_tracked", "field_update_path" (1 repaired, 0 recomputed), "field_invalidated" (|I|), "field_dirty_columns"
  * (|D|), "field_columns_read" (distinct columns whose entries the relaxation read, over all rounds), "field_column_visits" (the same
  * counted once per round), "field_entries_read", "field_rounds", "field_relaxations", "field_reached".
@@ -408,8 +409,9 @@ MPFMT_API int32_t mpfmt_host_field_repair(int64_t N, const int64_t* colptr, cons
  *      (G[x], x) among those with fl(G[x] + w_yx) == G[y].
  *      A TRACKED COST-TO-GO FIELD is (targets, checkpts, G, S), held in buffers of its own that no other call writes: G and S are
  *      exactly what mpfmt_graph_sssp_to returns for the targets.  It is admitted wherever mpfmt_graph_sssp_to is: r-disc, imported,
- *      k-nearest, double integrator, Dubins, Reeds-Shepp; unsharded ctx, not the 2-D SAT world.
- *      The REPAIR runs after any sequence of in-place box edits (mpfmt_boxes_add / _remove, mixed):
+ *      k-nearest, double integrator, Dubins, Reeds-Shepp; unsharded ctx; under the AABB checker or, on the Euclidean graphs, the 2-D
+ *      SAT world.
+ *      The REPAIR runs after any sequence of in-place edits (mpfmt_boxes_add / _remove, mpfmt_shapes2d_add / _remove, mixed):
  *        1. F is recomputed when checkpts is set (on a steering graph: the bitmap of the steering planners).
  *        2. Invalidate.  I0 = the non-target y with G[y] < Inf whose successor edge y -> S[y] is no longer usable: its mask bit is now
  *           clear, or checkpts is set and F[S[y]] is clear.  I = I0 plus every y whose successor chain passes through I0; G = +Inf on
@@ -894,6 +896,37 @@ MPFMT_API int32_t mpfmt_closeR(mpfmt_ctx* ctx, const double* P, int64_t n, const
 #define MPFMT_SHAPE_POLYGON 1
 MPFMT_API int32_t mpfmt_upload_shapes2d(mpfmt_ctx* ctx, int32_t n_shapes, const int32_t* kinds, const int32_t* nverts, const double* data,
                               const double* ss_lo, const double* ss_hi);
+/* ---- in-place edits of the 2-D SAT world's shape list (the counterpart of mpfmt_boxes_add / _remove, and what the
+ *      reference's addobstacle / addblocker(p, r) = Circle(p, r) of robots2D.jl:23-24 become on a resident roadmap).
+ *   mpfmt_shapes2d_add:    n_add shapes encoded as for mpfmt_upload_shapes2d and validated by the same constructors, appended behind
+ *                          the current list.
+ *   mpfmt_shapes2d_remove: ids 1-based, distinct; the remaining shapes keep their order.
+ * After either call the ctx is what mpfmt_upload_shapes2d(resulting list, same bounds) leaves -- the compound box recomputed from the
+ * resulting list -- except that a resident swept mask may follow in place (the table) and that the tracked fields (mpfmt_field_*,
+ * mpfmt_togo_*) are NOT dropped: on the in-place path they learn the columns the edit read and their update repairs; on the other
+ * path their delta history is lost and their update recomputes (path = 0) once the mask has been swept again.
+ * The bit of entry e (row y in column x, segment (v, w)) under list L with compound box B(L) is
+ *   in_ss(v) && ( gate(e, B(L)) || no S in L hits (v, w) ),   gate = the segment's box does not overlap B(L)
+ * and the gate is not inert in floating point (a circle can "hit" an endpoint one ulp outside its own box), so
+ *   add:    a free entry keeps its bit when gate(e, B') holds; else it is cleared when an added shape hits; else, when the compound
+ *           box changed and the old list was not empty, when gate(e, B) held and a shape of the old list hits.  Blocked entries stay.
+ *   remove: a blocked entry with in_ss(v) is set when gate(e, B') holds; else, when a removed shape hits it, it is evaluated again
+ *           against all that remains.  Free entries stay.  (An empty list: the gate always holds and nothing hits.)
+ * The mask is the one a whole sweep of the resulting list writes, bit for bit.
+ *   state at the call                                                                      | mask                 | "boxes_delta_path"
+ *   unsharded ctx, Euclidean graph (r-disc, imported, k-nearest) filled and swept, nnz > 0, | updated in place,    | 1
+ *   mask resident, no speculative step in flight                                           | "graph_swept" stays  |
+ *   anything else: no graph, unswept, nnz == 0, sharded, a step in flight, a steering graph | graph_swept = false, | 0
+ *   resident                                                                               | steer_swept = false  |
+ * If the update itself fails, the edited list stands and the graph is swept again.
+ * Refused, leaving the ctx as it was: NULL with a positive count, an id out of range or repeated, an invalid shape (radius, convexity,
+ * more than 16 vertices) (MPFMT_ERR_ARG); no shape world resident -- the AABB checker, or nothing uploaded
+ * (MPFMT_ERR_STATE).  A count of 0 succeeds and does nothing.
+ * mpfmt_get_stat: "boxes_delta_path", "boxes_delta_columns" (columns whose entries were read: sample within graph_r (1 + 1e-9) of a
+ * delta shape's box, or -- when the compound box changed -- outside the compound box of the smaller list; all columns of a k-nearest
+ * graph), "boxes_delta_entries" (entries that reached a shape test), "boxes" (the list length); timing key "shapes_delta". */
+MPFMT_API int32_t mpfmt_shapes2d_add(mpfmt_ctx* ctx, int32_t n_add, const int32_t* kinds, const int32_t* nverts, const double* data);
+MPFMT_API int32_t mpfmt_shapes2d_remove(mpfmt_ctx* ctx, const int64_t* ids, int32_t n_ids);
 /* The 2-D SAT world under a steering space (the notebook's double-integrator and Dubins examples, docs/MotionPlanning.ipynb cells 7-11:
  * PointRobot2D with DoubleIntegrator(2) / DubinsQuasiMetricSpace): upload the shapes (workspace bounds), then the state-space
  * bounds of the steering space (4 for the double integrator, 3 for SE2; src/statespaces.jl:29-34, in_state_space :150).  The

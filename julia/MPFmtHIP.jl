@@ -548,6 +548,29 @@ function hip_upload_shapes!(ctx::Ptr{Void}, parts::Vector, lo::Vector{Float64}, 
                    ctx, length(kinds), kinds, nverts, data, lo, hi))
 end
 
+# ---- the shape list edited in place (include/mpfmt.h, DESIGN.md 7o): what addobstacle(CC, o) / addblocker(CC, p, r) = Circle(p, r) of
+#      robots2D.jl:23-24 become on a resident roadmap -- the free-edge mask of a swept Euclidean graph follows in place and the tracked
+#      fields stay (hip_replan! / hip_togo_update! then repair).  ids are 1-based into the flat parts list.  The C caller that executes
+#      these calls with the same widths is tests/abi_c/abi_caller13.c. ----
+const sym_shapes2d_add = :mpfmt_shapes2d_add
+const sym_shapes2d_remove = :mpfmt_shapes2d_remove
+function hip_shapes_add!(ctx::Ptr{Void}, parts::Vector)
+    kinds = Int32[]; nverts = Int32[]; data = Float64[]
+    for s in parts
+        if isa(s, Circle)
+            push!(kinds, 0); push!(nverts, 0); append!(data, [s.c[1], s.c[2], s.r])
+        else
+            push!(kinds, 1); push!(nverts, length(s.points)); for p in s.points; append!(data, [p[1], p[2]]); end
+        end
+    end
+    chk(ctx, ccall((sym_shapes2d_add, libmpfmt), Int32, (Ptr{Void}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                   ctx, length(kinds), kinds, nverts, data))
+end
+hip_addblocker!(ctx::Ptr{Void}, p, r) = hip_shapes_add!(ctx, Any[Circle(p, r)])
+function hip_shapes_remove!(ctx::Ptr{Void}, ids::Vector{Int})
+    chk(ctx, ccall((sym_shapes2d_remove, libmpfmt), Int32, (Ptr{Void}, Ptr{Int64}, Int32), ctx, ids, length(ids)))
+end
+
 # ---- sample_free!(P, N) (sampling.jl:11-45): the rejection loop in device batches (counter-based stream, sequential semantics) ----
 function hip_sample_free!(ctx::Ptr{Void}, seed::UInt64, N::Int, init::Vector{Float64}, goal_kind::Int32, goal_params::Vector{Float64},
                           goal_ct::Int32)

@@ -199,6 +199,8 @@ SYMBOLS = [
     ("mpfmt_closeR", C.c_int32, [C.c_void_p, c_d_p, C.c_int64, c_d_p, C.c_double, c_i64_p, C.c_int64, c_i64_p, c_d_p, c_d_p,
                                  c_i64_p, c_i64_p]),
     ("mpfmt_upload_shapes2d", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_d_p, c_d_p, c_d_p]),
+    ("mpfmt_shapes2d_add", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_d_p]),
+    ("mpfmt_shapes2d_remove", C.c_int32, [C.c_void_p, c_i64_p, C.c_int32]),
     ("mpfmt_graph_import", C.c_int32, [C.c_void_p, C.c_double, c_i64_p, c_i64_p, c_d_p]),
     ("mpfmt_sample_free", C.c_int32, [C.c_void_p, C.c_uint64, C.c_int64, c_d_p, C.c_int32, c_d_p, C.c_int32, c_d_p, c_i64_p]),
     ("mpfmt_sample_free_biased", C.c_int32, [C.c_void_p, C.c_uint64, C.c_int64, c_d_p, C.c_int32, c_d_p, C.c_int32, C.c_double, c_d_p,
@@ -710,13 +712,36 @@ class Context:
         self._chk(self._L.mpfmt_steer_mask_read(self._h, _up(mask), nseg.ctypes.data_as(c_u8_p)))
         return mask[:nwords(n)], nseg[:n]
 
-    def upload_shapes2d(self, shapes, ss_lo=None, ss_hi=None):
-        """2-D SAT world: shapes = [("circle", (cx, cy), r) | ("polygon", [(x, y), ...]), ...] (a flat Compound2D)."""
+    @staticmethod
+    def _encode_shapes2d(shapes):
+        """(kinds, nverts, data) of a shape list as mpfmt_upload_shapes2d / mpfmt_shapes2d_add take them."""
         kinds = np.array([0 if s[0] == "circle" else 1 for s in shapes], dtype=np.int32)
         nv = np.array([0 if s[0] == "circle" else len(s[1]) for s in shapes], dtype=np.int32)
         parts = [np.array([s[1][0], s[1][1], s[2]], dtype=np.float64) if s[0] == "circle"
                  else np.ascontiguousarray(s[1], dtype=np.float64).reshape(-1) for s in shapes]
         data = np.concatenate(parts) if parts else np.zeros(1)
+        return kinds, nv, data
+
+    def shapes_add(self, shapes):
+        """Append shapes (the tuples of upload_shapes2d) to the uploaded 2-D SAT world in place (mpfmt_shapes2d_add): the free-edge mask
+        of a swept resident Euclidean graph is brought up to date instead of being thrown away (stat("boxes_delta_path") == 1), and
+        the tracked fields stay."""
+        shapes = list(shapes)
+        kinds, nv, data = self._encode_shapes2d(shapes)
+        i32 = C.POINTER(C.c_int32)
+        self._chk(self._L.mpfmt_shapes2d_add(self._h, len(shapes), kinds.ctypes.data_as(i32), nv.ctypes.data_as(i32), _dp(data)))
+        self._cc_epoch += 1
+
+    def shapes_remove(self, ids):
+        """Remove the shapes `ids` (1-based, distinct) from the uploaded 2-D SAT world in place (mpfmt_shapes2d_remove); the others
+        keep their order."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int64)
+        self._chk(self._L.mpfmt_shapes2d_remove(self._h, _ip(ids), ids.size))
+        self._cc_epoch += 1
+
+    def upload_shapes2d(self, shapes, ss_lo=None, ss_hi=None):
+        """2-D SAT world: shapes = [("circle", (cx, cy), r) | ("polygon", [(x, y), ...]), ...] (a flat Compound2D)."""
+        kinds, nv, data = self._encode_shapes2d(shapes)
         lo = None if ss_lo is None else np.ascontiguousarray(ss_lo, dtype=np.float64)
         hi = None if ss_hi is None else np.ascontiguousarray(ss_hi, dtype=np.float64)
         i32 = C.POINTER(C.c_int32)

@@ -23,7 +23,7 @@ static void extrema_on(const double (*pts)[2], int n, const double* ax, double* 
     out[0] = dmin; out[1] = dmax;
 }
 
-static int32_t build_shape(mpfmt_ctx* ctx, int idx, int32_t kind, int32_t n, const double* data, mpfmt_shape2d* S)
+int32_t mpfmt_build_shape2d(mpfmt_ctx* ctx, int idx, int32_t kind, int32_t n, const double* data, mpfmt_shape2d* S)
 {
     memset(S, 0, sizeof *S);
     S->kind = kind;
@@ -89,7 +89,7 @@ int32_t mpfmt_upload_shapes2d(mpfmt_ctx* ctx, int32_t n_shapes, const int32_t* k
     mpfmt_aabb2d box;
     box.xr[0] = box.yr[0] = INFINITY; box.xr[1] = box.yr[1] = -INFINITY;
     for (int i = 0; i < n_shapes; ++i) {
-        if ((rc = build_shape(ctx, i, kinds[i], nverts[i], p, &S[i]))) return rc;
+        if ((rc = mpfmt_build_shape2d(ctx, i, kinds[i], nverts[i], p, &S[i]))) return rc;
         p += (kinds[i] == MPFMT_SHAPE_CIRCLE) ? 3 : 2 * nverts[i];
         box.xr[0] = std::min(box.xr[0], S[i].xr[0]); box.xr[1] = std::max(box.xr[1], S[i].xr[1]);       // Compound2D ctor, SAT2D.jl:93-97
         box.yr[0] = std::min(box.yr[0], S[i].yr[0]); box.yr[1] = std::max(box.yr[1], S[i].yr[1]);
@@ -100,6 +100,7 @@ int32_t mpfmt_upload_shapes2d(mpfmt_ctx* ctx, int32_t n_shapes, const int32_t* k
     HIPCHK(ctx, hipMemcpyAsync(ctx->shapes2d, S.data(), sizeof(mpfmt_shape2d) * S.size(), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->M = n_shapes; ctx->dw = 2; ctx->have_boxes = true; ctx->cc_kind = 1; ctx->aabb2d = box;
+    ctx->shapes_host.assign(S.begin(), S.begin() + n_shapes);      // (a host copy: mpfmt_shapes2d_add / _remove assemble the edited list from it)
     ctx->ss.has = ss_lo ? 1 : 0;
     ctx->ss.d = ss_lo ? 2 : 0;
     for (int i = 0; i < MPFMT_MAX_DIM; ++i) { ctx->ss.lo[i] = -INFINITY; ctx->ss.hi[i] = INFINITY; }

@@ -370,9 +370,11 @@ struct mpfmt_ctx {
     bool have_boxes = false;
     int32_t cc_kind = 0;                 // collision checker: 0 = PointRobotNDBoxes, 1 = PointRobot2D (SAT)
     mpfmt_dbuf<mpfmt_shape2d> shapes2d;   // [M] when cc_kind == 1
+    std::vector<mpfmt_shape2d> shapes_host;      // the same on the host
     mpfmt_aabb2d aabb2d;                 // Compound2D bounding box
     mpfmt_ss ss;
-    // in-place edits of the box list (mpfmt_boxes_add / _remove, kernels_boxdelta.hip): the flagged columns, their count and the
+    // in-place edits of the box list (mpfmt_boxes_add / _remove, kernels_boxdelta.hip) and of the 2-D shape list (mpfmt_shapes2d_add /
+    // _remove, kernels_shapedelta.hip): the flagged columns, their count and the
     // entries tested (device), and the stats of the last call
     mpfmt_dbuf<int32_t> bd_cols;          // [N]
     mpfmt_dbuf<unsigned long long> bd_ctr; // [2] flagged columns, entries that reached an exact test
@@ -577,6 +579,8 @@ int32_t mpfmt_launch_points_free(mpfmt_ctx* ctx, const int64_t* d_idx1, int64_t 
 int32_t mpfmt_2d_launch_points(mpfmt_ctx* ctx, const double* X, const int64_t* idx1, int64_t n, uint64_t* d_mask);
 int32_t mpfmt_2d_launch_edges(mpfmt_ctx* ctx, const int64_t* s1, const int64_t* t1, const double* P, const double* Q, int64_t E, uint64_t* d_mask);
 int32_t mpfmt_2d_launch_graph(mpfmt_ctx* ctx);
+// the reference's shape constructors (kernels_sat2d.hip): Circle / convex Polygon from the ABI's encoding, refused as SAT2D.jl refuses
+int32_t mpfmt_build_shape2d(mpfmt_ctx* ctx, int idx, int32_t kind, int32_t n, const double* data, mpfmt_shape2d* S);
 int32_t mpfmt_launch_states_free(mpfmt_ctx* ctx, const double* d_P, int64_t n, uint64_t* d_mask);
 int32_t mpfmt_launch_edges_free(mpfmt_ctx* ctx, const int64_t* d_src1, const int64_t* d_dst1, int64_t E, uint64_t* d_mask);
 int32_t mpfmt_launch_motions_free(mpfmt_ctx* ctx, const double* d_P, const double* d_Q, int64_t n, uint64_t* d_mask);

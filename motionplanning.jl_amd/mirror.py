@@ -210,18 +210,35 @@ class PointRobot2D:
         self.count = 0
         self._ctx = None
         self._ss = None
+        self._bound = None                   # (parts and bounds, the context's checker epoch) of the last _bind
+
+    @staticmethod
+    def _key(parts, SS):
+        return (repr(parts), np.asarray(SS.lo, dtype=np.float64).tobytes(), np.asarray(SS.hi, dtype=np.float64).tobytes())
 
     def _bind(self, ctx, SS):
         if SS.workspace_dim != 2:
             raise ValueError("PointRobot2D needs a 2-D workspace")
-        ctx.upload_shapes2d(self.obstacles.parts(), SS.lo[:2], SS.hi[:2])
+        parts = self.obstacles.parts()
+        key = self._key(parts, SS)
+        # a list the context already holds is not uploaded again (an upload throws the resident free-edge mask and the tracked fields
+        # away); anything else that changed the context's checker since moved its epoch on
+        if self._ctx is ctx and self._bound == (key, ctx._cc_epoch):
+            self._ss = SS
+            return
+        ctx.upload_shapes2d(parts, SS.lo[:2], SS.hi[:2])
         if dim(SS) != 2:                                     # a steering space over the 2-D world (double integrator, SE2 cars)
             ctx.set_state_bounds(SS.lo, SS.hi)
         self._ctx, self._ss = ctx, SS
+        self._bound = (key, ctx._cc_epoch)
 
     def _bind_workspace(self, ctx, SS):
         ctx.upload_shapes2d(self.obstacles.parts(), None, None)
         self._ctx = None
+
+    def _edited(self, ctx):
+        """The list was edited in place on the bound context: what was bound is the new list."""
+        self._bound = (self._key(self.obstacles.parts(), self._ss), ctx._cc_epoch)
 
     def addobstacle(self, o):                                                 # robots2D.jl:23
         return PointRobot2D(Compound2D(self.obstacles, o))
@@ -231,19 +248,31 @@ class PointRobot2D:
 
 
 def _cc_bound_to(P):
-    """P.CC is a box checker whose list P.ctx holds right now (bound by _bind and untouched since)."""
+    """P.CC is a checker (boxes or 2-D shapes) whose list P.ctx holds right now (bound by _bind and untouched since)."""
     CC = P.CC
-    return (isinstance(CC, PointRobotNDBoxes) and CC._ctx is P.ctx and CC._ss is P.SS and CC._bound is not None
+    return (isinstance(CC, (PointRobotNDBoxes, PointRobot2D)) and CC._ctx is P.ctx and CC._ss is P.SS and CC._bound is not None
             and CC._bound[1] == P.ctx._cc_epoch)
 
 
 def addobstacle_(P, o):
     """In-place addobstacle (boxesND.jl): appends the box to P.CC.boxes; when P.CC is bound to P.ctx the context's list and the
     resident free-edge mask follow in place (Context.boxes_add), so the next solve on the same samples sweeps nothing again -- in the
-    Euclidean spaces and, mask and segment counts, in the double-integrator and car spaces (fmtstar_ with band=...)."""
+    Euclidean spaces and, mask and segment counts, in the double-integrator and car spaces (fmtstar_ with band=...).
+    On a PointRobot2D (robots2D.jl:23) o is a Circle, a Polygon or a Compound2D: its flattened parts go behind P.CC's parts, and the
+    context follows through Context.shapes_add (the mask of a Euclidean roadmap in place, the tracked fields kept)."""
     CC = P.CC
+    if isinstance(CC, PointRobot2D):
+        if not isinstance(o, (Circle, Polygon, Compound2D)):
+            raise TypeError("a PointRobot2D takes a Circle, a Polygon or a Compound2D")
+        bound = _cc_bound_to(P)
+        if bound:
+            P.ctx.shapes_add(o.parts())
+        CC.obstacles = Compound2D(CC.obstacles, o)
+        if bound:
+            CC._edited(P.ctx)
+        return P
     if not isinstance(CC, PointRobotNDBoxes):
-        raise TypeError("in-place obstacle edits are for PointRobotNDBoxes (the 2-D shape world is rebuilt: CC.addobstacle)")
+        raise TypeError("in-place obstacle edits are for PointRobotNDBoxes and PointRobot2D")
     o = o if isinstance(o, BoxBounds) else BoxBounds(o)
     bound = _cc_bound_to(P)
     if bound:
@@ -255,16 +284,32 @@ def addobstacle_(P, o):
 
 
 def addblocker_(P, v, r):
-    """In-place addblocker: the box [v - r, v + r] (boxesND.jl)."""
+    """In-place addblocker: the box [v - r, v + r] (boxesND.jl); on a PointRobot2D the Circle(v, r) (robots2D.jl:24)."""
+    if isinstance(P.CC, PointRobot2D):
+        return addobstacle_(P, Circle(v, r))
     v = np.asarray(v, dtype=np.float64)
     return addobstacle_(P, BoxBounds(v - r, v + r))
 
 
 def removeobstacle_(P, i):
-    """Remove box i (1-based, as the reference indexes CC.boxes) in place; see addobstacle_."""
+    """Remove box i (1-based, as the reference indexes CC.boxes) in place; see addobstacle_.  On a PointRobot2D i indexes the
+    flattened parts list."""
     CC = P.CC
+    if isinstance(CC, PointRobot2D):
+        parts = CC.obstacles.parts()
+        i = int(i)
+        if not 1 <= i <= len(parts):
+            raise IndexError("shape %d out of range 1..%d" % (i, len(parts)))
+        bound = _cc_bound_to(P)
+        if bound:
+            P.ctx.shapes_remove([i])
+        del parts[i - 1]
+        CC.obstacles = Compound2D([Circle(q[1], q[2]) if q[0] == "circle" else Polygon(q[1]) for q in parts])
+        if bound:
+            CC._edited(P.ctx)
+        return P
     if not isinstance(CC, PointRobotNDBoxes):
-        raise TypeError("in-place obstacle edits are for PointRobotNDBoxes")
+        raise TypeError("in-place obstacle edits are for PointRobotNDBoxes and PointRobot2D")
     i = int(i)
     if not 1 <= i <= len(CC.boxes):
         raise IndexError("box %d out of range 1..%d" % (i, len(CC.boxes)))
