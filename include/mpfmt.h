@@ -916,9 +916,28 @@ MPFMT_API int32_t mpfmt_upload_shapes2d(mpfmt_ctx* ctx, int32_t n_shapes, const 
  *   state at the call                                                                      | mask                 | "boxes_delta_path"
  *   unsharded ctx, Euclidean graph (r-disc, imported, k-nearest) filled and swept, nnz > 0, | updated in place,    | 1
  *   mask resident, no speculative step in flight                                           | "graph_swept" stays  |
+ *   option "steer_shapes_delta" = 1, unsharded ctx, steering graph (double integrator in    | mask and segment     | 1
+ *   R^4, Dubins, Reeds-Shepp) filled and swept, nnz > 0, mask and counts resident, state    | counts updated in    |
+ *   bounds unset or of the state's dimension (what the whole sweep accepts)                 | place, "steer_swept" |
+ *                                                                                          | stays                |
  *   anything else: no graph, unswept, nnz == 0, sharded, a step in flight, a steering graph | graph_swept = false, | 0
- *   resident                                                                               | steer_swept = false  |
+ *   resident without the option                                                            | steer_swept = false  |
  * If the update itself fails, the edited list stands and the graph is swept again.
+ * Under a steering graph an entry is walked over the segments between its collision waypoints, the state bounds checked
+ * before each; the walk is the whole sweep's own with a delta predicate in the place of the segment test:
+ *   add:    P_add(s) = gate(s, B') || ( no added shape hits s && !( the compound box changed, the old list was not empty, gate(s, B)
+ *           holds and a shape of the old list hits s ) );  free' = free && free under P_add, count' = min(count, count under P_add).
+ *           Every entry of a flagged column is walked: a blocked entry keeps its bit, but its count can drop.
+ *   remove: P_rem(s) = gate(s, B) || ( no removed shape hits s && !( the compound box changed or nothing remains, and nothing remains
+ *           or gate(s, B') holds ) );  a blocked entry whose walk under P_rem is not free is evaluated again from nothing against
+ *           what remains; nothing else changes.
+ * Mask words (the padding bits of the last word included) and segment counts are byte for byte those of the whole sweep of the
+ * resulting list; mpfmt_steer_mask_read reads them, the next mpfmt_*_fmtstar_wavefront on the same parameters builds and sweeps
+ * nothing, and a tracked cost-to-go field learns the flagged columns (mpfmt_togo_update repairs).  Flagged columns: the workspace
+ * position within the column's reach (double integrator: r (|v1| + r / sqrt(rho)) (1 + 1e-9) with v1 the column's velocity; cars:
+ * r (1 + 1e-6)) of a delta shape's box on both axes, or -- when the compound box changed
+ * and the smaller side's list is not empty -- not inside the smaller compound box shrunk by the reach on every side.
+ * "boxes_delta_entries" then counts the entries walked under the delta predicate; the timing key is "steer_delta".
  * Refused, leaving the ctx as it was: NULL with a positive count, an id out of range or repeated, an invalid shape (radius, convexity,
  * more than 16 vertices) (MPFMT_ERR_ARG); no shape world resident -- the AABB checker, or nothing uploaded
  * (MPFMT_ERR_STATE).  A count of 0 succeeds and does nothing.
@@ -1200,6 +1219,9 @@ MPFMT_API int32_t mpfmt_timing_get(mpfmt_ctx* ctx, const char* name, double* avg
  * built for the shard's tiles and their neighbour cells only; cell ids are block-major so that a shard is a compact block.
  * "wf_pos_space" (default 1): the device solve keeps its sets a second time by cell-sorted position from the SECOND solve on a graph on
  * (2: from the first, 0: never).
+ * "steer_shapes_delta" (default 0): 1 = mpfmt_shapes2d_add / _remove under a filled and swept steering graph bring its mask and
+ * segment counts up to date in place (the table at mpfmt_shapes2d_add) instead of invalidating them; the mask and counts
+ * any later sweep writes are the same whatever its value.  mpfmt_get_stat "steer_shapes_delta" reads it back.
  * Tuning knobs only: the graph and the masks are the same bit for bit whatever their values.
  * "debug_small_lists": test knob, shrinks the pending lists of the fused edge tests so that their overflow path runs. */
 MPFMT_API int32_t mpfmt_set_option(mpfmt_ctx* ctx, const char* name, int64_t value);

@@ -551,7 +551,11 @@ end
 # ---- the shape list edited in place (include/mpfmt.h, DESIGN.md 7o): what addobstacle(CC, o) / addblocker(CC, p, r) = Circle(p, r) of
 #      robots2D.jl:23-24 become on a resident roadmap -- the free-edge mask of a swept Euclidean graph follows in place and the tracked
 #      fields stay (hip_replan! / hip_togo_update! then repair).  ids are 1-based into the flat parts list.  The C caller that executes
-#      these calls with the same widths is tests/abi_c/abi_caller13.c. ----
+#      these calls with the same widths is tests/abi_c/abi_caller13.c.
+#      Under a swept steering graph (double integrator in R^4, Dubins, Reeds-Shepp over the shape world) the same two calls keep its
+#      mask and segment counts up to date in place once the ctx's option "steer_shapes_delta" is 1 (DESIGN.md 7p; default 0: the graph
+#      is swept again): mpfmt_set_option(ctx, "steer_shapes_delta", 1), widths (Ptr{Void}, Cstring, Int64) -> Int32, executed by
+#      tests/abi_c/abi_caller14.c.  This glue does not set it. ----
 const sym_shapes2d_add = :mpfmt_shapes2d_add
 const sym_shapes2d_remove = :mpfmt_shapes2d_remove
 function hip_shapes_add!(ctx::Ptr{Void}, parts::Vector)

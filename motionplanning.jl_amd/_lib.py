@@ -87,6 +87,7 @@ DISC_DT, DISC_N = 0, 1
 ROADMAP_SOLVED, ROADMAP_NO_PATH, ROADMAP_START_BLOCKED, ROADMAP_GOAL_BLOCKED = 0, 1, 2, 3
 WF_SINGLE, WF_EAGER, WF_LAZY = 1, 2, 4
 COMM_ID_BYTES = 128
+OPT_STEER_SHAPES_DELTA = "steer_shapes_delta"     # Context.set_option: shape edits under a swept steering graph in place (default 0)
 
 # every symbol include/mpfmt.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -725,7 +726,8 @@ class Context:
     def shapes_add(self, shapes):
         """Append shapes (the tuples of upload_shapes2d) to the uploaded 2-D SAT world in place (mpfmt_shapes2d_add): the free-edge mask
         of a swept resident Euclidean graph is brought up to date instead of being thrown away (stat("boxes_delta_path") == 1), and
-        the tracked fields stay."""
+        the tracked fields stay.  After set_option("steer_shapes_delta", 1) the same holds for the mask and segment counts of a swept
+        steering graph (double integrator in R^4, Dubins, Reeds-Shepp): steer_mask_read() gives the bytes of a whole sweep."""
         shapes = list(shapes)
         kinds, nv, data = self._encode_shapes2d(shapes)
         i32 = C.POINTER(C.c_int32)
@@ -1617,6 +1619,8 @@ class Context:
         return ms.value, n.value
 
     def set_option(self, name, value):
+        """mpfmt_set_option (include/mpfmt.h lists the options).  OPT_STEER_SHAPES_DELTA = 1: shapes_add / shapes_remove under a swept
+        steering graph (double integrator in R^4, Dubins, Reeds-Shepp) bring mask and segment counts up to date in place."""
         self._chk(self._L.mpfmt_set_option(self._h, name.encode(), int(value)))
 
     def stat(self, name):

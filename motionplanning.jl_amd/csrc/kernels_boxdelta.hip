@@ -271,3 +271,22 @@ int32_t mpfmt_boxdelta_apply(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, 
     ctx->bd_columns = (int64_t)h[0]; ctx->bd_entries = (int64_t)h[1];
     return MPFMT_OK;
 }
+
+// flag + update kernels of an in-place edit under a steering graph (`launch`, on ctx->stream) between the set-up of bd_cols / bd_ctr
+// and the read-back of the two counters; timing key "steer_delta".  Box edits: mpfmt_capi.hip; shape edits: kernels_shapedelta.hip.
+int32_t mpfmt_steer_delta_run(mpfmt_ctx* ctx, const std::function<int32_t()>& launch)
+{
+    int32_t rc;
+    if ((rc = mpfmt_side_join(ctx))) return rc;
+    if ((rc = ctx->bd_cols.ensure(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(ctx->N, 1)))) return rc;
+    if ((rc = ctx->bd_ctr.ensure(ctx, sizeof(unsigned long long) * 2))) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->bd_ctr, 0, sizeof(unsigned long long) * 2, ctx->stream));
+    mpfmt_timed tm(ctx);
+    if ((rc = launch())) return rc;
+    tm.end("steer_delta");
+    unsigned long long h[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(h, ctx->bd_ctr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->bd_columns = (int64_t)h[0]; ctx->bd_entries = (int64_t)h[1];
+    return MPFMT_OK;
+}

@@ -235,10 +235,11 @@ __device__ __forceinline__ bool in_ss3(const double* p, const mpfmt_ss& ss)
     return ok != 0;
 }
 
-// is_free_motion(v, w, CC, SS) over the reference's collision waypoints; *nseg = segment tests made (CC.count)
-template <int KIND>
+// is_free_motion(v, w, CC, SS) over the reference's collision waypoints; *nseg = segment tests made (CC.count).  seg is the segment
+// test under the shape world: the whole sweep's (seg_whole_2d) or a delta predicate of the in-place shape edits (steer_delta.h)
+template <int KIND, class SEG = seg_whole_2d>
 __device__ inline bool car_motion_free(const double* v0, const double* w, double rt, double sp, const mpfmt_ws2d& cc,
-                                       const mpfmt_ss& ss, int* nseg)
+                                       const mpfmt_ss& ss, int* nseg, const SEG seg = SEG())
 {
     car_step path[5];
     int L;
@@ -253,7 +254,7 @@ __device__ inline bool car_motion_free(const double* v0, const double* w, double
             if (!in_ss3(prev, ss)) ok = false;
             else {
                 ++cnt;                                     // boxesND.jl:26 / robots2D.jl:13: one count per segment asked for
-                const bool fr = cc.kind == 1 ? motion_free_2d(prev[0], prev[1], p[0], p[1], cc.shapes, cc.ns, cc.aabb)
+                const bool fr = cc.kind == 1 ? seg(prev[0], prev[1], p[0], p[1], cc)
                                              : seg_free_boxes2(prev[0], prev[1], p[0], p[1], cc.boxes, cc.M);
                 if (!fr) ok = false;
             }
@@ -418,6 +419,62 @@ __global__ __launch_bounds__(SD_THREADS) void k_car_delta(const double* __restri
                         nseg[e] = (uint8_t)min(sr, 255);
                     }
                 } else {
+                    const int old = (int)nseg[e];
+                    sd = min(sd, 255);
+                    if (sd < old) nseg[e] = (uint8_t)sd;
+                    change = isfree && !fd;
+                }
+            }
+            const unsigned long long ch = __ballot(change);
+            if (lane == 0 && ch) {
+                if (REMOVE) atomicOr(&mask[wd], ch); else atomicAnd(&mask[wd], ~ch);
+            }
+            tested_n += (unsigned long long)__popcll(__ballot(cand));
+        }
+    }
+    if (lane == 0 && tested_n) atomicAdd(ctr + 1, tested_n);
+}
+
+// ---- in-place shape edits under the 2-D SAT world (steer_delta.h) ------------------------------------------------------
+// The structure of k_car_delta; F(delta) is car_motion_free under the edit's delta predicate in the place of the segment test, and a
+// remove's candidates are evaluated again by the whole sweep's own call against what remains.  Shapes are read at wave-uniform
+// addresses as kernels_sat2d.hip reads them.  ctr[1] += entries whose walk under the delta predicate was evaluated.
+template <int KIND, bool REMOVE>
+__global__ __launch_bounds__(SD_THREADS) void k_car_sdelta(const double* __restrict__ X, const int64_t* __restrict__ colptr,
+                                                          const int32_t* __restrict__ rowval, const int32_t* __restrict__ cols,
+                                                          unsigned long long* __restrict__ ctr, sd_shapes_edit E, double rt, double sp,
+                                                          mpfmt_ss ss, unsigned long long* __restrict__ mask, uint8_t* __restrict__ nseg)
+{
+    mpfmt_ws2d cc;                                           // what remains (remove) -- kind 1 also routes the walk to the predicate
+    cc.kind = 1; cc.boxes = nullptr; cc.M = 0; cc.shapes = E.list; cc.ns = E.nl; cc.aabb = E.Bnew;
+    const int lane = threadIdx.x & 63;
+    const int64_t gwave = ((int64_t)blockIdx.x * SD_THREADS + threadIdx.x) >> 6;
+    const int64_t nwaves = (int64_t)gridDim.x * (SD_THREADS / 64);
+    const int64_t ncols = (int64_t)ctr[0];
+    unsigned long long tested_n = 0;
+    for (int64_t ci = gwave; ci < ncols; ci += nwaves) {
+        const int64_t x = (int64_t)__builtin_amdgcn_readfirstlane(cols[ci]);
+        const int64_t beg = colptr[x], end = colptr[x + 1];
+        for (int64_t wd = beg >> 6; wd * 64 < end; ++wd) {
+            const int64_t e = wd * 64 + lane;
+            const unsigned long long cur = sd_word(mask, wd);
+            const bool mine = e >= beg && e < end;
+            const bool isfree = (cur >> lane) & 1ull;
+            const bool cand = REMOVE ? (mine && !isfree) : mine;
+            if (__ballot(cand) == 0) continue;
+            bool change = false;
+            if (cand) {
+                const int64_t y = rowval[e];
+                int sd = 0;
+                if (REMOVE) {
+                    const bool fd = car_motion_free<KIND>(X + 3 * y, X + 3 * x, rt, sp, cc, ss, &sd, seg_shapes_remove{E});
+                    if (!fd) {                                 // from nothing against what is left
+                        int sr = 0;
+                        change = car_motion_free<KIND>(X + 3 * y, X + 3 * x, rt, sp, cc, ss, &sr);
+                        nseg[e] = (uint8_t)min(sr, 255);
+                    }
+                } else {
+                    const bool fd = car_motion_free<KIND>(X + 3 * y, X + 3 * x, rt, sp, cc, ss, &sd, seg_shapes_add{E});
                     const int old = (int)nseg[e];
                     sd = min(sd, 255);
                     if (sd < old) nseg[e] = (uint8_t)sd;
@@ -612,6 +669,30 @@ int32_t mpfmt_car_delta_launch(mpfmt_ctx* ctx, const double* d_delta, int32_t nd
     if (ctx->steer_kind == MPFMT_STEER_REEDSSHEPP) { if (remove) CAR_DELTA_GO(2, true); else CAR_DELTA_GO(2, false); }
     else { if (remove) CAR_DELTA_GO(1, true); else CAR_DELTA_GO(1, false); }
 #undef CAR_DELTA_GO
+    HIPCHK(ctx, hipGetLastError());
+    return MPFMT_OK;
+}
+
+// the same for an edit of the shape list of the 2-D SAT world: d_delta = the nd shapes added (the tail of ctx->shapes2d) or a copy of
+// the nd shapes removed; Bold / M_before: the compound box and the list length before the edit
+int32_t mpfmt_car_sdelta_launch(mpfmt_ctx* ctx, const mpfmt_shape2d* d_delta, int32_t nd, bool remove, const mpfmt_aabb2d& Bold, int32_t M_before)
+{
+    const int64_t N = ctx->N;
+    sd_shapes_edit E;
+    int rule_b;
+    mpfmt_aabb2d small;
+    sd_shapes_edit_of(ctx, d_delta, nd, remove, Bold, M_before, E, rule_b, small);
+    const unsigned nbf = (unsigned)((N + SD_THREADS - 1) / SD_THREADS), nbu = sd_update_blocks(ctx);
+    const double rpad = ctx->steer_r * (1.0 + 1e-6) + 1e-300;
+    unsigned long long* mask = (unsigned long long*)ctx->graph_free.get();
+    hipLaunchKernelGGL((k_sd_flag_shapes<3, false>), dim3(nbf), dim3(SD_THREADS), 0, ctx->stream, ctx->Xo, N, d_delta, (int)nd, rpad, 0.0, rule_b,
+                       small, ctx->bd_cols, ctx->bd_ctr);
+#define CAR_SDELTA_GO(KIND, REM)                                                                                                      \
+    hipLaunchKernelGGL((k_car_sdelta<KIND, REM>), dim3(nbu), dim3(SD_THREADS), 0, ctx->stream, ctx->Xo, ctx->colptr, ctx->rowval, ctx->bd_cols, \
+                       ctx->bd_ctr, E, ctx->car_rt, ctx->car_sp, ctx->ss, mask, ctx->steer_nseg)
+    if (ctx->steer_kind == MPFMT_STEER_REEDSSHEPP) { if (remove) CAR_SDELTA_GO(2, true); else CAR_SDELTA_GO(2, false); }
+    else { if (remove) CAR_SDELTA_GO(1, true); else CAR_SDELTA_GO(1, false); }
+#undef CAR_SDELTA_GO
     HIPCHK(ctx, hipGetLastError());
     return MPFMT_OK;
 }

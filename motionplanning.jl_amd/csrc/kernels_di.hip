@@ -275,10 +275,11 @@ __device__ __forceinline__ bool ws_point_in_ss(const double (&p)[2 * M], const m
 
 // One entry: the motion x0 -> x1 of duration t against nbox boxes at sbox ([nbox][2 M], LDS or global) -- or, M == 2 and cc.kind == 1,
 // the 2-D SAT world.  Stages in the reference's order: bounds of waypoint q, boxes on segment q, q = 0..3; stops at the first that
-// fails.  segs = segment tests the reference would have counted.  The whole sweep and the in-place updates (steer_delta.h) run THIS.
-template <int M>
+// fails.  segs = segment tests the reference would have counted.  The whole sweep and the in-place updates (steer_delta.h) run THIS;
+// seg is the segment test under the shape world: the whole sweep's (seg_whole_2d) or a delta predicate of the in-place shape edits.
+template <int M, class SEG = seg_whole_2d>
 __device__ __forceinline__ bool di_motion_free(const double (&x0)[2 * M], const double (&x1)[2 * M], const double t, const double* sbox,
-                                               const int nbox, const mpfmt_ss& ss, const mpfmt_ws2d& cc, int& segs)
+                                               const int nbox, const mpfmt_ss& ss, const mpfmt_ws2d& cc, int& segs, const SEG seg = SEG())
 {
     constexpr int NS = 2 * M;
     double wp[NS], wn[NS];
@@ -299,7 +300,7 @@ __device__ __forceinline__ bool di_motion_free(const double (&x0)[2 * M], const 
             h[i] = (pv[i] < pw[i]) ? pw[i] : pv[i];
         }
         if constexpr (M == 2) {
-            if (cc.kind == 1 && !motion_free_2d(pv[0], pv[1], pw[0], pw[1], cc.shapes, cc.ns, cc.aabb)) fr = false;      // robots2D.jl:13-14
+            if (cc.kind == 1 && !seg(pv[0], pv[1], pw[0], pw[1], cc)) fr = false;      // robots2D.jl:13-14
         }
         for (int k = 0; k < nbox && fr; ++k) {
             // box in registers, comparisons combined without control flow (an LDS operand behind && / || becomes
@@ -427,6 +428,69 @@ __global__ __launch_bounds__(SD_THREADS) void k_di_delta(const double* __restric
                         nseg[e] = (uint8_t)sr;
                     }
                 } else {
+                    const int old = (int)nseg[e];
+                    if (sd < old) nseg[e] = (uint8_t)sd;
+                    change = isfree && !fd;
+                }
+            }
+            const unsigned long long ch = __ballot(change);
+            if (lane == 0 && ch) {
+                if (REMOVE) atomicOr(&mask[wd], ch); else atomicAnd(&mask[wd], ~ch);
+            }
+            tested_n += (unsigned long long)__popcll(__ballot(cand));
+        }
+    }
+    if (lane == 0 && tested_n) atomicAdd(ctr + 1, tested_n);
+}
+
+// ---- in-place shape edits under the 2-D SAT world (steer_delta.h): workspace dim 2 ------------------------------------
+// The structure of k_di_delta; F(delta) is di_motion_free under the edit's delta predicate in the place of the segment test, and a
+// remove's candidates are evaluated again by the whole sweep's own call against what remains.  Shapes are read at wave-uniform
+// addresses as kernels_sat2d.hip reads them.  ctr[1] += entries whose walk under the delta predicate was evaluated.
+template <bool REMOVE>
+__global__ __launch_bounds__(SD_THREADS) void k_di_sdelta(const double* __restrict__ X, const int64_t* __restrict__ colptr,
+                                                         const int32_t* __restrict__ rowval, const double* __restrict__ tval,
+                                                         const int32_t* __restrict__ cols, unsigned long long* __restrict__ ctr,
+                                                         sd_shapes_edit E, mpfmt_ss ss, unsigned long long* __restrict__ mask,
+                                                         uint8_t* __restrict__ nseg)
+{
+    mpfmt_ws2d cc;                                           // what remains (remove) -- kind 1 also routes the walk to the predicate
+    cc.kind = 1; cc.boxes = nullptr; cc.M = 0; cc.shapes = E.list; cc.ns = E.nl; cc.aabb = E.Bnew;
+    const int lane = threadIdx.x & 63;
+    const int64_t gwave = ((int64_t)blockIdx.x * SD_THREADS + threadIdx.x) >> 6;
+    const int64_t nwaves = (int64_t)gridDim.x * (SD_THREADS / 64);
+    const int64_t ncols = (int64_t)ctr[0];
+    unsigned long long tested_n = 0;
+    for (int64_t ci = gwave; ci < ncols; ci += nwaves) {
+        const int64_t x = (int64_t)__builtin_amdgcn_readfirstlane(cols[ci]);
+        const int64_t beg = colptr[x], end = colptr[x + 1];
+        double x1[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x1[i] = X[x * 4 + i];
+        for (int64_t wd = beg >> 6; wd * 64 < end; ++wd) {
+            const int64_t e = wd * 64 + lane;
+            const unsigned long long cur = sd_word(mask, wd);
+            const bool mine = e >= beg && e < end;
+            const bool isfree = (cur >> lane) & 1ull;
+            const bool cand = REMOVE ? (mine && !isfree) : mine;
+            if (__ballot(cand) == 0) continue;
+            bool change = false;
+            if (cand) {
+                const int64_t y = rowval[e];
+                const double t = tval[e];
+                double x0[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) x0[i] = X[y * 4 + i];
+                int sd = 0;
+                if (REMOVE) {
+                    const bool fd = di_motion_free<2>(x0, x1, t, nullptr, 0, ss, cc, sd, seg_shapes_remove{E});
+                    if (!fd) {                                 // from nothing against what is left
+                        int sr = 0;
+                        change = di_motion_free<2>(x0, x1, t, nullptr, 0, ss, cc, sr);
+                        nseg[e] = (uint8_t)sr;
+                    }
+                } else {
+                    const bool fd = di_motion_free<2>(x0, x1, t, nullptr, 0, ss, cc, sd, seg_shapes_add{E});
                     const int old = (int)nseg[e];
                     if (sd < old) nseg[e] = (uint8_t)sd;
                     change = isfree && !fd;
@@ -761,6 +825,31 @@ int32_t mpfmt_di_delta_launch(mpfmt_ctx* ctx, const double* d_delta, int32_t nd,
             hipLaunchKernelGGL((k_di_delta<DM, false>), dim3(nbu), dim3(SD_THREADS), lds, ctx->stream, ctx->Xo, ctx->colptr, ctx->rowval, ctx->tval,
                                ctx->bd_cols, ctx->bd_ctr, d_delta, (int)nd, (const double*)nullptr, 0, ctx->ss, mask, ctx->steer_nseg);
     });
+    HIPCHK(ctx, hipGetLastError());
+    return MPFMT_OK;
+}
+
+// the same for an edit of the shape list of the 2-D SAT world (states in R^4): d_delta = the nd shapes added (the tail of
+// ctx->shapes2d) or a copy of the nd shapes removed; Bold / M_before: the compound box and the list length before the edit
+int32_t mpfmt_di_sdelta_launch(mpfmt_ctx* ctx, const mpfmt_shape2d* d_delta, int32_t nd, bool remove, const mpfmt_aabb2d& Bold, int32_t M_before)
+{
+    if (ctx->d != 4) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the in-place shape edit needs double-integrator states in R^4");
+    const int64_t N = ctx->N;
+    sd_shapes_edit E;
+    int rule_b;
+    mpfmt_aabb2d small;
+    sd_shapes_edit_of(ctx, d_delta, nd, remove, Bold, M_before, E, rule_b, small);
+    const unsigned nbf = (unsigned)((N + SD_THREADS - 1) / SD_THREADS), nbu = sd_update_blocks(ctx);
+    const double pad_a = ctx->steer_r, pad_b = ctx->steer_r / sqrt(ctx->di_rho);
+    unsigned long long* mask = (unsigned long long*)ctx->graph_free.get();
+    hipLaunchKernelGGL((k_sd_flag_shapes<4, true>), dim3(nbf), dim3(SD_THREADS), 0, ctx->stream, ctx->Xo, N, d_delta, (int)nd, pad_a, pad_b, rule_b,
+                       small, ctx->bd_cols, ctx->bd_ctr);
+    if (remove)
+        hipLaunchKernelGGL((k_di_sdelta<true>), dim3(nbu), dim3(SD_THREADS), 0, ctx->stream, ctx->Xo, ctx->colptr, ctx->rowval, ctx->tval,
+                           ctx->bd_cols, ctx->bd_ctr, E, ctx->ss, mask, ctx->steer_nseg);
+    else
+        hipLaunchKernelGGL((k_di_sdelta<false>), dim3(nbu), dim3(SD_THREADS), 0, ctx->stream, ctx->Xo, ctx->colptr, ctx->rowval, ctx->tval,
+                           ctx->bd_cols, ctx->bd_ctr, E, ctx->ss, mask, ctx->steer_nseg);
     HIPCHK(ctx, hipGetLastError());
     return MPFMT_OK;
 }

@@ -228,11 +228,38 @@ static bool shapes_delta_in_place(const mpfmt_ctx* ctx)
            ctx->graph_free && ctx->step_state != 1;
 }
 
+// the same for a resident, swept steering graph (double integrator in R^4, cars) when the ctx opted in (option "steer_shapes_delta"):
+// mask and segment counts follow (steer_delta.h).  The conditions are those under which the space's whole sweep would
+// accept the resulting list.
+static bool steer_shapes_delta_in_place(const mpfmt_ctx* ctx)
+{
+    if (!(ctx->steer_shapes_delta && ctx->world == 1 && ctx->cc_kind == 1 && ctx->dw == 2 && ctx->steer_filled && ctx->steer_swept && ctx->nnz > 0 &&
+          ctx->graph_free && ctx->steer_nseg))
+        return false;
+    if (ctx->steer_kind == MPFMT_STEER_DI) return ctx->d == 4 && (!ctx->ss.has || ctx->ss.d == 4);
+    return ctx->d == 3 && (!ctx->ss.has || ctx->ss.d == 3);
+}
+
+static int32_t steer_shapedelta_apply(mpfmt_ctx* ctx, const mpfmt_shape2d* d_delta, int32_t nd, bool remove, const mpfmt_aabb2d& Bold, int32_t M_before)
+{
+    return mpfmt_steer_delta_run(ctx, [&]() {
+        return ctx->steer_kind == MPFMT_STEER_DI ? mpfmt_di_sdelta_launch(ctx, d_delta, nd, remove, Bold, M_before)
+                                                 : mpfmt_car_sdelta_launch(ctx, d_delta, nd, remove, Bold, M_before);
+    });
+}
+
 // the list has been edited: the mask follows in place or goes stale, as after an upload
 static int32_t shapes_delta_finish(mpfmt_ctx* ctx, const mpfmt_shape2d* d_delta, int32_t nd, bool remove, const mpfmt_aabb2d& Bold, int32_t M_before)
 {
     ctx->bd_columns = ctx->bd_entries = 0;
     ctx->pend_valid = false;
+    if (steer_shapes_delta_in_place(ctx)) {                  // (a steering graph is resident: the Euclidean graph state is not)
+        ctx->bd_path = 1;
+        ctx->graph_swept = false;
+        const int32_t rc = steer_shapedelta_apply(ctx, d_delta, nd, remove, Bold, M_before);
+        if (rc) { ctx->steer_swept = false; ctx->bd_path = 0; return rc; }   // (the list stands, the mask is swept again)
+        return mpfmt_togo_mark_dirty(ctx);                   // (a tracked cost-to-go field learns which columns the edit read)
+    }
     ctx->bd_path = shapes_delta_in_place(ctx) ? 1 : 0;
     ctx->steer_swept = false;
     if (!ctx->bd_path) { ctx->graph_swept = false; return MPFMT_OK; }

@@ -517,20 +517,9 @@ static bool steer_delta_in_place(const mpfmt_ctx* ctx)
 
 static int32_t steer_delta_apply(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove)
 {
-    int32_t rc;
-    if ((rc = mpfmt_side_join(ctx))) return rc;
-    if ((rc = ctx->bd_cols.ensure(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(ctx->N, 1)))) return rc;
-    if ((rc = ctx->bd_ctr.ensure(ctx, sizeof(unsigned long long) * 2))) return rc;
-    HIPCHK(ctx, hipMemsetAsync(ctx->bd_ctr, 0, sizeof(unsigned long long) * 2, ctx->stream));
-    mpfmt_timed tm(ctx);
-    rc = ctx->steer_kind == MPFMT_STEER_DI ? mpfmt_di_delta_launch(ctx, d_delta, nd, remove) : mpfmt_car_delta_launch(ctx, d_delta, nd, remove);
-    if (rc) return rc;
-    tm.end("steer_delta");
-    unsigned long long h[2] = {0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(h, ctx->bd_ctr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->bd_columns = (int64_t)h[0]; ctx->bd_entries = (int64_t)h[1];
-    return MPFMT_OK;
+    return mpfmt_steer_delta_run(ctx, [&]() {
+        return ctx->steer_kind == MPFMT_STEER_DI ? mpfmt_di_delta_launch(ctx, d_delta, nd, remove) : mpfmt_car_delta_launch(ctx, d_delta, nd, remove);
+    });
 }
 
 // the list has been edited: the mask follows in place (delta = the boxes added or a copy of those removed) or goes stale
@@ -2802,6 +2791,7 @@ int32_t mpfmt_set_option(mpfmt_ctx* ctx, const char* name, int64_t value)
     }
     if (strcmp(name, "di_path") == 0) { ctx->di_path = (int32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 2); ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false; return MPFMT_OK; }
     if (strcmp(name, "wf_force_sharded") == 0) { ctx->wf_force_sharded = value != 0; return MPFMT_OK; }
+    if (strcmp(name, "steer_shapes_delta") == 0) { ctx->steer_shapes_delta = value != 0; return MPFMT_OK; }
     return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown option %s", name);
 }
 
@@ -2887,6 +2877,7 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "discretize_steps") == 0) { *value = ctx->disc_steps; return MPFMT_OK; }
     if (strcmp(name, "discretize_samples") == 0) { *value = ctx->disc_samples; return MPFMT_OK; }
     if (strcmp(name, "steer_swept") == 0) { *value = (ctx->steer_filled && ctx->steer_swept) ? 1 : 0; return MPFMT_OK; }
+    if (strcmp(name, "steer_shapes_delta") == 0) { *value = ctx->steer_shapes_delta; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_path") == 0) { *value = ctx->bd_path; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_columns") == 0) { *value = ctx->bd_columns; return MPFMT_OK; }
     if (strcmp(name, "boxes_delta_entries") == 0) { *value = ctx->bd_entries; return MPFMT_OK; }

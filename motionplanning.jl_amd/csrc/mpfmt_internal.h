@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cmath>
+#include <functional>
 #include <string>
 #include <map>
 #include <utility>
@@ -356,6 +357,7 @@ struct mpfmt_ctx {
     int64_t di_pool_cap = 0; bool di_pool_valid = false;
     mpfmt_dbuf<void> di_ops;              // matrix-core prefilter of the double-integrator build (kernels_di_mfma.hip): target- and source-role operands
     bool di_mf = false; float di_negT = 0.f;     // the counted DI graph went through it; its threshold
+    int32_t steer_shapes_delta = 0;      // option: 1 = shape edits under a swept steering graph update mask and counts in place
     int32_t di_path = 0;                 // option: 0 auto, 1 vector-ALU candidate test, 2 matrix-core prefilter
     double car_rt = 1.0, car_sp = 1.0;   // Dubins turning radius / speed of the built graph
     mpfmt_dbuf<uint64_t> car_keep;        // keep bits over the candidate (positions) graph
@@ -597,6 +599,10 @@ int32_t mpfmt_boxdelta_apply(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, 
 // the same for a resident, swept steering graph (steer_delta.h): mask AND segment counts; flag + update launched on ctx->stream
 int32_t mpfmt_di_delta_launch(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove);      // kernels_di.hip
 int32_t mpfmt_car_delta_launch(mpfmt_ctx* ctx, const double* d_delta, int32_t nd, bool remove);     // kernels_car.hip
+int32_t mpfmt_steer_delta_run(mpfmt_ctx* ctx, const std::function<int32_t()>& launch);             // kernels_boxdelta.hip: set-up, launch, counters
+// the same for an edit of the shape list of the 2-D SAT world (option "steer_shapes_delta"): Bold / M_before describe the list before it
+int32_t mpfmt_di_sdelta_launch(mpfmt_ctx* ctx, const mpfmt_shape2d* d_delta, int32_t nd, bool remove, const mpfmt_aabb2d& Bold, int32_t M_before);
+int32_t mpfmt_car_sdelta_launch(mpfmt_ctx* ctx, const mpfmt_shape2d* d_delta, int32_t nd, bool remove, const mpfmt_aabb2d& Bold, int32_t M_before);
 bool mpfmt_di_sweep_fits(int64_t M, int m);              // M boxes of an m-dimensional workspace are within the whole sweep's LDS limit
 
 // kernels_di.hip ----------------------------------------------------------------------------------

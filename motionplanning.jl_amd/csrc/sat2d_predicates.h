@@ -88,6 +88,15 @@ __device__ __forceinline__ bool motion_free_2d(double vx, double vy, double wx, 
     return !hit;
 }
 
+// The segment test a steering sweep makes under the shape world (di_motion_free, car_motion_free), as a functor: the whole sweeps
+// run this one; the in-place shape edits (steer_delta.h) walk the same waypoints under their delta predicates.
+struct seg_whole_2d {
+    __device__ __forceinline__ bool operator()(double vx, double vy, double wx, double wy, const mpfmt_ws2d& cc) const
+    {
+        return motion_free_2d(vx, vy, wx, wy, cc.shapes, cc.ns, cc.aabb);
+    }
+};
+
 __device__ __forceinline__ bool in_ss_2d(double x, double y, const mpfmt_ss& ss)
 {
     if (!ss.has) return true;

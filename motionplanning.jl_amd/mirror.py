@@ -247,6 +247,62 @@ class PointRobot2D:
         return self.addobstacle(Circle(p, r))
 
 
+def _shape2d_fields(q):
+    """What the library's constructor keeps of one part (csrc/kernels_sat2d.hip, mpfmt_build_shape2d), in its order of operations."""
+    if q[0] == "circle":
+        cx, cy, r = float(q[1][0]), float(q[1][1]), float(q[2])
+        return dict(kind=0, c=(cx, cy), r=r, xr=(cx - r, cx + r), yr=(cy - r, cy + r))
+    pts = [(float(p[0]), float(p[1])) for p in q[1]]
+    n = len(pts)
+    area = 0.0
+    for i in range(n):
+        j = (i + 1) % n
+        t = (pts[j][0] - pts[i][0]) * (pts[j][1] + pts[i][1])
+        area = t if i == 0 else area + t
+    if area > 0:
+        pts = pts[::-1]
+    normals, nex = [], []
+    for i in range(n):
+        j = (i + 1) % n
+        ex, ey = pts[j][0] - pts[i][0], pts[j][1] - pts[i][1]
+        px, py = ey, -ex
+        nrm = math.sqrt(px * px + py * py)
+        normals.append((px / nrm, py / nrm))
+    for nx, ny in normals:
+        d = [p[0] * nx + p[1] * ny for p in pts]
+        nex.append((min(d), max(d)))
+    return dict(kind=1, normals=normals, nex=nex, xr=(min(p[0] for p in pts), max(p[0] for p in pts)),
+                yr=(min(p[1] for p in pts), max(p[1] for p in pts)))
+
+
+def points_free_shapes2d(P, parts):
+    """is_free_state(p, PointRobot2D) for the points P (n, 2) on the host: point_free_2d of csrc/sat2d_predicates.h (comparisons and
+    a few products, fp64, one rounded operation at a time), so the bits are those Context.states_free gives for the same list.  For the
+    point test of a steering problem, which must not touch the context's checker (an upload drops the swept mask)."""
+    P = np.asarray(P, dtype=np.float64)
+    L = [_shape2d_fields(q) for q in parts]
+    if not L:
+        B = (0.0, 0.0, 0.0, 0.0)                             # the stored box of an empty list
+    else:
+        B = (min(S["xr"][0] for S in L), max(S["xr"][1] for S in L), min(S["yr"][0] for S in L), max(S["yr"][1] for S in L))
+    px, py = P[:, 0], P[:, 1]
+    hit = np.zeros(len(P), dtype=bool)
+    for S in L:
+        if S["kind"] == 0:
+            tx, ty = px - S["c"][0], py - S["c"][1]
+            p, q = tx * tx, ty * ty
+            hit |= (p + q) <= S["r"] * S["r"]
+            continue
+        h = (S["xr"][0] <= px) & (px <= S["xr"][1]) & (S["yr"][0] <= py) & (py <= S["yr"][1])
+        for (nx, ny), (e0, e1) in zip(S["normals"], S["nex"]):
+            p, q = px * nx, py * ny
+            d = p + q
+            h &= ~((e0 <= d) & (d <= e1))
+        hit |= h
+    inbox = (B[0] <= px) & (px <= B[1]) & (B[2] <= py) & (py <= B[3])
+    return ~inbox | ~hit
+
+
 def _cc_bound_to(P):
     """P.CC is a checker (boxes or 2-D shapes) whose list P.ctx holds right now (bound by _bind and untouched since)."""
     CC = P.CC
@@ -254,18 +310,28 @@ def _cc_bound_to(P):
             and CC._bound[1] == P.ctx._cc_epoch)
 
 
+def _steer_shapes_in_place(P):
+    """A steering space over the 2-D shape world: shape edits keep the swept mask and counts of the context (option
+    "steer_shapes_delta", default off on a raw Context)."""
+    if dim(P.SS) != 2:
+        P.ctx.set_option(_lib.OPT_STEER_SHAPES_DELTA, 1)
+
+
 def addobstacle_(P, o):
     """In-place addobstacle (boxesND.jl): appends the box to P.CC.boxes; when P.CC is bound to P.ctx the context's list and the
     resident free-edge mask follow in place (Context.boxes_add), so the next solve on the same samples sweeps nothing again -- in the
     Euclidean spaces and, mask and segment counts, in the double-integrator and car spaces (fmtstar_ with band=...).
     On a PointRobot2D (robots2D.jl:23) o is a Circle, a Polygon or a Compound2D: its flattened parts go behind P.CC's parts, and the
-    context follows through Context.shapes_add (the mask of a Euclidean roadmap in place, the tracked fields kept)."""
+    context follows through Context.shapes_add (the mask of a Euclidean roadmap in place, the tracked fields kept; under a steering
+    space the mirror turns the context's option "steer_shapes_delta" on, so mask and segment counts of the swept steering graph follow
+    in place too)."""
     CC = P.CC
     if isinstance(CC, PointRobot2D):
         if not isinstance(o, (Circle, Polygon, Compound2D)):
             raise TypeError("a PointRobot2D takes a Circle, a Polygon or a Compound2D")
         bound = _cc_bound_to(P)
         if bound:
+            _steer_shapes_in_place(P)
             P.ctx.shapes_add(o.parts())
         CC.obstacles = Compound2D(CC.obstacles, o)
         if bound:
@@ -302,6 +368,7 @@ def removeobstacle_(P, i):
             raise IndexError("shape %d out of range 1..%d" % (i, len(parts)))
         bound = _cc_bound_to(P)
         if bound:
+            _steer_shapes_in_place(P)
             P.ctx.shapes_remove([i])
         del parts[i - 1]
         CC.obstacles = Compound2D([Circle(q[1], q[2]) if q[0] == "circle" else Polygon(q[1]) for q in parts])
@@ -324,7 +391,7 @@ def removeobstacle_(P, i):
 
 def _holds_swept_steering_graph(CC, SS, ctx):
     """ctx holds CC's list, bound with SS (nothing changed its checker since), and a swept steering graph."""
-    return (isinstance(CC, PointRobotNDBoxes) and CC._ctx is ctx and CC._ss is SS and CC._bound is not None
+    return (isinstance(CC, (PointRobotNDBoxes, PointRobot2D)) and CC._ctx is ctx and CC._ss is SS and CC._bound is not None
             and CC._bound[1] == getattr(ctx, "_cc_epoch", None) and hasattr(ctx, "stat") and ctx.stat("steer_swept") == 1)
 
 
@@ -341,6 +408,9 @@ def is_free_state(v, CC, SS, ctx):
             # binding the checker to the workspace alone and back is two uploads, and an upload throws away the swept mask that
             # boxes_add / boxes_remove keep up to date: the point test (comparisons only, k_points_free) is made here instead
             Pw = V[:, :SS.workspace_dim]
+            if isinstance(CC, PointRobot2D):
+                out = inb & points_free_shapes2d(Pw, CC.obstacles.parts())
+                return bool(out[0]) if np.ndim(v) == 1 else out
             out = inb.copy()
             for b in CC.boxes:
                 out &= np.any(~(b.lo <= Pw) | ~(Pw <= b.hi), axis=1)
