@@ -369,7 +369,8 @@ MPFMT_API int32_t mpfmt_reedsshepp_prmstar(mpfmt_ctx* ctx, double turn_radius, d
  *      path_len, nnz), collision_checks = 0; path has capacity N.  While box edits are pending (no mpfmt_field_update since) the
  *      field is that of the previous box set: MPFMT_ERR_STATE (mpfmt_field_read hands out the field as it was last valid).
  * mpfmt_field_drop   : forgets the field (always succeeds).
- * The field is dropped by new samples, a new graph (another r or k, an import), mpfmt_upload_boxes, mpfmt_upload_shapes2d,
+ * The field is dropped by new samples (mpfmt_samples_add carries it across an in-place growth once the ctx's option
+ * "samples_add_keeps_fields" is 1: "growing the sample set" below), a new graph (another r or k, an import), mpfmt_upload_boxes, mpfmt_upload_shapes2d,
  * mpfmt_set_state_bounds, mpfmt_set_shard and by destroying the ctx; mpfmt_field_update / _read / _goal then return MPFMT_ERR_STATE
  * until mpfmt_field_begin.  mpfmt_graph_sssp, mpfmt_prmstar and the roadmap queries keep scratch buffers of their own and leave it alone.
  * Unsharded ctx, Euclidean samples; the in-place edits are those of the AABB checker (mpfmt_boxes_add / _remove) and of the 2-D SAT
@@ -441,7 +442,13 @@ MPFMT_API int32_t mpfmt_host_field_repair(int64_t N, const int64_t* colptr, cons
  *      info->path = 0.  No swept mask for the resident graph and the current box set: MPFMT_ERR_STATE, the field stays tracked.
  * mpfmt_togo_read   : host copies of G[N] and S[N] (S may be NULL, and so may G): the field as it was last valid.
  * mpfmt_togo_drop   : forgets the field (always succeeds).
- * The field is dropped by new samples, another graph (another radius, k, steering space or steering parameters; an import),
+ * mpfmt_togo_targets_add : 1-based targets join the tracked set (duplicates and old targets allowed, ntgt = 0 legal and does
+ *      nothing).  Each is a label decrease: target bit, G = 0, S = 0, and the sample joins D, so it pushes in round 0 of the next
+ *      repair; the field's target list is extended (a recomputation, path = 0, starts from it).  Legal while box edits or a carried
+ *      growth are pending; the next mpfmt_togo_update yields the bytes of mpfmt_graph_sssp_to for the union of the targets.  An index
+ *      outside 1 .. N: MPFMT_ERR_ARG; no tracked field: MPFMT_ERR_STATE; a refusal leaves the field untouched.
+ * The field is dropped by new samples (mpfmt_samples_add carries it across an in-place growth of an r-disc graph once the ctx's option
+ * "samples_add_keeps_fields" is 1: "growing the sample set" below), another graph (another radius, k, steering space or steering parameters; an import),
  * mpfmt_upload_shapes2d, mpfmt_set_state_bounds, mpfmt_set_shard and by destroying the ctx: mpfmt_togo_update / _read then return
  * MPFMT_ERR_STATE until mpfmt_togo_begin.  mpfmt_upload_boxes replaces the list whole: the labels lose their history but the targets
  * stay, and after the whole sweep that such an upload needs mpfmt_togo_update recomputes (path = 0).  mpfmt_field_*,
@@ -469,6 +476,7 @@ typedef struct {
 MPFMT_API int32_t mpfmt_togo_begin(mpfmt_ctx* ctx, const int64_t* targets, int64_t ntgt, int32_t checkpts, mpfmt_togo_info* info);
 MPFMT_API int32_t mpfmt_togo_update(mpfmt_ctx* ctx, mpfmt_togo_info* info);
 MPFMT_API int32_t mpfmt_togo_read(mpfmt_ctx* ctx, double* G, int64_t* S);
+MPFMT_API int32_t mpfmt_togo_targets_add(mpfmt_ctx* ctx, const int64_t* targets, int64_t ntgt);
 MPFMT_API int32_t mpfmt_togo_drop(mpfmt_ctx* ctx);
 
 /* ---- roadmap queries for external states: start and goal states that are NOT samples (the robot's present pose, a batch of candidate
@@ -552,8 +560,29 @@ MPFMT_API int32_t mpfmt_host_roadmap_query(int64_t N, int32_t d, const double* X
  *      s = fl(sqrt(fl(r_new * r_new))) a stored distance < s is a member, > s is not, == s decides nothing and the entry's d2 is
  *      computed again from the coordinates.  An imported graph's distances are taken as given.
  *      Afterwards the ctx is in the state mpfmt_graph_import leaves plus a current swept mask: the radius is r_new, the cell grid
- *      is that of the grown set, a resident steering graph, a tracked field and a tracked cost-to-go are dropped (as new samples drop
- *      them); mpfmt_prmstar / mpfmt_fmtstar at r_new run without pair phase or sweep, mpfmt_boxes_add / _remove stay in place.
+ *      is that of the grown set, a resident steering graph is dropped, and so are a tracked field and a tracked cost-to-go (as new
+ *      samples drop them) unless the ctx opted in to carrying them -- option "samples_add_keeps_fields", below;
+ *      mpfmt_prmstar / mpfmt_fmtstar at r_new run without pair phase or sweep, mpfmt_boxes_add / _remove stay in place.
+ *      TRACKED FIELDS.  With mpfmt_set_option(ctx, "samples_add_keeps_fields", 1) (default 0) an in-place call CARRIES a
+ *      live tracked cost-to-come field and a live tracked cost-to-go field whose delta history stands (one that the next update would
+ *      recompute anyway is dropped): labels, parents and successors of the old samples are kept, the new samples get +Inf and none and
+ *      are no targets, the entry index of every parent edge is found again in the grown column, and the CHANGED COLUMNS -- every new
+ *      column, every old column that lost an entry to the radius rule or gained a row -- join the field's dirty set beside the
+ *      pending columns of earlier box or shape edits.  A parent edge that the smaller radius dropped counts as an edge that lost its
+ *      bit.  The field stays tracked, and mpfmt_field_update / mpfmt_togo_update then run the repair as after a box edit (path = 1):
+ *      C / A are byte for byte mpfmt_graph_sssp(source) on the grown graph, G / S byte for byte mpfmt_graph_sssp_to(targets), for any
+ *      interleaving of growths (radius kept or shrunk) with mpfmt_boxes_add / _remove, with or without checkpts.  Between a carried
+ *      growth and the next update mpfmt_field_read, mpfmt_field_goal and mpfmt_togo_read return MPFMT_ERR_STATE: the last valid
+ *      field has another length.  The carry writes spare buffers that change places with the tracked ones only when the whole call
+ *      has succeeded (footprint: each carried field twice at the peak); a refused call leaves both fields as they were.  On the
+ *      invalidating path both are dropped whatever the option.  New goal samples join a carried cost-to-go field through
+ *      mpfmt_togo_targets_add.
+ *      Measured on one MI355X (profiles/growfield_mi355x.json): at N = 1e6 in R^6, 100 new samples change 1 % of the
+ *      columns and mpfmt_samples_add + mpfmt_field_update cost 4.2 ms against 15.3 ms for mpfmt_samples_add + mpfmt_field_begin (3.7x;
+ *      the cost-to-go field of a ball of targets: 5.2 against 10.9 ms, 2.1x), at the radius kept or shrunk by the default rule
+ *      (3.1x / 1.9x); 1e4 new samples change 65-84 % of the columns and the two ways are level (1.04-1.18x); at n_add / N = 10 %
+ *      (N = 1e5) the repair is slower than the recomputation (0.87-0.99x).  Carrying pays up to n_add / N of about 0.1 % and is level at
+ *      1 %: the range in which growth itself pays; beyond that, leave the option at 0 and begin the fields again.
  *      ALL OR NOTHING: the grown arrays are built in spare buffers that change places with the ctx's own only when everything has
  *      succeeded.  Footprint: at the peak the ctx holds the graph twice (old and grown colptr / rowval / nzval / mask) plus one
  *      byte per grown entry and the new samples' lists (about 2 x 21 bytes per added entry); the spare buffers stay with the ctx.
@@ -564,8 +593,11 @@ MPFMT_API int32_t mpfmt_host_roadmap_query(int64_t N, int32_t d, const double* X
  *      non-identity workspace, r_new above the graph's radius): the samples are appended on the device and the ctx is what
  *      mpfmt_upload_samples of the concatenated set leaves.
  *      mpfmt_get_stat: "samples_add_path" (1 in place, 0 invalidated), "samples_add_candidates" (distances evaluated),
- *      "samples_add_entries" (entries added, both directions), "samples_add_dropped" (old entries the smaller radius removed);
- *      timing keys "samples_add_near", "samples_add_merge", "samples_add".
+ *      "samples_add_entries" (entries added, both directions), "samples_add_dropped" (old entries the smaller radius removed),
+ *      "samples_add_flagged_columns" (the changed columns of an in-place call: a function of the two graphs alone),
+ *      "samples_add_fields_carried" (bit 0: the cost-to-come field, bit 1: the cost-to-go field was carried by the last call),
+ *      "samples_add_keeps_fields" (the option, read back);
+ *      timing keys "samples_add_near", "samples_add_merge", "samples_add_carry", "samples_add".
  *      Meant for n_add well below N (a refinement step).  The merge moves the whole CSC once whatever n_add is; every new sample walks
  *      its 3^d cells of the grid on its own.  Measured on one MI355X (profiles/grow_mi355x.json): at N = 1e6 in R^6
  *      (nnz 1.1e8) 100 new samples cost 1.5 ms against 3.4 ms for the upload and step of the concatenated set, 1e4 cost the same as
@@ -1222,6 +1254,8 @@ MPFMT_API int32_t mpfmt_timing_get(mpfmt_ctx* ctx, const char* name, double* avg
  * "steer_shapes_delta" (default 0): 1 = mpfmt_shapes2d_add / _remove under a filled and swept steering graph bring its mask and
  * segment counts up to date in place (the table at mpfmt_shapes2d_add) instead of invalidating them; the mask and counts
  * any later sweep writes are the same whatever its value.  mpfmt_get_stat "steer_shapes_delta" reads it back.
+ * "samples_add_keeps_fields" (default 0): 1 = an in-place mpfmt_samples_add / _device carries the tracked cost-to-come and cost-to-go
+ * fields instead of dropping them ("growing the sample set"); graph and mask are the same whatever its value.
  * Tuning knobs only: the graph and the masks are the same bit for bit whatever their values.
  * "debug_small_lists": test knob, shrinks the pending lists of the fused edge tests so that their overflow path runs. */
 MPFMT_API int32_t mpfmt_set_option(mpfmt_ctx* ctx, const char* name, int64_t value);

@@ -88,6 +88,7 @@ ROADMAP_SOLVED, ROADMAP_NO_PATH, ROADMAP_START_BLOCKED, ROADMAP_GOAL_BLOCKED = 0
 WF_SINGLE, WF_EAGER, WF_LAZY = 1, 2, 4
 COMM_ID_BYTES = 128
 OPT_STEER_SHAPES_DELTA = "steer_shapes_delta"     # Context.set_option: shape edits under a swept steering graph in place (default 0)
+OPT_SAMPLES_ADD_KEEPS_FIELDS = "samples_add_keeps_fields"      # Context.set_option: an in-place samples_add carries the tracked fields (default 0)
 
 # every symbol include/mpfmt.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -150,6 +151,7 @@ SYMBOLS = [
     ("mpfmt_togo_begin", C.c_int32, [C.c_void_p, c_i64_p, C.c_int64, C.c_int32, C.POINTER(TogoInfo)]),
     ("mpfmt_togo_update", C.c_int32, [C.c_void_p, C.POINTER(TogoInfo)]),
     ("mpfmt_togo_read", C.c_int32, [C.c_void_p, c_d_p, c_i64_p]),
+    ("mpfmt_togo_targets_add", C.c_int32, [C.c_void_p, c_i64_p, C.c_int64]),
     ("mpfmt_togo_drop", C.c_int32, [C.c_void_p]),
     ("mpfmt_host_field_repair", C.c_int32, [C.c_int64, c_i64_p, C.POINTER(C.c_int32), c_d_p, c_u64_p, c_u64_p, c_u64_p, C.c_int64, c_d_p, c_i64_p,
                                             c_i64_p]),
@@ -641,7 +643,11 @@ class Context:
         """Append X_add (n_add, d) behind the ctx's samples (mpfmt_samples_add).  A resident, swept r-disc graph of an unsharded ctx
         with the N-D AABB checker follows in place -- graph and mask byte for byte those of a fresh step on the concatenated set at r
         (default: the graph's radius, r <= it) -- and stat("samples_add_path") == 1; in every other state the ctx is what upload_samples
-        of the concatenated set leaves (then r only has to be finite and positive)."""
+        of the concatenated set leaves (then r only has to be finite and positive).  The tracked fields are dropped, unless
+        set_option("samples_add_keeps_fields", 1) was given and the call went in place: then stat("samples_add_fields_carried") has
+        bit 0 (field) / bit 1 (cost-to-go) set, the fields stay tracked with the changed columns pending, field_update / togo_update
+        repair them (path 1) to the bytes of graph_sssp / graph_sssp_to on the grown graph, and field_read / field_goal / togo_read
+        raise ERR_STATE until that update."""
         X_add = np.ascontiguousarray(X_add, dtype=np.float64)
         if X_add.ndim == 1:
             X_add = X_add[None]
@@ -984,6 +990,13 @@ class Context:
         S = np.empty(max(self.N, 1), dtype=np.int64) if want_successors else None
         self._chk(self._L.mpfmt_togo_read(self._h, _dp(G), _ip(S)))
         return G[:self.N], (None if S is None else S[:self.N])
+
+    def togo_targets_add(self, targets):
+        """Add 1-based `targets` to the tracked cost-to-go field (mpfmt_togo_targets_add): label decreases that the next togo_update
+        pushes from, also while box edits or a carried growth are pending; the update then equals graph_sssp_to of the union.  An
+        index outside 1..N raises ERR_ARG, no tracked field ERR_STATE; a refusal leaves the field untouched."""
+        tg = np.ascontiguousarray(np.atleast_1d(np.asarray(targets, dtype=np.int64)))
+        self._chk(self._L.mpfmt_togo_targets_add(self._h, _ip(tg) if tg.size else None, int(tg.size)))
 
     def togo_drop(self):
         self._chk(self._L.mpfmt_togo_drop(self._h))

@@ -64,8 +64,8 @@ __global__ __launch_bounds__(256) void k_field_i0(int64_t N, int64_t words, int6
     const uint64_t dw = D[w];
     bool inv = false;
     if (x < N && ((dw >> lane) & 1ull) && x != src && C[x] < INFINITY) {
-        const int64_t b = Ab[x];
-        inv = !((efree[b >> 6] >> (b & 63)) & 1ull);
+        const int64_t b = Ab[x];                                               // (FIELD_AB_GONE: the radius rule of a growth dropped the parent edge)
+        inv = b < 0 || !((efree[b >> 6] >> (b & 63)) & 1ull);
         if (F && !((F[w] >> lane) & 1ull)) inv = true;
         if (inv) C[x] = INFINITY;
     }
@@ -172,6 +172,39 @@ __global__ __launch_bounds__(256) void k_field_parents(int64_t N, int64_t src, c
     parents_body<false, true>(N, src, colptr, rowval, nzval, efree, C, nullptr, A, Ab, &st->reached);
 }
 
+// The field follows a growth of the sample set (mpfmt_samples_add with option "samples_add_keeps_fields"), lane per sample
+// of the grown set, out of the tracked buffers into the spare ones.  Old samples keep label and parent; the entry index of the parent
+// edge is found again by binary search of row A[x] - 1 in the GROWN column x (strictly ascending rows; every entry index has moved), and
+// is FIELD_AB_GONE when the smaller radius dropped the entry -- column x lost an entry, so it is in `changed` and k_field_i0 takes it.
+// New samples: +Inf, no parent.  Threads [0, words) also lay the bitmaps again for words = ceil(N / 64): dirty = the pending bits of
+// earlier edits | the changed columns of the growth, the ring slots empty.
+#define FIELD_AB_GONE ((int64_t)-1)
+__global__ __launch_bounds__(256) void k_field_carry(int64_t n_old, int64_t N, int64_t words_old, int64_t words, const int64_t* __restrict__ colptr,
+                                                     const int32_t* __restrict__ rowval, const double* __restrict__ C, const int64_t* __restrict__ A,
+                                                     const uint64_t* __restrict__ D, const uint64_t* __restrict__ changed, double* __restrict__ Cn,
+                                                     int64_t* __restrict__ An, int64_t* __restrict__ Abn, uint64_t* __restrict__ bmn)
+{
+    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x < N) {
+        double c = INFINITY;
+        int64_t p = 0, b = FIELD_AB_GONE;
+        if (x < n_old) {
+            c = C[x]; p = A[x];
+            if (p > 0 && p <= n_old) {
+                int64_t lo = colptr[x], hi = colptr[x + 1];
+                const int64_t end = hi, y = p - 1;
+                while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if ((int64_t)rowval[mid] < y) lo = mid + 1; else hi = mid; }
+                if (lo < end && (int64_t)rowval[lo] == y) b = lo;
+            }
+        }
+        Cn[x] = c; An[x] = p; Abn[x] = b;
+    }
+    if (x < words) {
+        bmn[x] = (x < words_old ? D[x] : 0ull) | changed[x];
+        bmn[words + x] = 0ull; bmn[2 * words + x] = 0ull; bmn[3 * words + x] = 0ull;
+    }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 
 static int32_t field_buffers(mpfmt_ctx* ctx)
@@ -232,7 +265,7 @@ int32_t mpfmt_field_compute(mpfmt_ctx* ctx, int64_t source0, int32_t checkpts, c
     ctx->fld_source0 = source0; ctx->fld_checkpts = checkpts;
     ctx->fld_samples_epoch = ctx->samples_epoch; ctx->fld_graph_epoch = ctx->graph_epoch; ctx->fld_sweep_epoch = ctx->sweep_epoch;
     ctx->fld_graph_r = ctx->graph_r; ctx->fld_knn_k = ctx->knn_k;
-    ctx->fld_dirty_any = false;
+    ctx->fld_dirty_any = false; ctx->fld_grown = false;
     return MPFMT_OK;
 }
 
@@ -311,14 +344,42 @@ int32_t mpfmt_field_repair(mpfmt_ctx* ctx, const uint64_t* d_F, mpfmt_field_info
     float ms = 0.f;
     HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->sssp_ev[0], ctx->sssp_ev[1]));
     field_stats(ctx, sh, 1, ms, info);
-    ctx->fld_dirty_any = false;
+    ctx->fld_dirty_any = false; ctx->fld_grown = false;
     return MPFMT_OK;
+}
+
+// ctx->N is the grown size; the tracked buffers hold the field of the first n_old samples (fld_N == n_old, checked by the caller through
+// mpfmt_field_live before the sample set changed).  Nothing tracked is written: a failure leaves the field as it was.
+int32_t mpfmt_field_carry(mpfmt_ctx* ctx, int64_t n_old, const int64_t* colptr_new, const int32_t* rowval_new, const uint64_t* changed)
+{
+    const int64_t N = ctx->N, words = (N + 63) / 64, words_old = (n_old + 63) / 64;
+    int32_t rc;
+    if ((rc = ctx->fld_C_next.ensure(ctx, sizeof(double) * (size_t)N))) return rc;
+    if ((rc = ctx->fld_A_next.ensure(ctx, sizeof(int64_t) * (size_t)N))) return rc;
+    if ((rc = ctx->fld_Ab_next.ensure(ctx, sizeof(int64_t) * (size_t)N))) return rc;
+    if ((rc = ctx->fld_bm_next.ensure(ctx, sizeof(uint64_t) * 4 * (size_t)words))) return rc;
+    hipLaunchKernelGGL(k_field_carry, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, n_old, N, words_old, words, colptr_new, rowval_new,
+                       (const double*)ctx->fld_C.get(), (const int64_t*)ctx->fld_A.get(), (const uint64_t*)ctx->fld_bm.get(), changed,
+                       ctx->fld_C_next.get(), ctx->fld_A_next.get(), ctx->fld_Ab_next.get(), ctx->fld_bm_next.get());
+    HIPCHK(ctx, hipGetLastError());
+    return MPFMT_OK;
+}
+
+// after the growth has succeeded (the ctx's epochs are those of the grown graph): the field is the ctx's again, with columns pending
+void mpfmt_field_carry_commit(mpfmt_ctx* ctx)
+{
+    ctx->fld_C.swap(ctx->fld_C_next); ctx->fld_A.swap(ctx->fld_A_next); ctx->fld_Ab.swap(ctx->fld_Ab_next); ctx->fld_bm.swap(ctx->fld_bm_next);
+    ctx->fld_N = ctx->N;
+    ctx->fld_samples_epoch = ctx->samples_epoch; ctx->fld_graph_epoch = ctx->graph_epoch; ctx->fld_sweep_epoch = ctx->sweep_epoch;
+    ctx->fld_graph_r = ctx->graph_r;
+    ctx->fld_dirty_any = true; ctx->fld_grown = true;
 }
 
 void mpfmt_field_drop_internal(mpfmt_ctx* ctx)
 {
     ctx->fld_tracked = false;
     ctx->fld_dirty_any = false;
+    ctx->fld_grown = false;
     ctx->fld_source0 = -1;
 }
 

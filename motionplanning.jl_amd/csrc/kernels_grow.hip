@@ -17,7 +17,10 @@
 //   k_grow_tsort   : puts every old column's segment into ascending row order, so the lists are the same whatever the scheduling.
 //   k_grow_count / k_grow_fill : the merge, one wavefront per grown column: the old entries that stay (all of them at the graph's own
 //                    radius; below it by the stored distance, an entry ON the tie by its recomputed d2), then the added ones.  The fill
-//                    also writes one BYTE per grown entry: its free bit (old bit, or the near pass's).
+//                    also writes one BYTE per grown entry: its free bit (old bit, or the near pass's).  The count leaves the CHANGED
+//                    COLUMNS as a bitmap over the grown set -- every new column, every old column that lost an entry to the radius
+//                    rule or gained a row -- which is what a tracked field has to look at again (kernels_field.hip, kernels_togo.hip:
+//                    the carry).  A bit is a function of the column alone, set by atomicOr: the bitmap does not depend on scheduling.
 //   k_grow_repack  : the mask.  Every bit position has shifted, so the words are assembled again: a wavefront owns 64 consecutive output
 //                    words, each word is the ballot of 64 bytes, written once by that wavefront alone (no atomics, no read-modify-write);
 //                    the bits behind the last entry are zero.
@@ -242,6 +245,7 @@ struct gw_merge_args {
     int64_t* cnt;                                          // count: [n_all + 1] entries per grown column
     const int64_t* optr; int32_t* orow; double* oval; uint8_t* obyte;                              // fill
     unsigned long long* dropped;
+    unsigned long long* changed; unsigned long long* flagged;      // count: bitmap of the changed columns [ceil(n_all / 64)], its population
 };
 
 // does old entry e of column x stay at the new radius?  The stored distance decides unless it sits on the tie
@@ -299,7 +303,14 @@ __global__ __launch_bounds__(256) void k_grow_merge(gw_merge_args a)
         ab = a.nptr[(x - a.n_old) * GW_WAVES]; nadd = a.nptr[(x - a.n_old + 1) * GW_WAVES] - ab;
         arow = a.nidx; adist = a.ndist; abit = a.nbits;
     }
-    if (!FILL) { if (lane == 0) a.cnt[x] = kept + nadd; return; }
+    if (!FILL) {
+        if (lane == 0) {
+            a.cnt[x] = kept + nadd;
+            const bool chg = x >= a.n_old || nadd > 0 || kept < a.colptr[x + 1] - a.colptr[x];
+            if (chg) { atomicOr(&a.changed[x >> 6], 1ull << (x & 63)); atomicAdd(a.flagged, 1ull); }
+        }
+        return;
+    }
     for (int64_t t = lane; t < nadd; t += 64) {
         const int64_t pos = o + kept + t;
         if (pos < o_end) { a.orow[pos] = arow[ab + t]; a.oval[pos] = adist[ab + t]; a.obyte[pos] = (uint8_t)(abit[ab + t] & 1); }
@@ -340,7 +351,7 @@ static int32_t gw_near_launch(mpfmt_ctx* ctx, gw_near_args& a, double r)
     return MPFMT_OK;
 }
 
-int32_t mpfmt_grow_apply(mpfmt_ctx* ctx, int64_t n_old, double r_new)
+int32_t mpfmt_grow_apply(mpfmt_ctx* ctx, int64_t n_old, double r_new, int32_t carry)
 {
     int32_t rc;
     const int64_t N = ctx->N, n_add = N - n_old, nnz_old = ctx->nnz;
@@ -363,13 +374,14 @@ int32_t mpfmt_grow_apply(mpfmt_ctx* ctx, int64_t n_old, double r_new)
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int64_t nvq = n_add * GW_WAVES;                     // (new sample, part) pairs: the near pass's units
     const size_t o_ncnt = 0, o_nptr = o_ncnt + up(sizeof(int64_t) * (size_t)(nvq + 1)), o_ctr = o_nptr + up(sizeof(int64_t) * (size_t)(nvq + 1)),
-                 o_tcnt = o_ctr + up(sizeof(unsigned long long) * 2), o_tcur = o_tcnt + up(sizeof(int64_t) * (size_t)(n_old + 1)),
+                 o_tcnt = o_ctr + up(sizeof(unsigned long long) * 3), o_tcur = o_tcnt + up(sizeof(int64_t) * (size_t)(n_old + 1)),
                  o_tptr = o_tcur + up(sizeof(int64_t) * (size_t)(n_old + 1)), o_mcnt = o_tptr + up(sizeof(int64_t) * (size_t)(n_old + 1)),
-                 a_bytes = o_mcnt + up(sizeof(int64_t) * (size_t)(N + 1));
+                 o_chg = o_mcnt + up(sizeof(int64_t) * (size_t)(N + 1)), a_bytes = o_chg + up(sizeof(uint64_t) * (size_t)((N + 63) / 64));
     if ((rc = ctx->grow_counts.ensure(ctx, a_bytes))) return rc;
     char* ca = (char*)ctx->grow_counts.get();
     int64_t* ncnt = (int64_t*)(ca + o_ncnt); int64_t* nptr = (int64_t*)(ca + o_nptr);
-    unsigned long long* ctr = (unsigned long long*)(ca + o_ctr);      // [0] candidates, [1] dropped
+    unsigned long long* ctr = (unsigned long long*)(ca + o_ctr);      // [0] candidates, [1] dropped, [2] changed columns (the 256 bytes hold them)
+    unsigned long long* chg = (unsigned long long*)(ca + o_chg);      // bitmap of the changed columns over the grown set
     unsigned long long* tcnt = (unsigned long long*)(ca + o_tcnt); unsigned long long* tcur = (unsigned long long*)(ca + o_tcur);
     int64_t* tptr = (int64_t*)(ca + o_tptr); int64_t* mcnt = (int64_t*)(ca + o_mcnt);
     HIPCHK(ctx, hipMemsetAsync(ca, 0, a_bytes, ctx->stream));
@@ -415,13 +427,13 @@ int32_t mpfmt_grow_apply(mpfmt_ctx* ctx, int64_t n_old, double r_new)
     ma.colptr = ctx->colptr; ma.rowval = ctx->rowval; ma.nzval = ctx->nzval; ma.efree = ctx->graph_free;
     ma.nptr = nptr; ma.nidx = nidx; ma.ndist = ndist; ma.nbits = nbits;
     ma.tptr = tptr; ma.trow = trow; ma.tdist = tdist; ma.tbit = tbit;
-    ma.cnt = mcnt; ma.dropped = ctr + 1;
+    ma.cnt = mcnt; ma.dropped = ctr + 1; ma.changed = chg; ma.flagged = ctr + 2;
     const unsigned nbm = (unsigned)((N + 3) / 4);
     hipLaunchKernelGGL(k_grow_merge<false>, dim3(nbm), dim3(256), 0, ctx->stream, ma);
     HIPCHK(ctx, hipGetLastError());
     if ((rc = mpfmt_scan_i64(ctx, mcnt, ctx->colptr_next, (size_t)(N + 1)))) return rc;
     int64_t nnz_new = 0;
-    unsigned long long hctr[2] = {0, 0};
+    unsigned long long hctr[3] = {0, 0, 0};
     HIPCHK(ctx, hipMemcpyAsync(&nnz_new, ctx->colptr_next.get() + N, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(hctr, ctr, sizeof(hctr), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -439,6 +451,13 @@ int32_t mpfmt_grow_apply(mpfmt_ctx* ctx, int64_t n_old, double r_new)
         HIPCHK(ctx, hipGetLastError());
     }
     tg.end("samples_add_merge");
+    // ---- the tracked fields follow (option "samples_add_keeps_fields"): into spare buffers of their own, over the grown arrays ----
+    if (carry) {
+        mpfmt_timed tc(ctx);
+        if ((carry & 1) && (rc = mpfmt_field_carry(ctx, n_old, ctx->colptr_next, ctx->rowval_next, (const uint64_t*)chg))) return rc;
+        if ((carry & 2) && (rc = mpfmt_togo_carry(ctx, n_old, (const uint64_t*)chg))) return rc;
+        tc.end("samples_add_carry");
+    }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // ---- everything has succeeded: the grown arrays change places with the ctx's own ----
     ctx->colptr.swap(ctx->colptr_next); ctx->rowval.swap(ctx->rowval_next); ctx->nzval.swap(ctx->nzval_next);
@@ -449,6 +468,7 @@ int32_t mpfmt_grow_apply(mpfmt_ctx* ctx, int64_t n_old, double r_new)
     ctx->sweep_in_order = false; ctx->sweep_pending_used = false; ctx->bits_in_records = false;
     ctx->grow_candidates = (int64_t)hctr[0];
     ctx->grow_dropped = (int64_t)hctr[1];
+    ctx->grow_flagged = (int64_t)hctr[2];
     ctx->grow_entries = nnz_new - (nnz_old - ctx->grow_dropped);
     return MPFMT_OK;
 }

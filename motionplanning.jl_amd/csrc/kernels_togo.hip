@@ -244,6 +244,43 @@ __global__ __launch_bounds__(256) void k_togo_finish(int64_t N, int64_t words, c
     }
 }
 
+// The field follows a growth of the sample set (mpfmt_samples_add with option "samples_add_keeps_fields"), lane per sample
+// of the grown set, out of the tracked buffers into the spare ones: old samples keep label and successor, new ones get +Inf and none and
+// are no targets.  Threads [0, words) lay the seven bitmaps again for words = ceil(N / 64): the targets extended by zeros, dirty = the
+// pending bits of earlier edits | the changed columns of the growth, everything else empty.  No invalidation rule of its own: k_togo_i0
+// finds the successor edge of y by binary search in column S[y] whenever that column is dirty, and a column that lost the entry is.
+__global__ __launch_bounds__(256) void k_togo_carry(int64_t n_old, int64_t N, int64_t words_old, int64_t words, const double* __restrict__ G,
+                                                    const unsigned long long* __restrict__ S, const uint64_t* __restrict__ bm,
+                                                    const uint64_t* __restrict__ changed, double* __restrict__ Gn, unsigned long long* __restrict__ Sn,
+                                                    uint64_t* __restrict__ bmn)
+{
+    const int64_t y = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (y < N) {
+        Gn[y] = y < n_old ? G[y] : INFINITY;
+        Sn[y] = y < n_old ? S[y] : 0ull;
+    }
+    if (y < words) {
+        const bool old = y < words_old;
+        bmn[y] = 0ull; bmn[words + y] = 0ull; bmn[2 * words + y] = 0ull;
+        bmn[TOGO_BM_TARGETS * words + y] = old ? bm[TOGO_BM_TARGETS * words_old + y] : 0ull;
+        bmn[TOGO_BM_DIRTY * words + y] = (old ? bm[TOGO_BM_DIRTY * words_old + y] : 0ull) | changed[y];
+        bmn[TOGO_BM_INV * words + y] = 0ull; bmn[TOGO_BM_SEEN * words + y] = 0ull;
+    }
+}
+
+// targets that join a tracked field (mpfmt_togo_targets_add; 1-based, validated on the host; duplicates and old targets write the same
+// values): a label decrease -- G = 0, no successor, the target bit, and the dirty bit, so the sample pushes in round 0 of the next repair
+__global__ __launch_bounds__(256) void k_togo_targets_add(int64_t ntgt, int64_t words, const int64_t* __restrict__ tgt1, double* __restrict__ G,
+                                                          unsigned long long* __restrict__ S, uint64_t* bm)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ntgt) return;
+    const int64_t t = tgt1[e] - 1;
+    G[t] = 0.0; S[t] = 0ull;
+    atomicOr((unsigned long long*)&bm[TOGO_BM_TARGETS * words + (t >> 6)], 1ull << (t & 63));
+    atomicOr((unsigned long long*)&bm[TOGO_BM_DIRTY * words + (t >> 6)], 1ull << (t & 63));
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 
 static int32_t togo_buffers(mpfmt_ctx* ctx)
@@ -327,7 +364,7 @@ static void togo_adopt(mpfmt_ctx* ctx)
     ctx->tg_steer_kind = ctx->steer_kind;
     ctx->tg_steer_a = !steer ? 0.0 : ctx->steer_kind == MPFMT_STEER_DI ? ctx->di_rho : ctx->car_rt;
     ctx->tg_steer_b = !steer || ctx->steer_kind == MPFMT_STEER_DI ? 0.0 : ctx->car_sp;
-    ctx->tg_dirty_any = false;
+    ctx->tg_dirty_any = false; ctx->tg_grown = false;
 }
 
 // The whole field of the target set into the tracked buffers (targets1: 1-based, on the host, validated by the caller; it may be the
@@ -419,7 +456,51 @@ int32_t mpfmt_togo_repair(mpfmt_ctx* ctx, const uint64_t* d_F, mpfmt_togo_info* 
     float ms = 0.f;
     HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->sssp_ev[0], ctx->sssp_ev[1]));
     togo_stats(ctx, sh, 1, ms, info);
-    ctx->tg_dirty_any = false;
+    ctx->tg_dirty_any = false; ctx->tg_grown = false;
+    return MPFMT_OK;
+}
+
+// ctx->N is the grown size; the tracked buffers hold the field of the first n_old samples (tg_N == n_old, checked by the caller through
+// mpfmt_togo_live before the sample set changed).  Nothing tracked is written: a failure leaves the field as it was.
+int32_t mpfmt_togo_carry(mpfmt_ctx* ctx, int64_t n_old, const uint64_t* changed)
+{
+    const int64_t N = ctx->N, words = (N + 63) / 64, words_old = (n_old + 63) / 64;
+    int32_t rc;
+    if ((rc = ctx->tg_G_next.ensure(ctx, sizeof(double) * (size_t)N))) return rc;
+    if ((rc = ctx->tg_S_next.ensure(ctx, sizeof(unsigned long long) * (size_t)N))) return rc;
+    if ((rc = ctx->tg_bm_next.ensure(ctx, sizeof(uint64_t) * TOGO_BITMAPS * (size_t)words))) return rc;
+    if ((rc = ctx->tg_best.ensure(ctx, sizeof(unsigned long long) * (size_t)N))) return rc;      // (scratch of the successor passes: nothing to keep)
+    hipLaunchKernelGGL(k_togo_carry, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, n_old, N, words_old, words,
+                       (const double*)ctx->tg_G.get(), (const unsigned long long*)ctx->tg_S.get(), (const uint64_t*)ctx->tg_bm.get(), changed,
+                       ctx->tg_G_next.get(), ctx->tg_S_next.get(), ctx->tg_bm_next.get());
+    HIPCHK(ctx, hipGetLastError());
+    return MPFMT_OK;
+}
+
+// after the growth has succeeded (the ctx's epochs are those of the grown graph): the field is the ctx's again, with columns pending
+void mpfmt_togo_carry_commit(mpfmt_ctx* ctx)
+{
+    ctx->tg_G.swap(ctx->tg_G_next); ctx->tg_S.swap(ctx->tg_S_next); ctx->tg_bm.swap(ctx->tg_bm_next);
+    ctx->tg_N = ctx->N;
+    ctx->tg_samples_epoch = ctx->samples_epoch; ctx->tg_build_epoch = ctx->graph_epoch; ctx->tg_sweep_epoch = ctx->sweep_epoch;
+    ctx->tg_graph_r = ctx->graph_r;
+    ctx->tg_dirty_any = true; ctx->tg_grown = true;
+}
+
+// targets1: 1-based in 1 .. ctx->N, on the host (validated by the caller), ntgt > 0; the field is live
+int32_t mpfmt_togo_add_targets(mpfmt_ctx* ctx, const int64_t* targets1, int64_t ntgt)
+{
+    const int64_t words = (ctx->N + 63) / 64;
+    int32_t rc;
+    mpfmt_dbuf<int64_t> d_t;                                                   // (tg_tgt holds the field's own list: a recomputation uploads into it)
+    if ((rc = d_t.ensure(ctx, sizeof(int64_t) * (size_t)ntgt))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(d_t, targets1, sizeof(int64_t) * (size_t)ntgt, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_togo_targets_add, dim3((unsigned)((ntgt + 255) / 256)), dim3(256), 0, ctx->stream, ntgt, words, (const int64_t*)d_t.get(),
+                       ctx->tg_G.get(), ctx->tg_S.get(), ctx->tg_bm.get());
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->tg_targets.insert(ctx->tg_targets.end(), targets1, targets1 + ntgt);
+    ctx->tg_dirty_any = true;
     return MPFMT_OK;
 }
 
@@ -427,6 +508,7 @@ void mpfmt_togo_drop_internal(mpfmt_ctx* ctx)
 {
     ctx->tg_tracked = false;
     ctx->tg_dirty_any = false;
+    ctx->tg_grown = false;
     ctx->tg_targets.clear();
 }
 

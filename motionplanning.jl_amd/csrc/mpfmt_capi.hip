@@ -404,11 +404,18 @@ static int32_t samples_add(mpfmt_ctx* ctx, const double* src, bool src_on_host, 
         for (int b = 0; b < nb; ++b) { lo[i] = std::min(lo[i], h->part[b][0][i]); hi[i] = std::max(hi[i], h->part[b][1][i]); }
     }
     const bool in_place = samples_add_in_place(ctx, r_new);
+    // the tracked fields that follow the growth (option "samples_add_keeps_fields"): live fields of the old set whose delta history stands,
+    // asked BEFORE the ctx takes the grown set (a field of another N is not live).  One that needs a recomputation anyway is dropped
+    int32_t carry = 0;
+    if (in_place && ctx->grow_keeps_fields) {
+        if (mpfmt_field_live(ctx) && mpfmt_field_history(ctx)) carry |= 1;
+        if (mpfmt_togo_live(ctx) && !ctx->tg_steer && mpfmt_togo_history(ctx)) carry |= 2;
+    }
     ctx->Xo.swap(ctx->Xo_next);
     ctx->N = N;
     for (int i = 0; i < d; ++i) { ctx->bb_lo[i] = lo[i]; ctx->bb_hi[i] = hi[i]; }
     if (in_place) {
-        if ((rc = mpfmt_grow_apply(ctx, n_old, r_new))) {     // the ctx is again what it was; the cell order is rebuilt by whoever needs it next
+        if ((rc = mpfmt_grow_apply(ctx, n_old, r_new, carry))) {     // the ctx is again what it was; the cell order is rebuilt by whoever needs it next
             ctx->Xo.swap(ctx->Xo_next);
             ctx->N = n_old;
             for (int i = 0; i < d; ++i) { ctx->bb_lo[i] = lo_was[i]; ctx->bb_hi[i] = hi_was[i]; }
@@ -417,15 +424,16 @@ static int32_t samples_add(mpfmt_ctx* ctx, const double* src, bool src_on_host, 
         }
     }
     ctx->samples_epoch += 1;
-    mpfmt_field_drop_internal(ctx);
-    mpfmt_togo_drop_internal(ctx);
+    if (carry & 1) mpfmt_field_carry_commit(ctx); else mpfmt_field_drop_internal(ctx);
+    if (carry & 2) mpfmt_togo_carry_commit(ctx); else mpfmt_togo_drop_internal(ctx);
+    ctx->grow_carried = carry;
     ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false;
     ctx->grow_path = in_place ? 1 : 0;
     if (!in_place) {                                         // what mpfmt_upload_samples of the concatenated set leaves
         ctx->grid_r = -1.0; ctx->graph_r = -1.0; ctx->ops_r = -1.0; ctx->lists_r = -1.0;
         ctx->graph_counted = ctx->graph_filled = ctx->graph_swept = false; ctx->knn_k = 0;
         ctx->nnz = 0;
-        ctx->grow_candidates = ctx->grow_entries = ctx->grow_dropped = 0;
+        ctx->grow_candidates = ctx->grow_entries = ctx->grow_dropped = ctx->grow_flagged = 0;
     }
     tm.end("samples_add");
     return MPFMT_OK;
@@ -1528,6 +1536,7 @@ int32_t mpfmt_field_read(mpfmt_ctx* ctx, double* C, int64_t* A)
 {
     if (!ctx) return MPFMT_ERR_ARG;
     if (!mpfmt_field_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked field (mpfmt_field_begin)");
+    if (ctx->fld_grown) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the sample set grew since the tracked field was last valid (mpfmt_field_update)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)ctx->N;
     if (C) HIPCHK(ctx, hipMemcpyAsync(C, ctx->fld_C, sizeof(double) * N, hipMemcpyDeviceToHost, ctx->stream));
@@ -1544,6 +1553,7 @@ int32_t mpfmt_field_goal(mpfmt_ctx* ctx, int32_t goal_kind, const double* goal_p
     if (ctx->Xo && ctx->steer_filled)
         return mpfmt_fail(ctx, MPFMT_ERR_STATE, "tracked fields and external states: Euclidean graphs only (the resident graph is a steering graph)");
     if (!mpfmt_field_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked field (mpfmt_field_begin)");
+    if (ctx->fld_grown) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the sample set grew since the tracked field was last valid (mpfmt_field_update)");
     if (ctx->fld_dirty_any || !mpfmt_field_history(ctx) || !ctx->graph_swept)
         return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the box set was edited since the tracked field was last valid (mpfmt_field_update)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1612,12 +1622,27 @@ int32_t mpfmt_togo_read(mpfmt_ctx* ctx, double* G, int64_t* S)
 {
     if (!ctx) return MPFMT_ERR_ARG;
     if (!mpfmt_togo_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked cost-to-go field (mpfmt_togo_begin)");
+    if (ctx->tg_grown) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "the sample set grew since the tracked cost-to-go field was last valid (mpfmt_togo_update)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)ctx->N;
     if (G) HIPCHK(ctx, hipMemcpyAsync(G, ctx->tg_G, sizeof(double) * N, hipMemcpyDeviceToHost, ctx->stream));
     if (S) HIPCHK(ctx, hipMemcpyAsync(S, ctx->tg_S, sizeof(int64_t) * N, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return MPFMT_OK;
+}
+
+// targets that join the tracked set: label decreases, pending until the next mpfmt_togo_update.  A refusal has touched nothing
+int32_t mpfmt_togo_targets_add(mpfmt_ctx* ctx, const int64_t* targets, int64_t ntgt)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (ntgt < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "ntgt < 0");
+    if (ntgt > 0 && !targets) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "targets is NULL");
+    if (!mpfmt_togo_live(ctx)) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "no tracked cost-to-go field (mpfmt_togo_begin)");
+    int32_t rc;
+    if ((rc = check_idx(ctx, targets, ntgt, "targets"))) return rc;
+    if (ntgt == 0) return MPFMT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return mpfmt_togo_add_targets(ctx, targets, ntgt);
 }
 
 int32_t mpfmt_togo_drop(mpfmt_ctx* ctx)
@@ -2792,6 +2817,7 @@ int32_t mpfmt_set_option(mpfmt_ctx* ctx, const char* name, int64_t value)
     if (strcmp(name, "di_path") == 0) { ctx->di_path = (int32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 2); ctx->steer_counted = ctx->steer_filled = ctx->steer_swept = false; return MPFMT_OK; }
     if (strcmp(name, "wf_force_sharded") == 0) { ctx->wf_force_sharded = value != 0; return MPFMT_OK; }
     if (strcmp(name, "steer_shapes_delta") == 0) { ctx->steer_shapes_delta = value != 0; return MPFMT_OK; }
+    if (strcmp(name, "samples_add_keeps_fields") == 0) { ctx->grow_keeps_fields = value != 0; return MPFMT_OK; }
     return mpfmt_fail(ctx, MPFMT_ERR_ARG, "unknown option %s", name);
 }
 
@@ -2818,6 +2844,9 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "samples_add_candidates") == 0) { *value = ctx->grow_candidates; return MPFMT_OK; }
     if (strcmp(name, "samples_add_entries") == 0) { *value = ctx->grow_entries; return MPFMT_OK; }
     if (strcmp(name, "samples_add_dropped") == 0) { *value = ctx->grow_dropped; return MPFMT_OK; }
+    if (strcmp(name, "samples_add_flagged_columns") == 0) { *value = ctx->grow_flagged; return MPFMT_OK; }
+    if (strcmp(name, "samples_add_fields_carried") == 0) { *value = ctx->grow_carried; return MPFMT_OK; }
+    if (strcmp(name, "samples_add_keeps_fields") == 0) { *value = ctx->grow_keeps_fields; return MPFMT_OK; }
     if (strcmp(name, "pend_overflowed") == 0) { *value = ctx->pend_overflowed ? 1 : 0; return MPFMT_OK; }
     if (strcmp(name, "redo_count") == 0) { *value = ctx->redo_count; return MPFMT_OK; }
     if (strcmp(name, "redo_reason") == 0) { *value = ctx->redo_reason; ctx->redo_reason = 0; return MPFMT_OK; }      // (bits since the last read)

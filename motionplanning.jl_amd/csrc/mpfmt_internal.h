@@ -392,6 +392,9 @@ struct mpfmt_ctx {
     mpfmt_dbuf<void> grow_counts, grow_lists, grow_bytes;      // the call's temporaries (grow-only): counters and offsets | the new samples' lists | one byte per grown entry
     int32_t grow_path = 0;               // 1: the resident graph was grown in place, 0: invalidated
     int64_t grow_candidates = 0, grow_entries = 0, grow_dropped = 0;      // stats of the last call
+    int64_t grow_flagged = 0;            // stat: the changed columns of the last in-place call (new | lost an entry | gained a row)
+    int32_t grow_keeps_fields = 0;       // option "samples_add_keeps_fields": 1 = an in-place growth carries the tracked fields
+    int32_t grow_carried = 0;            // stat: bit 0 the cost-to-come field, bit 1 the cost-to-go field was carried by the last call
 
     // ---- scratch -------------------------------------------------------------------------------
     mpfmt_dbuf<void> scratch;
@@ -466,6 +469,10 @@ struct mpfmt_ctx {
     int64_t fld_samples_epoch = -1, fld_graph_epoch = -1, fld_sweep_epoch = -1, fld_N = 0, fld_knn_k = 0;
     double fld_graph_r = -1.0;
     bool fld_dirty_any = false;          // a delta call has flagged columns since the field was last valid
+    bool fld_grown = false;              // the sample set grew under the field: nothing of the ctx's N to read before the next update
+    mpfmt_dbuf<double> fld_C_next;        // the spare buffers of the carry (mpfmt_field_carry): they change places with the four above
+    mpfmt_dbuf<int64_t> fld_A_next, fld_Ab_next;
+    mpfmt_dbuf<uint64_t> fld_bm_next;
     // stats of the last mpfmt_field_begin / _update
     int32_t fld_path = 0;
     int64_t fld_invalidated = 0, fld_dirty_columns = 0, fld_columns_read = 0, fld_column_visits = 0, fld_entries_read = 0, fld_rounds = 0,
@@ -489,6 +496,10 @@ struct mpfmt_ctx {
     double tg_graph_r = -1.0, tg_steer_a = 0.0, tg_steer_b = 0.0;      // the graph's identity: radius (or k), steering parameters
     mpfmt_steer tg_steer_kind = MPFMT_STEER_DI;
     bool tg_dirty_any = false;           // a delta call has flagged columns since the field was last valid
+    bool tg_grown = false;               // the sample set grew under the field: nothing of the ctx's N to read before the next update
+    mpfmt_dbuf<double> tg_G_next;         // the spare buffers of the carry (mpfmt_togo_carry)
+    mpfmt_dbuf<unsigned long long> tg_S_next;
+    mpfmt_dbuf<uint64_t> tg_bm_next;
     // stats of the last mpfmt_togo_begin / _update
     int32_t tg_path = 0, tg_seed_form = 0;
     int64_t tg_invalidated = 0, tg_dirty_columns = 0, tg_columns_read = 0, tg_column_visits = 0, tg_entries_read = 0, tg_rounds = 0,
@@ -659,6 +670,11 @@ int32_t mpfmt_field_mark_dirty(mpfmt_ctx* ctx);          // ORs ctx->bd_cols[0 .
 void mpfmt_field_drop_internal(mpfmt_ctx* ctx);
 bool mpfmt_field_live(mpfmt_ctx* ctx);                   // a tracked field of the resident samples and graph (drops one of another graph)
 bool mpfmt_field_history(const mpfmt_ctx* ctx);          // no graph build and no whole sweep since the field was last valid
+// the field follows a growth of the sample set (ctx->N is the grown size, the field is that of the first n_old samples): C / A extended,
+// Ab found again in the grown columns, the dirty bitmap re-laid and ORed with `changed` -- all into the spare buffers, on ctx->stream.
+// mpfmt_field_carry_commit changes them for the tracked ones and moves the field's identity to the ctx's (after the call has succeeded)
+int32_t mpfmt_field_carry(mpfmt_ctx* ctx, int64_t n_old, const int64_t* colptr_new, const int32_t* rowval_new, const uint64_t* changed);
+void mpfmt_field_carry_commit(mpfmt_ctx* ctx);
 // the tracked cost-to-go field (kernels_togo.hip)
 int32_t mpfmt_togo_compute(mpfmt_ctx* ctx, const int64_t* targets1, int64_t ntgt, int32_t checkpts, const uint64_t* d_F, mpfmt_togo_info* info);
 int32_t mpfmt_togo_repair(mpfmt_ctx* ctx, const uint64_t* d_F, mpfmt_togo_info* info);      // steps 2-5 on the tracked buffers
@@ -666,6 +682,9 @@ int32_t mpfmt_togo_mark_dirty(mpfmt_ctx* ctx);           // ORs ctx->bd_cols[0 .
 void mpfmt_togo_drop_internal(mpfmt_ctx* ctx);
 bool mpfmt_togo_live(mpfmt_ctx* ctx);                    // a tracked field of the resident samples and graph (drops one of another graph)
 bool mpfmt_togo_history(const mpfmt_ctx* ctx);           // no graph build and no whole sweep since the field was last valid
+int32_t mpfmt_togo_carry(mpfmt_ctx* ctx, int64_t n_old, const uint64_t* changed);      // as mpfmt_field_carry: G / S / targets / dirty
+void mpfmt_togo_carry_commit(mpfmt_ctx* ctx);
+int32_t mpfmt_togo_add_targets(mpfmt_ctx* ctx, const int64_t* targets1, int64_t ntgt);      // validated 1-based targets join the tracked set (label decreases)
 // the field of the usable seeds of one external start: entries [n] of a near list (1-based samples, distances, bits: 2 = usable) become
 // C[y] = seed[y] = fl(0 + dist); labels stay in ctx->sssp_C, parents in ctx->sssp_A (1-based, -1 = the start, 0 = none)
 int32_t mpfmt_sssp_seeded_device(mpfmt_ctx* ctx, const int64_t* d_idx1, const double* d_dist, const uint8_t* d_bits, int64_t n, const uint64_t* d_F,
@@ -693,7 +712,9 @@ int32_t mpfmt_steer_roadmap_reduce(mpfmt_ctx* ctx, mpfmt_tmp& tmp, const double*
 // The ctx holds the grown sample set (N, Xo, bounding box) and, untouched, the swept graph of its first n_old samples: the graph and
 // mask of radius r_new over all N are built in the spare buffers and change places with the ctx's own.  An error return has changed
 // neither the graph's arrays nor its flags (the cell grid may be that of the grown set: the caller marks it stale).
-int32_t mpfmt_grow_apply(mpfmt_ctx* ctx, int64_t n_old, double r_new);
+// carry (option "samples_add_keeps_fields"): bit 0 = the tracked cost-to-come field, bit 1 = the tracked cost-to-go field follow the
+// growth into their spare buffers (mpfmt_field_carry / mpfmt_togo_carry); the caller commits them once the whole call has succeeded.
+int32_t mpfmt_grow_apply(mpfmt_ctx* ctx, int64_t n_old, double r_new, int32_t carry);
 
 // kernels_sssp_multi.hip ----------------------------------------------------------------------------
 // nsrc fields (sources 1-based, on the host) in groups of 64 over the resident graph and mask; C_host [nsrc][N], A_host [nsrc][N] or nullptr

@@ -662,7 +662,11 @@ def grow_(P, N, r=None, ensure_goal_ct=1, rng=None, seed=None):
     makes, and Context.samples_add installs them behind the resident ones -- a resident, swept r-disc graph follows in place
     (P.ctx.stat("samples_add_path") == 1), so that a following prmstar_(P, r=r) / fmtstar_(P, r=r) plans on the grown graph with
     neither pair phase nor sweep.  r = None keeps the graph's radius; a smaller r (the default rule shrinks it as N grows) drops the
-    entries beyond it.  seed seeds the generator when no rng is given.  Returns the number of samples added."""
+    entries beyond it.  seed seeds the generator when no rng is given.  Returns the number of samples added.
+    The mirror turns the context's option "samples_add_keeps_fields" on first, so that the field of prmstar_(..., keep_field=True) and
+    the policy of cost_to_go_(P, keep_field=True) follow an in-place growth (P.ctx.stat("samples_add_fields_carried")): replan_(P) /
+    repolicy_(P) then REPAIR them on the grown graph -- anytime refinement is grow_ -> replan_ / repolicy_ -- and equal a fresh
+    prmstar_ / cost_to_go_ on the grown set.  Where the growth could not go in place the fields are dropped, as new samples drop them."""
     n_add = int(N) - len(P.V)
     if n_add <= 0:
         return 0
@@ -670,6 +674,7 @@ def grow_(P, N, r=None, ensure_goal_ct=1, rng=None, seed=None):
         rng = np.random.default_rng(seed)
     P.CC._bind(P.ctx, P.SS)
     W = _draw_free(P, n_add, ensure_goal_ct=ensure_goal_ct, rng=rng)
+    P.ctx.set_option(_lib.OPT_SAMPLES_ADD_KEEPS_FIELDS, 1)
     P.ctx.samples_add(W, r=r)
     P.V = MetricNN(np.concatenate([P.V.V, W]), P.V.dist, P.V.init, P.ctx, upload=False)
     return n_add
@@ -762,7 +767,8 @@ def prmstar_(P, N=None, rm=1.0, connections="R", r=0.0, ensure_goal_ct=1, init_i
     and ReedsSheppExact spaces the steering graph of the space takes the r-disc graph's place (mpfmt_di_prmstar, mpfmt_dubins_prmstar,
     mpfmt_reedsshepp_prmstar), with fmtstar_'s radius rule and goal mapping; connections = "K" and keep_field = True are Euclidean only.
     keep_field = True: the context keeps the field of init_idx (Context.field_begin), so that after addobstacle_ / addblocker_ /
-    removeobstacle_ a replan_(P) repairs it instead of computing it again."""
+    removeobstacle_ -- and after grow_, which carries the field across an in-place growth of the sample set -- a replan_(P) repairs it
+    instead of computing it again."""
     t0 = time.time()
     N = len(P.V) if N is None else int(N)
     P.CC.count = 0
@@ -821,7 +827,9 @@ def replan_(P):
     """After addobstacle_ / addblocker_ / removeobstacle_ on a problem solved by prmstar_(..., keep_field=True): repair the field the
     context kept (Context.field_update: work that follows the edit; a whole recomputation only where the edit could not be applied in
     place), then extract goal and path from it (Context.field_goal).  Fills P.solution as prmstar_ does, with
-    metadata["field_info"] = the repair's counters.  Raises (MPFMTError, ERR_STATE) without a tracked field."""
+    metadata["field_info"] = the repair's counters.  Raises (MPFMTError, ERR_STATE) without a tracked field.
+    The same after grow_ (alone or mixed with obstacle edits): the field was carried across the growth and the repair works on the
+    changed columns; path, cost, cost_to_come and tree equal a fresh prmstar_ on the grown sample set at the grown graph's radius."""
     t0 = time.time()
     if P.solution is None or P.ctx is None or P.solution.metadata.get("planner") != "prmstar":
         raise RuntimeError("replan_ needs the solution of a prmstar_(..., keep_field=True) call")
@@ -838,6 +846,7 @@ def replan_(P):
     P.status = "solved" if res["status"] == 1 else "failed"
     path = res["path"]
     meta = dict(old)
+    meta["num_samples"] = len(Cc)
     meta.update({"collision_checks": 0, "cost": res["cost"], "cumcost": Cc[path - 1], "solved": res["status"] == 1, "tree": A, "path": path,
                  "cost_to_come": Cc, "ms_host_loop": res["ms_host_loop"], "field_info": info})
     P.solution = MPSolution(P.status, res["cost"], time.time() - t0, meta)
@@ -905,7 +914,8 @@ def cost_to_go_(P, checkpts=True, keep_field=False):
     cannot be reached, 0 on the goal samples; S 1-based successors (0 = goal sample or unreached).  Stores metadata["cost_to_go"] and
     metadata["successor"].
     keep_field = True: the context keeps the policy (Context.togo_begin), in any space, so that after addobstacle_ / addblocker_ /
-    removeobstacle_ a repolicy_(P) repairs it instead of computing it again."""
+    removeobstacle_ -- and, in a Euclidean space, after grow_, which carries the policy across an in-place growth of the sample set -- a
+    repolicy_(P) repairs it instead of computing it again."""
     if P.solution is None or P.ctx is None:
         raise RuntimeError("cost_to_go_ needs the roadmap of a prmstar_ / fmtstar_ call")
     P.CC._bind(P.ctx, P.SS)
@@ -918,6 +928,7 @@ def cost_to_go_(P, checkpts=True, keep_field=False):
     P.solution.metadata["cost_to_go"] = G
     P.solution.metadata["successor"] = S
     P.solution.metadata["cost_to_go_info"] = info
+    P._policy_samples = len(G)                              # (repolicy_: goal samples behind it are new targets)
     return G, S
 
 
@@ -925,7 +936,10 @@ def repolicy_(P):
     """After addobstacle_ / addblocker_ / removeobstacle_ on a problem whose policy cost_to_go_(P, keep_field=True) left in the context:
     repair it (Context.togo_update: work that follows the edit; a whole recomputation only where the edit could not be applied in place)
     and refresh metadata["cost_to_go"] / ["successor"]; metadata["cost_to_go_info"] = the repair's counters.  successor_paths then
-    serves any current state.  Returns (G, S).  Raises (MPFMTError, ERR_STATE) without a tracked policy."""
+    serves any current state.  Returns (G, S).  Raises (MPFMTError, ERR_STATE) without a tracked policy.
+    The same after grow_ (alone or mixed with obstacle edits): the policy was carried across the growth; the goal members among the new
+    samples (_goal_members over the grown P.V) first join the target set (Context.togo_targets_add), then the repair runs, and (G, S)
+    equal a fresh cost_to_go_ on the grown sample set."""
     if P.solution is None or P.ctx is None:
         raise RuntimeError("repolicy_ needs the policy of a cost_to_go_(P, keep_field=True) call")
     ctx = P.ctx
@@ -941,11 +955,16 @@ def repolicy_(P):
             ctx.dubins_graph_edges_free() if isinstance(P.SS.dist, DubinsExact) else ctx.reedsshepp_graph_edges_free()
     elif ctx.stat("graph_swept") != 1:
         ctx.knn_graph_edges_free() if "k" in P.solution.metadata else ctx.graph_sweep_device()
+    n_seen = getattr(P, "_policy_samples", len(P.V))
+    if len(P.V) > n_seen:                                   # grow_ since the policy was last valid: the new goal samples are targets too
+        members = _goal_members(P)
+        ctx.togo_targets_add(members[members > n_seen])
     info = ctx.togo_update()
     G, S = ctx.togo_read()
     P.solution.metadata["cost_to_go"] = G
     P.solution.metadata["successor"] = S
     P.solution.metadata["cost_to_go_info"] = info
+    P._policy_samples = len(G)                              # (repolicy_: goal samples behind it are new targets)
     return G, S
 
 
