@@ -819,6 +819,78 @@ MPFMT_API int32_t mpfmt_discretize(mpfmt_ctx* ctx, int32_t space, int32_t d, con
                          double dt, int64_t n_samples, int32_t append_end, double* out_X, double* out_T, int32_t* out_seg, int64_t out_cap,
                          mpfmt_disc_info* info);
 
+/* ---- steering shortcut: shortcutting of solution paths in the double-integrator, Dubins and Reeds-Shepp spaces, for a BATCH of paths on
+ *      the device (one wavefront per path), and the pair primitive it is made of.  The reference refuses these spaces
+ *      (adaptive_shortcut: "requires Euclidean SS", postprocessors.jl:41-50); the procedure below is this library's own statement.
+ *      space / d / params as mpfmt_discretize: MPFMT_SPACE_DI (d = 2 m, m = 1 .. 6, params {rho, tmax}: tmax the Newton bracket of the
+ *      steer), MPFMT_SPACE_DUBINS / _REEDSSHEPP (d = 3, params {turn_radius, speed}).
+ *      The checker is the ctx's resident one, bound as the space's graph sweep binds it: the workspace boxes of mpfmt_upload_boxes (dw = m
+ *      for the double integrator, dw = 2 for the cars) with the d state bounds, or the 2-D shape world (mpfmt_upload_shapes2d; cars, and
+ *      the double integrator with m = 2; its d state bounds through mpfmt_set_state_bounds).  No sample set and no graph is needed:
+ *      mpfmt_upload_boxes takes the number of state bounds as an argument, so a fresh ctx with a checker serves.
+ *
+ *   mpfmt_steer_motions_free: n pairs (P_e, Q_e), P and Q d x n column-major.  Per pair: cost[e] = the steer's cost (mpfmt_di_steer,
+ *      mpfmt_dubins_steer, mpfmt_reedsshepp_steer); dur[e] = t* for the double integrator, the left-to-right sum of the step durations for
+ *      the cars; bit e of mask = is_free_motion(P_e, Q_e, CC, SS) exactly as the space's graph sweep computes it, with the same device
+ *      functions: 5 waypoints at the steer's t*, or arc waypoints every pi / 12, the bounds test of each segment's first waypoint
+ *      included; nseg[e] = the segment tests counted (what CC.count gains).  cost, dur and nseg may be NULL; mask has ceil(n / 64) words.
+ *      Errors as mpfmt_discretize (MPFMT_ERR_ARG: NULL P / Q / mask with n > 0, n < 0, a non-finite coordinate or parameter, a d that does
+ *      not fit the space), plus MPFMT_ERR_STATE: no checker, a checker whose workspace or bounds do not fit the space, a sharded ctx.
+ *      n == 0 succeeds and does nothing.  Timer "steer_motions_free".
+ *
+ *   mpfmt_steer_shortcut_batch / mpfmt_steer_shortcut: with (cost, dur, bit, nseg)(v, w) the primitive's results for the pair,
+ *      Working path and leg costs: the working path is p_1 .. p_n with leg costs c_i (and leg durations); cum_1 = 0 and cum_i+1 =
+ *        fl(cum_i + c_i), a left-to-right fold.  Input legs are steered and tested once; legs_blocked counts input legs whose own test
+ *        fails: they are reported, not altered.
+ *      Acceptance: ok(i, j), for j > i + 1, holds iff bit(p_i, p_j) is set and cost(p_i, p_j) <= fl(SLACK * fl(cum_j - cum_i)), SLACK =
+ *        1 + 2^-30 (exact in fp64): a reconnection that IS the replaced trajectory ties on the accepting side, not on rounding noise.
+ *        The cost condition also covers a double-integrator steer clamped at its bracket tmax: a valid trajectory, not an improvement.
+ *        Every ok asked evaluates the pair test (its nseg counts) whatever the cost comparison gives.
+ *      shortcut(p): postprocessors.jl:6-16 with is_free_motion replaced by ok: n == 2 -> p; ok(1, n) -> the two ends; else mid =
+ *        ceil(n / 2) and shortcut(p[1:mid])[1:end-1] ++ shortcut(p[mid:n]); cum is the fold of the path the pass began with.  An accepted
+ *        node's leg cost (and duration) is its steer's.  Applied to a fixed point: the length strictly decreases until it stops.
+ *      refine(p): every leg of duration T > 0 proposes the state m at fl(T / 2) along its own steered trajectory: the double integrator's
+ *        closed-form waypoint state, the cars' partial propagate through the control steps, both exactly as mpfmt_discretize samples a
+ *        two-state path at 3 samples.  m is inserted iff bit(p_i, m), bit(m, p_i+1) and fl(c' + c'') <= fl(SLACK * c_i) for the two
+ *        re-steered costs; both halves are always asked.  Invariant: every leg of the working path is an input leg or has passed the
+ *        motion test.
+ *      Driver: shortcut to a fixed point; then `iterations` times: refine, then shortcut to a fixed point.  An iteration that returns the
+ *        bit-identical states it began with ends the loop (later ones would repeat it); it still counts in iterations_done.  Guard: a
+ *        refine that would make the working path longer than max_states returns the path of the last completed iteration, status
+ *        MPFMT_SHORTCUT_TRUNCATED (the tests of that refine were asked and are counted); MPFMT_SHORTCUT_STUCK cannot occur.
+ *      Outputs: out_P, out_offsets and cumcost laid out as mpfmt_adaptive_shortcut_batch (cumcost = the cum fold of the result);
+ *        out_origin (may be NULL): int32 per output state, the 1-based index of the input state, 0 for an inserted one; per path an
+ *        mpfmt_steer_shortcut_info: inserted = states the completed refines inserted; collision_checks = the nseg of the tests the
+ *        SEQUENTIAL procedure asks for (input legs, asked nodes, both halves of every proposing leg); tests_evaluated = pair tests
+ *        actually run (the device tests the whole split tree speculatively); cost_in / cost_out = cum_n of the input and of the result;
+ *        max_working_len = the longest working path (the input and every completed refine).
+ *      A path of 2 states is shortcut to itself: with iterations == 0 it comes back unchanged with only its one leg test.
+ *      MPFMT_ERR_ARG: as the primitive, plus a path of fewer than 2 states, iterations < 0, max_states below a path's length or above 2^16;
+ *        MPFMT_ERR_STATE as the primitive.  sum of n_out > out_cap: MPFMT_ERR_CAPACITY with info and out_offsets written (out_cap == 0 with
+ *        NULL outputs is the size query; B * max_states always suffices).  A refused call leaves the ctx as it was.  There is no host
+ *        twin: the library has no host restatement of the steering sweeps.  Timer "steer_shortcut_batch"; stats
+ *        "steer_shortcut_tests_evaluated", "steer_shortcut_checks" (last batch). */
+typedef struct {
+    int32_t status;            /* MPFMT_SHORTCUT_DONE / _TRUNCATED */
+    int32_t iterations_done;
+    int64_t n_out;             /* states of the returned path */
+    int64_t max_working_len;
+    int64_t inserted;
+    int64_t legs_blocked;
+    int64_t collision_checks;
+    int64_t tests_evaluated;
+    double cost_in, cost_out;
+} mpfmt_steer_shortcut_info;
+MPFMT_API int32_t mpfmt_steer_motions_free(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, const double* Q,
+                                 int64_t n, uint64_t* mask, double* cost, double* dur, int32_t* nseg);
+MPFMT_API int32_t mpfmt_steer_shortcut_batch(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P,
+                                   const int64_t* offsets, int64_t B, int32_t iterations, int64_t max_states, double* out_P,
+                                   int64_t* out_offsets, int64_t out_cap, double* cumcost, int32_t* out_origin,
+                                   mpfmt_steer_shortcut_info* info);
+MPFMT_API int32_t mpfmt_steer_shortcut(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, int64_t n,
+                             int32_t iterations, int64_t max_states, double* out_P, int64_t out_cap, double* cumcost, int32_t* out_origin,
+                             mpfmt_steer_shortcut_info* info);
+
 /* ---- Monte-Carlo collision probability of candidate edges (BASELINE.json configs[4]).  The reference
  *      has no implementation (README.md:9-10 cites the papers only); the workload is the one SURVEY 8d defines: per edge
  *      (src[e] -> dst[e], 1-based sample indices) `rollouts` perturbed copies of the 2-point trajectory, each put through

@@ -417,6 +417,38 @@ function hip_adaptive_shortcut!(P::MPProblem, iterations::Int = 10; max_states::
     cum[n]
 end
 
+# ---- post-processing in the steering spaces (include/mpfmt.h, "steering shortcut"): the pair primitive and the batched shortcut.
+#      space: 1 double integrator (params (rho, tmax)), 2 Dubins, 3 Reeds-Shepp (params (turn radius, speed)); the checker of ctx is the
+#      one the last upload bound.  P, Q: d x n column-major.
+const sym_steer_motions_free = :mpfmt_steer_motions_free
+const sym_steer_shortcut_batch = :mpfmt_steer_shortcut_batch
+immutable SteerShortcutInfo
+    status::Int32; iterations_done::Int32; n_out::Int64; max_working_len::Int64; inserted::Int64; legs_blocked::Int64
+    collision_checks::Int64; tests_evaluated::Int64; cost_in::Float64; cost_out::Float64
+end
+function hip_steer_motions_free(ctx::Ptr{Void}, space::Integer, params::Vector{Float64}, P::Matrix{Float64}, Q::Matrix{Float64})
+    d, n = size(P)
+    mask = zeros(UInt64, max(div(n + 63, 64), 1)); cost = Vector{Float64}(n); dur = Vector{Float64}(n); nseg = Vector{Int32}(n)
+    chk(ctx, ccall((sym_steer_motions_free, libmpfmt), Int32,
+                   (Ptr{Void}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{UInt64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                   ctx, space, d, params, P, Q, n, mask, cost, dur, nseg))
+    [(mask[div(e - 1, 64) + 1] >> ((e - 1) % 64)) & 1 == 1 for e in 1:n], cost, dur, nseg
+end
+# paths: a vector of d x n_b matrices -> a vector of (path, cumcost, origin, info)
+function hip_steer_shortcut(ctx::Ptr{Void}, space::Integer, params::Vector{Float64}, paths::Vector{Matrix{Float64}}, iterations::Int = 4;
+                            max_states::Int = 256)
+    B = length(paths); d = size(paths[1], 1)
+    offsets = cumsum(vcat(Int64[0], Int64[size(p, 2) for p in paths])); P = hcat(paths...)
+    cap = B * max_states
+    out = Matrix{Float64}(d, cap); cum = Vector{Float64}(cap); org = Vector{Int32}(cap); out_off = Vector{Int64}(B + 1)
+    info = Vector{SteerShortcutInfo}(B)
+    chk(ctx, ccall((sym_steer_shortcut_batch, libmpfmt), Int32,
+                   (Ptr{Void}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Int64, Int32, Int64, Ptr{Float64}, Ptr{Int64}, Int64, Ptr{Float64},
+                    Ptr{Int32}, Ptr{SteerShortcutInfo}),
+                   ctx, space, d, params, P, offsets, B, iterations, max_states, out, out_off, cap, cum, org, info))
+    [(out[:, out_off[b]+1:out_off[b+1]], cum[out_off[b]+1:out_off[b+1]], org[out_off[b]+1:out_off[b+1]], info[b]) for b in 1:B]
+end
+
 # ---- multi-GPU: ONE Julia thread, G ctxs (SURVEY 8e); the RCCL exchange lives behind the ABI ------------------------
 function hip_comm_create!(ctxs::Vector{Ptr{Void}})
     id = Vector{UInt8}(128)

@@ -11,5 +11,6 @@ from .mirror import *  # noqa: F401,F403  (the reference's names: MPProblem, Uni
 from ._lib import Context, MPFMTError  # noqa: F401
 from ._lib import host_discretize, SPACE_EUCLID, SPACE_DI, SPACE_DUBINS, SPACE_REEDSSHEPP  # noqa: F401
 from .mirror import time_discretize_solution_, time_space_solution_, discretize_paths_  # noqa: F401
+from .mirror import steer_shortcut_, steer_shortcut_paths_  # noqa: F401
 
 __version__ = "0.1.0"

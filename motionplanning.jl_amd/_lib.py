@@ -80,7 +80,14 @@ class DiscInfo(C.Structure):
     _fields_ = [("n_out", C.c_int64), ("steps", C.c_int64), ("duration", C.c_double)]
 
 
+class SteerShortcutInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations_done", C.c_int32), ("n_out", C.c_int64), ("max_working_len", C.c_int64),
+                ("inserted", C.c_int64), ("legs_blocked", C.c_int64), ("collision_checks", C.c_int64), ("tests_evaluated", C.c_int64),
+                ("cost_in", C.c_double), ("cost_out", C.c_double)]
+
+
 SHORTCUT_DONE, SHORTCUT_TRUNCATED, SHORTCUT_STUCK = 0, 1, 2
+STEER_SHORTCUT_SLACK = 1.0 + 2.0 ** -30          # the acceptance slack of the steering shortcut (include/mpfmt.h), exact in binary64
 DI_MF_PROBE_TERMS = 16                # MPFMT_DI_MF_PROBE_TERMS
 SPACE_EUCLID, SPACE_DI, SPACE_DUBINS, SPACE_REEDSSHEPP = 0, 1, 2, 3
 DISC_DT, DISC_N = 0, 1
@@ -181,6 +188,12 @@ SYMBOLS = [
                                            C.c_int32, c_d_p, c_d_p, C.POINTER(C.c_int32), c_i64_p, C.c_int64, C.POINTER(DiscInfo)]),
     ("mpfmt_discretize", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, c_d_p, c_d_p, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, c_d_p,
                                      c_d_p, C.POINTER(C.c_int32), C.c_int64, C.POINTER(DiscInfo)]),
+    ("mpfmt_steer_motions_free", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, c_d_p, c_d_p, c_d_p, C.c_int64, c_u64_p, c_d_p, c_d_p,
+                                             C.POINTER(C.c_int32)]),
+    ("mpfmt_steer_shortcut_batch", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, c_d_p, c_d_p, c_i64_p, C.c_int64, C.c_int32, C.c_int64, c_d_p,
+                                               c_i64_p, C.c_int64, c_d_p, C.POINTER(C.c_int32), C.POINTER(SteerShortcutInfo)]),
+    ("mpfmt_steer_shortcut", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, c_d_p, c_d_p, C.c_int64, C.c_int32, C.c_int64, c_d_p, C.c_int64,
+                                         c_d_p, C.POINTER(C.c_int32), C.POINTER(SteerShortcutInfo)]),
     ("mpfmt_mc_edges_collision", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, c_i64_p]),
     ("mpfmt_mc_edges_collision_is", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("mpfmt_mc_edges_collision_ais", C.c_int32, [C.c_void_p, c_i64_p, c_i64_p, C.c_int64, C.c_double, C.c_int64, C.c_uint64, C.POINTER(C.c_uint64),
@@ -532,6 +545,19 @@ def host_adaptive_shortcut(path, lohi, ss_lo=None, ss_hi=None, iterations=10, ma
     if rc != 0:
         raise MPFMTError(rc, "mpfmt_host_adaptive_shortcut rejected its arguments")
     return out[:info.n_out].copy(), cc[:info.n_out].copy(), _shortcut_info(info)
+
+
+def _steer_shortcut_info(i):
+    return dict(status=int(i.status), iterations_done=int(i.iterations_done), n_out=int(i.n_out), max_working_len=int(i.max_working_len),
+                inserted=int(i.inserted), legs_blocked=int(i.legs_blocked), collision_checks=int(i.collision_checks),
+                tests_evaluated=int(i.tests_evaluated), cost_in=float(i.cost_in), cost_out=float(i.cost_out))
+
+
+def _steer_params(space, params):
+    prm = None if params is None else np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
+    if prm is None or prm.size != 2:
+        raise ValueError("params = (rho, tmax) for the double integrator, (turn_radius, speed) for the cars")
+    return prm
 
 
 def _disc_info(i):
@@ -1398,6 +1424,61 @@ class Context:
             self._chk(rc)
             break
         return [(out[out_off[b]:out_off[b + 1]].copy(), cc[out_off[b]:out_off[b + 1]].copy(), _shortcut_info(info[b])) for b in range(B)]
+
+    def steer_motions_free(self, space, params, P, Q):
+        """The steered motions P[e] -> Q[e] under the resident checker (include/mpfmt.h, "steering shortcut"): (bits (n,) bool, cost (n,),
+        dur (n,), nseg (n,) int32).  space: SPACE_DI / _DUBINS / _REEDSSHEPP; params: (rho, tmax) or (turn_radius, speed).  The bit is
+        is_free_motion exactly as the space's graph sweep computes it; no samples and no graph are needed."""
+        P = np.ascontiguousarray(P, dtype=np.float64); Q = np.ascontiguousarray(Q, dtype=np.float64)
+        if P.ndim != 2 or P.shape != Q.shape:
+            raise ValueError("P and Q must both be (n, d)")
+        prm = _steer_params(space, params)
+        n, d = P.shape
+        mask = np.zeros(max(nwords(n), 1), dtype=np.uint64)
+        cost = np.empty(max(n, 1)); dur = np.empty(max(n, 1)); nseg = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self._L.mpfmt_steer_motions_free(self._h, int(space), d, _dp(prm), _dp(P), _dp(Q), n, _up(mask), _dp(cost), _dp(dur), _ip32(nseg)))
+        return unpack_bits(mask, n), cost[:n], dur[:n], nseg[:n]
+
+    def steer_shortcut(self, paths, space, params, iterations=4, max_states=256):
+        """Shortcut of a batch of paths in a steering space under the resident checker, one wavefront per path (include/mpfmt.h,
+        "steering shortcut").  paths: a list of (n_i, d) arrays -> a list of (path, cumcost, origin, info) tuples; one (n, d) array -> one
+        tuple.  origin: the 1-based input index of every output state, 0 for an inserted one."""
+        single = isinstance(paths, np.ndarray) and paths.ndim == 2
+        plist = [np.ascontiguousarray(p, dtype=np.float64) for p in ([paths] if single else list(paths))]
+        for p in plist:
+            if p.ndim != 2 or p.shape[1] != plist[0].shape[1]:
+                raise ValueError("every path must be (n, d) with one d")
+        prm = _steer_params(space, params)
+        B = len(plist)
+        if B == 0:
+            return []
+        d = plist[0].shape[1]
+        if single:
+            P = plist[0]
+            cap = max(int(max_states), 2)
+            info = SteerShortcutInfo()
+            out = np.empty((cap, d)); cc = np.empty(cap); org = np.zeros(cap, dtype=np.int32)
+            self._chk(self._L.mpfmt_steer_shortcut(self._h, int(space), d, _dp(prm), _dp(P), P.shape[0], int(iterations), int(max_states), _dp(out),
+                                                   cap, _dp(cc), _ip32(org), C.byref(info)))
+            n = int(info.n_out)
+            return out[:n].copy(), cc[:n].copy(), org[:n].copy(), _steer_shortcut_info(info)
+        off = np.zeros(B + 1, dtype=np.int64)
+        off[1:] = np.cumsum([p.shape[0] for p in plist])
+        P = np.ascontiguousarray(np.concatenate(plist, axis=0))
+        info = (SteerShortcutInfo * B)()
+        out_off = np.zeros(B + 1, dtype=np.int64)
+        cap = max(int(off[-1]), 1)                       # most outputs are shorter than their inputs; grow once when they are not
+        for _ in range(2):
+            out = np.empty((cap, d)); cc = np.empty(cap); org = np.zeros(cap, dtype=np.int32)
+            rc = self._L.mpfmt_steer_shortcut_batch(self._h, int(space), d, _dp(prm), _dp(P), _ip(off), B, int(iterations), int(max_states),
+                                                    _dp(out), _ip(out_off), cap, _dp(cc), _ip32(org), info)
+            if rc == ERR_CAPACITY and int(out_off[-1]) > cap:
+                cap = int(out_off[-1])
+                continue
+            self._chk(rc)
+            break
+        return [(out[out_off[b]:out_off[b + 1]].copy(), cc[out_off[b]:out_off[b + 1]].copy(), org[out_off[b]:out_off[b + 1]].copy(),
+                 _steer_shortcut_info(info[b])) for b in range(B)]
 
     def discretize(self, paths, space, params=None, dt=None, n=None, append_end=False):
         """Time discretisation of a batch of paths on the device, lane = output sample (include/mpfmt.h, "time discretisation"):

@@ -1754,6 +1754,78 @@ int32_t mpfmt_discretize(mpfmt_ctx* ctx, int32_t space, int32_t d, const double*
                                   info);
 }
 
+// ---- steering shortcut (kernels_steershortcut.hip): the pair primitive and the batch --------------------------------------------------------
+// space / d / params and the resident checker, bound as the space's graph sweep expects it
+static int32_t steer_space_check(mpfmt_ctx* ctx, const char* who, int32_t space, int32_t d, const double* params)
+{
+    if (space == MPFMT_SPACE_EUCLID) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%s: a steering space is needed (the Euclidean calls are mpfmt_motions_free / mpfmt_adaptive_shortcut)", who);
+    if (const char* why = mpfmt_disc_check(space, d, params, MPFMT_DISC_N, 0.0, 2)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "%s: %s", who, why);
+    if (ctx->world != 1) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "%s runs on an unsharded ctx", who);
+    if (!ctx->have_boxes) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "%s: no obstacle set uploaded (mpfmt_upload_boxes / mpfmt_upload_shapes2d)", who);
+    const int dw = space == MPFMT_SPACE_DI ? d / 2 : 2;
+    if (ctx->dw != dw) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "%s: the checker's workspace has %d dims, the space needs %d", who, ctx->dw, dw);
+    if (ctx->ss.has && ctx->ss.d != d) return mpfmt_fail(ctx, MPFMT_ERR_STATE, "%s: state-space bounds have %d dims, states %d", who, ctx->ss.d, d);
+    return MPFMT_OK;
+}
+
+int32_t mpfmt_steer_motions_free(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, const double* Q, int64_t n,
+                                 uint64_t* mask, double* cost, double* dur, int32_t* nseg)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (n < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_motions_free: n < 0");
+    if (n > 0 && (!P || !Q || !mask)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_motions_free: P / Q / mask is NULL");
+    int32_t rc;
+    if ((rc = steer_space_check(ctx, "steer_motions_free", space, d, params))) return rc;
+    if (n > (int64_t)1 << 40) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_motions_free: more than 2^40 pairs");
+    for (int64_t i = 0; i < n * d; ++i)
+        if (!std::isfinite(P[i]) || !std::isfinite(Q[i])) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_motions_free: non-finite coordinate in pair %lld", (long long)(i / d + 1));
+    if (n == 0) return MPFMT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return mpfmt_steer_pairs_device(ctx, space, d, params, P, Q, n, mask, cost, dur, nseg);
+}
+
+int32_t mpfmt_steer_shortcut_batch(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, const int64_t* offsets,
+                                   int64_t B, int32_t iterations, int64_t max_states, double* out_P, int64_t* out_offsets, int64_t out_cap,
+                                   double* cumcost, int32_t* out_origin, mpfmt_steer_shortcut_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (B < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: B < 0");
+    if (!offsets || !out_offsets) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: offsets / out_offsets is NULL");
+    if (B > 0 && (!P || !info)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: P / info is NULL");
+    if (out_cap < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: out_cap < 0");
+    if (B > 0 && out_cap > 0 && (!out_P || !cumcost)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: out_P / cumcost is NULL");
+    if (iterations < 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: iterations < 0");
+    if (max_states < 2 || max_states > (1 << 16)) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: max_states must lie in [2, 2^16]");
+    int32_t rc;
+    if ((rc = steer_space_check(ctx, "steer_shortcut", space, d, params))) return rc;
+    if (offsets[0] != 0) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: offsets[0] must be 0");
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t n = offsets[b + 1] - offsets[b];
+        if (n < 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: path %lld has %lld states (a path has at least 2)", (long long)(b + 1), (long long)n);
+        if (n > max_states) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: path %lld has %lld states > max_states = %lld", (long long)(b + 1), (long long)n, (long long)max_states);
+    }
+    const int64_t total = offsets[B];
+    for (int64_t i = 0; i < total * d; ++i)
+        if (!std::isfinite(P[i])) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: non-finite coordinate in state %lld", (long long)(i / d + 1));
+    out_offsets[0] = 0;
+    if (B == 0) return MPFMT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return mpfmt_steer_shortcut_batch_device(ctx, space, d, params, P, offsets, B, iterations, max_states, out_P, out_offsets, out_cap, cumcost,
+                                             out_origin, info);
+}
+
+int32_t mpfmt_steer_shortcut(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, int64_t n, int32_t iterations,
+                             int64_t max_states, double* out_P, int64_t out_cap, double* cumcost, int32_t* out_origin,
+                             mpfmt_steer_shortcut_info* info)
+{
+    if (!ctx) return MPFMT_ERR_ARG;
+    if (n < 2) return mpfmt_fail(ctx, MPFMT_ERR_ARG, "steer_shortcut: a path has at least 2 states");
+    const int64_t offsets[2] = {0, n};
+    int64_t out_offsets[2] = {0, 0};
+    return mpfmt_steer_shortcut_batch(ctx, space, d, params, P, offsets, 1, iterations, max_states, out_P, out_offsets, out_cap, cumcost, out_origin,
+                                      info);
+}
+
 // ---- steering spaces: double integrator (LinearQuadratic quasi-metric), Dubins and Reeds-Shepp cars (kernels_di.hip, kernels_car.hip)
 
 static int32_t di_check(mpfmt_ctx* ctx, double rho, double r)
@@ -2903,6 +2975,8 @@ int32_t mpfmt_get_stat(mpfmt_ctx* ctx, const char* name, int64_t* value)
     if (strcmp(name, "steer_roadmap_steered") == 0) { *value = ctx->steer_roadmap_steered; return MPFMT_OK; }
     if (strcmp(name, "shortcut_tests_evaluated") == 0) { *value = ctx->shortcut_tests; return MPFMT_OK; }
     if (strcmp(name, "shortcut_checks") == 0) { *value = ctx->shortcut_checks; return MPFMT_OK; }
+    if (strcmp(name, "steer_shortcut_tests_evaluated") == 0) { *value = ctx->ssc_tests; return MPFMT_OK; }
+    if (strcmp(name, "steer_shortcut_checks") == 0) { *value = ctx->ssc_checks; return MPFMT_OK; }
     if (strcmp(name, "discretize_steps") == 0) { *value = ctx->disc_steps; return MPFMT_OK; }
     if (strcmp(name, "discretize_samples") == 0) { *value = ctx->disc_samples; return MPFMT_OK; }
     if (strcmp(name, "steer_swept") == 0) { *value = (ctx->steer_filled && ctx->steer_swept) ? 1 : 0; return MPFMT_OK; }

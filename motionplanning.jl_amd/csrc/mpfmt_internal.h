@@ -433,6 +433,7 @@ struct mpfmt_ctx {
 
     // ---- adaptive shortcutting (kernels_shortcut.hip): stats of the last batch ----
     int64_t shortcut_tests = 0, shortcut_checks = 0;
+    int64_t ssc_tests = 0, ssc_checks = 0;       // the same for the steering shortcut (kernels_steershortcut.hip)
     // ---- time discretisation (kernels_discretize.hip): stats of the last batch ----
     int64_t disc_steps = 0, disc_samples = 0;
 
@@ -738,6 +739,14 @@ int32_t mpfmt_shortcut_batch_device(mpfmt_ctx* ctx, const double* P, const int64
 int32_t mpfmt_discretize_batch_device(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, const int64_t* offsets,
                                       int64_t B, int32_t mode, double dt, int64_t n_samples, int32_t append_end, double* out_X, double* out_T,
                                       int32_t* out_seg, int64_t* out_offsets, int64_t out_cap, mpfmt_disc_info* info);
+
+// kernels_steershortcut.hip ------------------------------------------------------------------------
+// the pair primitive and the batch on the device; arguments already validated (mpfmt_steer_motions_free, mpfmt_steer_shortcut_batch)
+int32_t mpfmt_steer_pairs_device(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, const double* Q, int64_t n,
+                                 uint64_t* mask, double* cost, double* dur, int32_t* nseg);
+int32_t mpfmt_steer_shortcut_batch_device(mpfmt_ctx* ctx, int32_t space, int32_t d, const double* params, const double* P, const int64_t* offsets,
+                                          int64_t B, int32_t iterations, int64_t max_states, double* out_P, int64_t* out_offsets, int64_t out_cap,
+                                          double* cumcost, int32_t* out_origin, mpfmt_steer_shortcut_info* info);
 
 // kernels_expand.hip ----------------------------------------------------------------------------
 int32_t mpfmt_launch_expand(mpfmt_ctx* ctx, const uint64_t* d_W, const uint64_t* d_H, const uint64_t* d_F,

@@ -421,13 +421,32 @@ def is_free_state(v, CC, SS, ctx):
     return bool(out[0]) if np.ndim(v) == 1 else out
 
 
-def is_free_motion(v, w, CC, SS, ctx):
+def _steer_space(SS, tmax=None):
+    """(space, params) of the steering calls for SS; the double integrator's Newton bracket is tmax (default: the space's cost radius)."""
+    dist = SS.dist
+    if isinstance(dist, LinearQuadratic):
+        return _lib.SPACE_DI, (dist.rho, float(dist.cmax if tmax is None else tmax))
+    if isinstance(dist, DubinsExact):
+        return _lib.SPACE_DUBINS, (dist.r, dist.s)
+    if isinstance(dist, ReedsSheppExact):
+        return _lib.SPACE_REEDSSHEPP, (dist.r, dist.s)
+    raise ValueError("not a steering space")
+
+
+def is_free_motion(v, w, CC, SS, ctx, tmax=None):
     """Euclidean space: in_state_space(v) && segment test (statespaces.jl:153-158, geometric.jl:20); counts like
-    boxesND.jl:26.  v, w: (d,) or (n, d)."""
+    boxesND.jl:26.  The steering spaces: the steered motion v -> w over the space's collision waypoints, as the graph sweep tests an
+    edge (include/mpfmt.h, "steering shortcut"; the double integrator's Newton bracket is tmax, default the space's cost radius);
+    CC.count gains the segment tests.  v, w: (d,) or (n, d)."""
     V = np.atleast_2d(np.asarray(v, dtype=np.float64))
     W = np.atleast_2d(np.asarray(w, dtype=np.float64))
     if not isinstance(SS.dist, Euclidean):
-        raise NotImplementedError("scalar is_free_motion is provided for the Euclidean space; use fmtstar_ for LQ")
+        if CC._ctx is not ctx or CC._ss is not SS:
+            CC._bind(ctx, SS)
+        space, params = _steer_space(SS, tmax)
+        out, _, _, nseg = ctx.steer_motions_free(space, params, V, W)
+        CC.count += int(np.sum(nseg))
+        return bool(out[0]) if np.ndim(v) == 1 else out
     if CC._ctx is not ctx or CC._ss is not SS:
         CC._bind(ctx, SS)
     CC.count += int(np.sum(np.all((SS.lo <= V) & (V <= SS.hi), axis=1)))
@@ -1033,6 +1052,62 @@ def smooth_solution_(P):
     return None
 
 
+def _require_steer_shortcut(P):
+    if isinstance(P.SS.dist, Euclidean):
+        raise RuntimeError("steer_shortcut_ is for the steering spaces; a Euclidean problem is smoothed by adaptive_shortcut_")
+
+
+def steer_shortcut_(P, iterations=4, max_states=256, tmax=None):
+    """Shortcut of the solution of a solved double-integrator, Dubins or Reeds-Shepp problem on the device (include/mpfmt.h, "steering
+    shortcut"): fills metadata["smoothed_path"] (n, d), ["smoothed_cumcost"], ["smoothed_cost"], ["smoothed_origin"] and
+    ["smoothed_info"], adds the checks to P.CC.count and returns the smoothed cost.  The double integrator's Newton bracket tmax
+    defaults to the input path's cost (cost >= duration, so no improving connection needs a longer bracket).  (space, params) are kept in
+    metadata["smoothed_steer_params"]: time_discretize_solution_ / time_space_solution_ of the smoothed path steer its legs with THAT
+    bracket, not with the radius the plan was made with, which the reconnected legs may exceed."""
+    if P.status != "solved":
+        raise RuntimeError("Cannot post-process unsolved problem! (steer-shortcut)")
+    _require_steer_shortcut(P)
+    S = P.solution
+    if tmax is None and isinstance(P.SS.dist, LinearQuadratic):
+        tmax = float(S.cost)
+    space, params = _steer_space(P.SS, tmax)
+    P.CC._bind(P.ctx, P.SS)
+    path, cum, org, info = P.ctx.steer_shortcut(np.ascontiguousarray(P.V.V[S.metadata["path"] - 1]), space, params, iterations, max_states)
+    P.CC.count += info["collision_checks"]
+    S.metadata["smoothed_path"] = path
+    S.metadata["smoothed_cumcost"] = cum
+    S.metadata["smoothed_cost"] = float(cum[-1])
+    S.metadata["smoothed_origin"] = org
+    S.metadata["smoothed_info"] = info
+    S.metadata["smoothed_steer_params"] = (space, params)
+    return float(cum[-1])
+
+
+def steer_shortcut_paths_(P, nodes, iterations=4, max_states=256, tmax=None):
+    """The multi-query use after fmtstar_ / prmstar_ in a steering space: the tree paths from init to every sample of `nodes` (1-based; out
+    of metadata["tree"]) shortcut as ONE batch on the device.  Returns a list of (path, cumcost, origin, info), one per node, and adds
+    all checks to P.CC.count.  The double integrator's bracket tmax defaults to the largest cost-to-come of `nodes`."""
+    if P.solution is None or "tree" not in P.solution.metadata:
+        raise RuntimeError("Cannot post-process unsolved problem! (steer-shortcut)")
+    _require_steer_shortcut(P)
+    root = int(P.solution.metadata["path"][0])
+    idx = tree_paths(P.solution.metadata["tree"], nodes, root)
+    paths = [np.ascontiguousarray(P.V.V[p - 1]) for p in idx]
+    P.CC._bind(P.ctx, P.SS)
+    if tmax is None and isinstance(P.SS.dist, LinearQuadratic):
+        C = P.solution.metadata.get("cost_to_come")
+        if C is not None:
+            tmax = float(max(C[int(v) - 1] for v in nodes))
+        else:                                                 # the tree's legs cost at most the radius: steer them with that bracket and sum
+            space, params = _steer_space(P.SS)
+            legs = [P.ctx.steer_motions_free(space, params, p[:-1], p[1:])[1] for p in paths if len(p) > 1]
+            tmax = float(max([float(np.sum(c)) for c in legs] + [P.SS.dist.cmax]))
+    space, params = _steer_space(P.SS, tmax)
+    out = P.ctx.steer_shortcut(paths, space, params, iterations, max_states)
+    P.CC.count += sum(i["collision_checks"] for _, _, _, i in out)
+    return out
+
+
 def shortcut_paths_(P, nodes, iterations=10, max_states=256):
     """The multi-query use after prmstar_ / fmtstar_: the tree paths from init to every sample of `nodes` (1-based; out of
     metadata["tree"]) smoothed as ONE batch on the device.  Returns a list of (path, cumcost, info), one per node, and adds all
@@ -1076,6 +1151,8 @@ def _solution_states(P, usesmoothed):
 def _discretize_solution(P, usesmoothed, **kw):
     path = _solution_states(P, usesmoothed)
     space, params = _disc_space(P)
+    if usesmoothed and "smoothed_steer_params" in P.solution.metadata:      # a steer_shortcut_ path: the bracket its legs were steered with
+        space, params = P.solution.metadata["smoothed_steer_params"]
     (X, T, seg), info = P.ctx.discretize(path, space, params, **kw)
     S = P.solution
     S.metadata["discretized_path"] = X
